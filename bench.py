@@ -6,7 +6,12 @@ detokenize (TiTok decoder + conv upsampler) -> 50 sampler steps over the control
 seeded random-init weights are resident in HBM before the timed region.  N > 1: one process per GPU
 (torchrun), prompts sharded data-parallel, one RCCL all_gather of the finished uint8 frames per step.
 
+A plain run sets up, warms up, times --steps steps and prints the result line (metric, value, unit, ms_per_step, dtype, config,
+stage seconds).  --full adds what takes runs or passes of its own: box calibration, sclk / power sampling, attention and GEMM
+roofline figures, per-rank reports and the CPU baseline.  --dump-outputs DIR writes the last timed step's frames as .npy files.
+
   python bench.py --gpus 1 --steps 1 --warmup 1
+  python bench.py --gpus 1 --steps 1 --warmup 1 --full
 """
 from __future__ import annotations
 
@@ -299,6 +304,24 @@ def llm_step_bytes(c) -> float:
     return c.num_layers * per_layer + c.vocab * c.hidden * 4
 
 
+DUMP_MAX_ELEMS = 1 << 22        # per dumped array: 16 MB of float32 (a 49-frame 480x720 video holds 50.8 M values)
+
+
+def dump_outputs(outputs: dict, out_dir: str, max_elems: int = DUMP_MAX_ELEMS) -> None:
+    """out_dir/<name>.npy in float32 for every array: whole up to max_elems elements, else max_elems values at flat indices drawn
+    by a CPU generator seeded with 0 (with replacement, ascending) -- the same positions in every run and every build."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        flat = t.reshape(-1)
+        if flat.numel() > max_elems:
+            idx = torch.randint(flat.numel(), (max_elems,), generator=torch.Generator().manual_seed(0)).sort().values
+            arr = flat[idx.to(flat.device)]
+        else:
+            arr = t
+        np.save(os.path.join(out_dir, name + ".npy"), arr.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -322,7 +345,16 @@ def main():
                          "on the MI355X kernels -- FLAN-T5-XXL over 64 prompt tokens (LLM condition) and T5-v1.1-XXL over 226 padded "
                          "tokens (DiT context), random-init weights at true shapes -- and feeds their states to the pipeline; the "
                          "stage appears as `t5` in stage_seconds_rank0.  Not the BASELINE metric (which starts at the encoder outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: box calibration and sclk / power sampling, HIP events around the "
+                         "attention launches, one extra GEMM-timed step, the roofline objects, per-rank reports and (unless "
+                         "--no-cpu-baseline) the CPU baseline.  Off: set up, warm up, time --steps steps, print the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (the uint8 frames) as DIR/<name>.npy in float32: "
+                         f"whole up to {DUMP_MAX_ELEMS} elements, else a fixed seeded sample of that many")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.with_t5 and (args.tiny or args.stream_chunks or args.prompts_per_step > 1):
         raise SystemExit("--with-t5 applies to the headline workload only")
     if args.prompts_per_step > 1 and (args.stream_chunks or args.fp8_gemm or args.tiny):
@@ -399,21 +431,27 @@ def main():
 
     for _ in range(args.warmup):
         one_step()
-    sampler = ClockPowerSampler(dev)
-    calib = calibrate(dev, sampler)           # EVERY rank: the pool's GPUs differ by +-5 % under the power cap (per_rank.calibration)
+    # a plain run times the steps and nothing else; --full adds the box calibration, the clock / power sampler and the HIP events
+    # around every attention launch
+    sampler = calib = clocks = None
+    if args.full:
+        sampler = ClockPowerSampler(dev)
+        calib = calibrate(dev, sampler)           # EVERY rank: the pool's GPUs differ by +-5 % under the power cap (per_rank.calibration)
+        pipe.dit.attn_events = []                 # HIP events around every attention launch: the roofline object's `achieved`
+        pipe.dit.gemm_events = None               # (the GEMM events are collected in a separate, untimed step below)
     pipe.timings = {}
-    pipe.dit.attn_events = []                 # HIP events around every attention launch: the roofline object's `achieved`
-    pipe.dit.gemm_events = None               # (the GEMM events are collected in a separate, untimed step below)
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
-    sampler.start()
+    if sampler is not None:
+        sampler.start()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = one_step()
     torch.cuda.synchronize()
     local_elapsed = time.perf_counter() - t0
-    clocks = sampler.stop()
+    if sampler is not None:
+        clocks = sampler.stop()
     if use_dist:
         dist.barrier()
     elapsed = time.perf_counter() - t0
@@ -424,109 +462,30 @@ def main():
 
     n_frames = out[0].shape[1]
     stage_s = {k: v / args.steps for k, v in pipe.timings.items()}
-    gemm_step_s = None
-    if rank == 0 and P == 1 and not args.tiny and (not stream or args.fp8_gemm):      # (bf16 streaming runs: the headline line carries the figure)
-        # one more step OUTSIDE the timed region with HIP events around every large DiT Linear (~20 k event records per video
-        # would otherwise sit in the headline number)
-        keep_t, keep_a, keep_o = pipe.timings, pipe.dit.attn_events, pipe.dit.overlap
-        pipe.timings, pipe.dit.attn_events, pipe.dit.gemm_events = {}, None, []
-        pipe.dit.overlap = False                  # serial step: every GEMM launch has the GPU to itself while it is timed
-        pipe(inp)                                 # rank 0 only: NOT one_step(), whose frame gather is a collective every rank must enter
-        torch.cuda.synchronize()
-        gemm_step_s = dict(pipe.timings)
-        pipe.timings, pipe.dit.attn_events, pipe.dit.overlap = keep_t, keep_a, keep_o
-    reports = gather_rank_reports({"rank": rank, "frames_per_s": round(n_frames * args.steps / local_elapsed, 4),
-                                   "stage_seconds": {k: round(v, 3) for k, v in stage_s.items()},
-                                   "cores": len(my_cores) if my_cores else None,
-                                   "calibration": {"mfma_tflops": calib["mfma_tflops"], "hbm_gbs": calib["hbm_gbs"],
-                                                   "mfma_loop_sclk_mhz": calib["mfma_loop_sclk_mhz"],
-                                                   "timed_region_sclk_mhz": clocks["mean_sclk_mhz"] if clocks else None,
-                                                   "timed_region_power_w": clocks["mean_power_w"] if clocks else None}},
-                                  world if use_dist else 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs({"frames": torch.cat(out)}, args.dump_outputs)        # the last step's gathered uint8 frames [world, F, H, W, 3]
+    if args.full:
+        gemm_step_s = None
+        if rank == 0 and P == 1 and not args.tiny and (not stream or args.fp8_gemm):      # (bf16 streaming runs: the headline line carries the figure)
+            # one more step OUTSIDE the timed region with HIP events around every large DiT Linear (~20 k event records per video
+            # would otherwise sit in the headline number)
+            keep_t, keep_a, keep_o = pipe.timings, pipe.dit.attn_events, pipe.dit.overlap
+            pipe.timings, pipe.dit.attn_events, pipe.dit.gemm_events = {}, None, []
+            pipe.dit.overlap = False                  # serial step: every GEMM launch has the GPU to itself while it is timed
+            pipe(inp)                                 # rank 0 only: NOT one_step(), whose frame gather is a collective every rank must enter
+            torch.cuda.synchronize()
+            gemm_step_s = dict(pipe.timings)
+            pipe.timings, pipe.dit.attn_events, pipe.dit.overlap = keep_t, keep_a, keep_o
+        reports = gather_rank_reports({"rank": rank, "frames_per_s": round(n_frames * args.steps / local_elapsed, 4),
+                                       "stage_seconds": {k: round(v, 3) for k, v in stage_s.items()},
+                                       "cores": len(my_cores) if my_cores else None,
+                                       "calibration": {"mfma_tflops": calib["mfma_tflops"], "hbm_gbs": calib["hbm_gbs"],
+                                                       "mfma_loop_sclk_mhz": calib["mfma_loop_sclk_mhz"],
+                                                       "timed_region_sclk_mhz": clocks["mean_sclk_mhz"] if clocks else None,
+                                                       "timed_region_power_w": clocks["mean_power_w"] if clocks else None}},
+                                      world if use_dist else 1)
     if rank == 0:
         d = cfg.dit
-        ev_all = pipe.dit.attn_events
-        # With the control and the main chain overlapped on two streams (the default), a launch that has a partner shares the GPU
-        # with it and its event-to-event time is not the kernel's own: the kernel's duration is taken from the launches that run
-        # alone -- the main layers behind the last control state, 14 of a step's 45 -- all of them inside the timed region.
-        ev = [(a, b) for a, b, solo in ev_all if solo]
-        solo_rule = pipe.dit.overlap
-        if not ev:                    # (tiny configs: no main layer lies behind the last control state) every launch, and say so
-            ev, solo_rule = [(a, b) for a, b, _ in ev_all], False
-        attn_ms = sum(a.elapsed_time(b) for a, b in ev) / max(len(ev), 1)
-        attn_all_ms = sum(a.elapsed_time(b) for a, b, _ in ev_all) / max(len(ev_all), 1)
-        flops = 4.0 * 2 * d.heads * d.seq_len * d.seq_len * d.head_dim      # algorithmic FLOPs of one launch
-        achieved = flops / (attn_ms * 1e-3) / 1e12 if attn_ms > 0 else 0.0
-        peak = MFMA_BF16_PEAK
-        from landiff_amd import _lib
-        kname = (_lib.load().ld_attn_last_kernel() or b"").decode()      # what the launcher actually ran (shape + LD_ATTN_* knobs)
-        # the PMC traffic figure was collected on the default kernel at the headline shape only (profiles/, see ATTN_TRAFFIC)
-        headline = (not args.tiny and not stream and not args.fp8_gemm and kname == ATTN_TRAFFIC["kernel"]
-                    and not any(os.environ.get(k) for k in ("LD_ATTN_NW", "LD_ATTN_SAFE", "LD_ATTN_VARIANT", "LD_ATTN_MSUM", "LD_ATTN_Q64")))
-        attn_roof = {"kernel": "%s (DiT joint text+video attention, B=2,H=%d,N=%d,D=64)" % (kname, d.heads, d.seq_len),
-                     "bound": "mfma", "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
-                     "frac": round(achieved / peak, 4),
-                     "traffic": ATTN_TRAFFIC["bytes"] if headline else None, "traffic_source": ATTN_TRAFFIC["source"] if headline else None,
-                     "launches": len(ev), "launches_total": len(ev_all),
-                     "avg_launch_ms": round(attn_ms, 4), "avg_launch_ms_all_incl_overlapped": round(attn_all_ms, 4),
-                     "overlap": ("control chain on a second stream (LD_DIT_OVERLAP=1): `achieved` is over the launches that run alone"
-                                 if solo_rule else
-                                 "control chain on a second stream and NO launch runs alone in this configuration: `achieved` is over all launches, "
-                                 "whose event intervals include time shared with the other chain" if pipe.dit.overlap else
-                                 "serial step: every launch runs alone"),
-                     # the runner's per-layer choice between the default launch and ld_attn_fwd_bf16_exact (landiff_amd/dit.py):
-                     # with these weights no layer leaves the fast pass's window, so every launch above is the default kernel
-                     "attn_policy": {"mode": "auto" if pipe.dit.attn_auto else ("exact" if pipe.dit.attn_exact else "default"),
-                                     "layers_on_exact_form": len(pipe.dit.exact_layers)}}
-        # ---- per-stage achieved vs peak (rank 0) ----------------------------------------------------
-        stages = {"dit_attention": {k: attn_roof[k] for k in ("bound", "achieved", "peak", "unit", "frac")}}
-        stages["dit_attention"]["seconds_per_step"] = round(attn_ms * 1e-3 * len(ev_all) / args.steps, 3)
-        stages["dit_attention"]["what"] = ("the kernel's own duration (launches that run alone) x all launches of a step: GPU time, not wall time -- "
-                                           "overlapped launches take longer on the wall (avg_launch_ms_all_incl_overlapped)")
-        gev = pipe.dit.gemm_events
-        if gev:
-            # events of the e4m3 linears carry (flops, "mx"), the bf16 ones (all of them in the headline configuration; the control
-            # zero-linears under --fp8-gemm) plain flops
-            split = {"bf16": [0.0, 0.0, 0], "mx": [0.0, 0.0, 0]}
-            for a, b, f in gev:
-                kind = "bf16"
-                if isinstance(f, tuple):
-                    f, kind = f
-                acc = split[kind]
-                acc[0] += a.elapsed_time(b) * 1e-3; acc[1] += f; acc[2] += 1
-            what = ("HIP events around every qkv / dense / 4h / 4h->h Linear and control zero-linear of the DiT loop "
-                    "(2 M N K each; 3.145 TFLOP per layer-call + 0.262 per control layer), tail launches included; "
-                    "collected in ONE extra, serial step after the timed region (the headline loop carries no GEMM events)")
-            if split["bf16"][2]:
-                g_s, g_fl, n_ = split["bf16"]
-                g_ach = g_fl / g_s / 1e12
-                stages["dit_gemm"] = {"bound": "mfma", "achieved": round(g_ach, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(g_ach / peak, 4),
-                                      "seconds_per_step": round(g_s, 3), "launches": n_,
-                                      "what": what if not args.fp8_gemm else "the bf16 linears left under --fp8-gemm (control zero-linears); " + what}
-            if split["mx"][2]:
-                g_s, g_fl, n_ = split["mx"]
-                g_ach = g_fl / g_s / 1e12
-                stages["dit_gemm_mxfp8"] = {"bound": "mfma", "achieved": round(g_ach, 1), "peak": 2 * peak, "unit": "TFLOP/s", "frac": round(g_ach / (2 * peak), 4),
-                                            "seconds_per_step": round(g_s, 3), "launches": n_,
-                                            "what": "the e4m3 (MXFP8) qkv / dense / 4h / 4h->h linears against the dense MX-fp8 MFMA peak (~5 PFLOP/s); " + what}
-        if "detokenize" in stage_s and not stream and P == 1 and not args.tiny:
-            dtf = detok_tflop(cfg)
-            stages["detokenize"] = {"bound": "mfma", "achieved": round(dtf / stage_s["detokenize"], 1), "peak": peak, "unit": "TFLOP/s",
-                                    "frac": round(dtf / stage_s["detokenize"] / peak, 4), "seconds_per_step": round(stage_s["detokenize"], 4),
-                                    "what": "%.2f TFLOP (TiTok decoder linears + frame-masked attention at its mask density, conv upsampler, conv_out) "
-                                            "/ the detokenize stage's wall time" % dtf}
-        if "llm" in stage_s and not stream and P == 1 and not args.tiny:
-            steps_llm = 1244
-            gbs = llm_step_bytes(cfg.llm) * steps_llm / stage_s["llm"] / 1e9
-            stages["llm_decode"] = {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK, "unit": "GB/s", "frac": round(gbs / HBM_PEAK, 4),
-                                    "seconds_per_step": round(stage_s["llm"], 3),
-                                    "what": "%d decode steps x %.3f GB of weights (bf16 blocks + fp32 head) / the llm stage's wall time (prefill included)"
-                                            % (steps_llm, llm_step_bytes(cfg.llm) / 1e9)}
-        if "vae" in stage_s and not stream and P == 1 and not args.tiny:
-            tf = VAE_TFLOP / stage_s["vae"]
-            stages["vae_decode"] = {"bound": "mfma", "achieved": round(tf, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(tf / peak, 4),
-                                    "seconds_per_step": round(stage_s["vae"], 3),
-                                    "what": "315 TFLOP of causal 3D / 2D convolutions per 49-frame video / the vae stage's wall time (norm, upsample and uint8 passes included)"}
         serving = P > 1
         res = {
             "metric": (METRIC + " [SECONDARY: incl. both T5-XXL text encoders on the GPU, SURVEY 8d]") if args.with_t5 else METRIC if not serving else METRIC + " [SERVING MODE: %d prompts per GPU and step, AR decode overlapped -- not the BASELINE configuration]" % P,
@@ -549,38 +508,124 @@ def main():
                        "sampler_steps": cfg.sampler.num_steps, "llm_steps": (1244 if not stream else None) if not args.tiny else None,
                        "prompts_per_step": P,
                        "parallelism": f"dp{world} over prompts, RCCL all_gather of uint8 frames only"},
-            "roofline": attn_roof,
-            "roofline_stages": stages,
-            "stage_figures_note": "llm_decode / vae_decode / detokenize divide the stage's algorithmic bytes or FLOPs by its WALL time "
-                                  "(prefill, norm, upsample, uint8 passes and launch gaps included); dit_attention / dit_gemm are HIP-event "
-                                  "kernel times",
-            "calibration": dict(calib or {}, **({"timed_region": clocks} if clocks else {})),
         }
-        if calib:                # the same fractions against what THIS box sustained a few seconds earlier
-            boxc = {"dit_attention": round(achieved / calib["mfma_tflops"], 4)}
-            if "dit_gemm" in stages:
-                boxc["dit_gemm"] = round(stages["dit_gemm"]["achieved"] / calib["mfma_tflops"], 4)
-            if "vae_decode" in stages:
-                boxc["vae_decode"] = round(stages["vae_decode"]["achieved"] / calib["mfma_tflops"], 4)
-            if "llm_decode" in stages:
-                boxc["llm_decode"] = round(stages["llm_decode"]["achieved"] / calib["hbm_gbs"], 4)
-            res["frac_of_box_ceiling"] = boxc
         if not serving:            # generate_many records no per-stage wall times (its stages overlap)
             res["stage_seconds_rank0"] = {k: round(v, 3) for k, v in stage_s.items()}
-        if world > 1 or use_dist:
-            fps = [r["frames_per_s"] for r in reports]
+        if use_dist:
             res["n_ranks_seen"] = dist.get_world_size()          # what RCCL itself says the job size was
-            # What a rank's GPU sustained right before its timed region, so that a scaling curve can be read net of the pool's
-            # GPU-to-GPU spread (+-5 % under the power cap): frames_per_s_normalised = frames_per_s x (mean MFMA-only rate of the
-            # job's GPUs / this GPU's) -- a rank on a slow GPU is not a scaling loss.  Each rank's own wall time, before the MAX.
-            cal = [r["calibration"] for r in reports]
-            mean_mfma = sum(c["mfma_tflops"] for c in cal) / len(cal)
-            res["per_rank"] = {"frames_per_s_min": min(fps), "frames_per_s_max": max(fps), "frames_per_s": fps,
-                               "frames_per_s_normalised": [round(f * mean_mfma / c["mfma_tflops"], 4) for f, c in zip(fps, cal)],
-                               "calibration": cal, "calibration_mean_mfma_tflops": round(mean_mfma, 1),
-                               "stage_seconds": [r["stage_seconds"] for r in reports], "cores_per_rank": [r["cores"] for r in reports]}
-        if not args.no_cpu_baseline and world == 1:
-            res["cpu_baseline"] = cpu_baseline(PipelineConfig.full())
+        if args.full:
+            ev_all = pipe.dit.attn_events
+            # With the control and the main chain overlapped on two streams (the default), a launch that has a partner shares the GPU
+            # with it and its event-to-event time is not the kernel's own: the kernel's duration is taken from the launches that run
+            # alone -- the main layers behind the last control state, 14 of a step's 45 -- all of them inside the timed region.
+            ev = [(a, b) for a, b, solo in ev_all if solo]
+            solo_rule = pipe.dit.overlap
+            if not ev:                    # (tiny configs: no main layer lies behind the last control state) every launch, and say so
+                ev, solo_rule = [(a, b) for a, b, _ in ev_all], False
+            attn_ms = sum(a.elapsed_time(b) for a, b in ev) / max(len(ev), 1)
+            attn_all_ms = sum(a.elapsed_time(b) for a, b, _ in ev_all) / max(len(ev_all), 1)
+            flops = 4.0 * 2 * d.heads * d.seq_len * d.seq_len * d.head_dim      # algorithmic FLOPs of one launch
+            achieved = flops / (attn_ms * 1e-3) / 1e12 if attn_ms > 0 else 0.0
+            peak = MFMA_BF16_PEAK
+            from landiff_amd import _lib
+            kname = (_lib.load().ld_attn_last_kernel() or b"").decode()      # what the launcher actually ran (shape + LD_ATTN_* knobs)
+            # the PMC traffic figure was collected on the default kernel at the headline shape only (profiles/, see ATTN_TRAFFIC)
+            headline = (not args.tiny and not stream and not args.fp8_gemm and kname == ATTN_TRAFFIC["kernel"]
+                        and not any(os.environ.get(k) for k in ("LD_ATTN_NW", "LD_ATTN_SAFE", "LD_ATTN_VARIANT", "LD_ATTN_MSUM", "LD_ATTN_Q64")))
+            attn_roof = {"kernel": "%s (DiT joint text+video attention, B=2,H=%d,N=%d,D=64)" % (kname, d.heads, d.seq_len),
+                         "bound": "mfma", "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
+                         "frac": round(achieved / peak, 4),
+                         "traffic": ATTN_TRAFFIC["bytes"] if headline else None, "traffic_source": ATTN_TRAFFIC["source"] if headline else None,
+                         "launches": len(ev), "launches_total": len(ev_all),
+                         "avg_launch_ms": round(attn_ms, 4), "avg_launch_ms_all_incl_overlapped": round(attn_all_ms, 4),
+                         "overlap": ("control chain on a second stream (LD_DIT_OVERLAP=1): `achieved` is over the launches that run alone"
+                                     if solo_rule else
+                                     "control chain on a second stream and NO launch runs alone in this configuration: `achieved` is over all launches, "
+                                     "whose event intervals include time shared with the other chain" if pipe.dit.overlap else
+                                     "serial step: every launch runs alone"),
+                         # the runner's per-layer choice between the default launch and ld_attn_fwd_bf16_exact (landiff_amd/dit.py):
+                         # with these weights no layer leaves the fast pass's window, so every launch above is the default kernel
+                         "attn_policy": {"mode": "auto" if pipe.dit.attn_auto else ("exact" if pipe.dit.attn_exact else "default"),
+                                         "layers_on_exact_form": len(pipe.dit.exact_layers)}}
+            # ---- per-stage achieved vs peak (rank 0) ----------------------------------------------------
+            stages = {"dit_attention": {k: attn_roof[k] for k in ("bound", "achieved", "peak", "unit", "frac")}}
+            stages["dit_attention"]["seconds_per_step"] = round(attn_ms * 1e-3 * len(ev_all) / args.steps, 3)
+            stages["dit_attention"]["what"] = ("the kernel's own duration (launches that run alone) x all launches of a step: GPU time, not wall time -- "
+                                               "overlapped launches take longer on the wall (avg_launch_ms_all_incl_overlapped)")
+            gev = pipe.dit.gemm_events
+            if gev:
+                # events of the e4m3 linears carry (flops, "mx"), the bf16 ones (all of them in the headline configuration; the control
+                # zero-linears under --fp8-gemm) plain flops
+                split = {"bf16": [0.0, 0.0, 0], "mx": [0.0, 0.0, 0]}
+                for a, b, f in gev:
+                    kind = "bf16"
+                    if isinstance(f, tuple):
+                        f, kind = f
+                    acc = split[kind]
+                    acc[0] += a.elapsed_time(b) * 1e-3; acc[1] += f; acc[2] += 1
+                what = ("HIP events around every qkv / dense / 4h / 4h->h Linear and control zero-linear of the DiT loop "
+                        "(2 M N K each; 3.145 TFLOP per layer-call + 0.262 per control layer), tail launches included; "
+                        "collected in ONE extra, serial step after the timed region (the headline loop carries no GEMM events)")
+                if split["bf16"][2]:
+                    g_s, g_fl, n_ = split["bf16"]
+                    g_ach = g_fl / g_s / 1e12
+                    stages["dit_gemm"] = {"bound": "mfma", "achieved": round(g_ach, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(g_ach / peak, 4),
+                                          "seconds_per_step": round(g_s, 3), "launches": n_,
+                                          "what": what if not args.fp8_gemm else "the bf16 linears left under --fp8-gemm (control zero-linears); " + what}
+                if split["mx"][2]:
+                    g_s, g_fl, n_ = split["mx"]
+                    g_ach = g_fl / g_s / 1e12
+                    stages["dit_gemm_mxfp8"] = {"bound": "mfma", "achieved": round(g_ach, 1), "peak": 2 * peak, "unit": "TFLOP/s", "frac": round(g_ach / (2 * peak), 4),
+                                                "seconds_per_step": round(g_s, 3), "launches": n_,
+                                                "what": "the e4m3 (MXFP8) qkv / dense / 4h / 4h->h linears against the dense MX-fp8 MFMA peak (~5 PFLOP/s); " + what}
+            if "detokenize" in stage_s and not stream and P == 1 and not args.tiny:
+                dtf = detok_tflop(cfg)
+                stages["detokenize"] = {"bound": "mfma", "achieved": round(dtf / stage_s["detokenize"], 1), "peak": peak, "unit": "TFLOP/s",
+                                        "frac": round(dtf / stage_s["detokenize"] / peak, 4), "seconds_per_step": round(stage_s["detokenize"], 4),
+                                        "what": "%.2f TFLOP (TiTok decoder linears + frame-masked attention at its mask density, conv upsampler, conv_out) "
+                                                "/ the detokenize stage's wall time" % dtf}
+            if "llm" in stage_s and not stream and P == 1 and not args.tiny:
+                steps_llm = 1244
+                gbs = llm_step_bytes(cfg.llm) * steps_llm / stage_s["llm"] / 1e9
+                stages["llm_decode"] = {"bound": "hbm", "achieved": round(gbs, 1), "peak": HBM_PEAK, "unit": "GB/s", "frac": round(gbs / HBM_PEAK, 4),
+                                        "seconds_per_step": round(stage_s["llm"], 3),
+                                        "what": "%d decode steps x %.3f GB of weights (bf16 blocks + fp32 head) / the llm stage's wall time (prefill included)"
+                                                % (steps_llm, llm_step_bytes(cfg.llm) / 1e9)}
+            if "vae" in stage_s and not stream and P == 1 and not args.tiny:
+                tf = VAE_TFLOP / stage_s["vae"]
+                stages["vae_decode"] = {"bound": "mfma", "achieved": round(tf, 1), "peak": peak, "unit": "TFLOP/s", "frac": round(tf / peak, 4),
+                                        "seconds_per_step": round(stage_s["vae"], 3),
+                                        "what": "315 TFLOP of causal 3D / 2D convolutions per 49-frame video / the vae stage's wall time (norm, upsample and uint8 passes included)"}
+            res.update({
+                "roofline": attn_roof,
+                "roofline_stages": stages,
+                "stage_figures_note": "llm_decode / vae_decode / detokenize divide the stage's algorithmic bytes or FLOPs by its WALL time "
+                                      "(prefill, norm, upsample, uint8 passes and launch gaps included); dit_attention / dit_gemm are HIP-event "
+                                      "kernel times",
+                "calibration": dict(calib or {}, **({"timed_region": clocks} if clocks else {})),
+            })
+            if calib:                # the same fractions against what THIS box sustained a few seconds earlier
+                boxc = {"dit_attention": round(achieved / calib["mfma_tflops"], 4)}
+                if "dit_gemm" in stages:
+                    boxc["dit_gemm"] = round(stages["dit_gemm"]["achieved"] / calib["mfma_tflops"], 4)
+                if "vae_decode" in stages:
+                    boxc["vae_decode"] = round(stages["vae_decode"]["achieved"] / calib["mfma_tflops"], 4)
+                if "llm_decode" in stages:
+                    boxc["llm_decode"] = round(stages["llm_decode"]["achieved"] / calib["hbm_gbs"], 4)
+                res["frac_of_box_ceiling"] = boxc
+            if use_dist:
+                fps = [r["frames_per_s"] for r in reports]
+                # What a rank's GPU sustained right before its timed region, so that a scaling curve can be read net of the pool's
+                # GPU-to-GPU spread (+-5 % under the power cap): frames_per_s_normalised = frames_per_s x (mean MFMA-only rate of the
+                # job's GPUs / this GPU's) -- a rank on a slow GPU is not a scaling loss.  Each rank's own wall time, before the MAX.
+                cal = [r["calibration"] for r in reports]
+                mean_mfma = sum(c["mfma_tflops"] for c in cal) / len(cal)
+                res["per_rank"] = {"frames_per_s_min": min(fps), "frames_per_s_max": max(fps), "frames_per_s": fps,
+                                   "frames_per_s_normalised": [round(f * mean_mfma / c["mfma_tflops"], 4) for f, c in zip(fps, cal)],
+                                   "calibration": cal, "calibration_mean_mfma_tflops": round(mean_mfma, 1),
+                                   "stage_seconds": [r["stage_seconds"] for r in reports], "cores_per_rank": [r["cores"] for r in reports]}
+            if not args.no_cpu_baseline and world == 1:
+                res["cpu_baseline"] = cpu_baseline(PipelineConfig.full())
         print(json.dumps(res))
     if use_dist:
         dist.destroy_process_group()

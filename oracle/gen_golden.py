@@ -555,9 +555,33 @@ def gen_dit():
 
 
 # ------------------------------------------------------------------------------------------
+def gen_config():
+    """The reference's diffusion YAML pair as load_diffusion_config reads it (tests/test_facade.py: the shipped pair must give the same)."""
+    import dataclasses
+    import json
+    from landiff_amd.config import load_diffusion_config
+    os.environ["LANDIFF_SKIP_INIT"] = "1"
+    cfgs = os.path.join(REF, "landiff", "diffusion", "configs")
+    r = load_diffusion_config(os.path.join(cfgs, "cogvideox_2b_control_theia_interpolate_video_vq.yaml"),
+                              os.path.join(cfgs, "infer_cfgs", "2b.yaml"))
+    os.makedirs(OUT, exist_ok=True)
+    path = os.path.join(OUT, "reference_diffusion_config.json")
+    with open(path, "w") as f:
+        json.dump(dataclasses.asdict(r), f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(f"wrote {path}")
+    # the YAML names a tokenizer config of this project's `landiff` package: drop that package from the module cache, so that
+    # the generators after this one import the reference's `landiff` (install_stubs() puts the reference first on sys.path)
+    for name in [m for m in sys.modules if m == "landiff" or m.startswith("landiff.")]:
+        del sys.modules[name]
+
+
+# ------------------------------------------------------------------------------------------
 def main():
+    which = sys.argv[1:] or ["schedule", "rope", "llm", "titok", "titok_enc", "ups", "vae", "dit", "config"]
+    if "config" in which:
+        gen_config()          # (before the stubs: the tokenizer config the YAML names resolves to this project's landiff package)
     install_stubs()
-    which = sys.argv[1:] or ["schedule", "rope", "llm", "titok", "titok_enc", "ups", "vae", "dit"]
     if "schedule" in which:
         gen_schedule_and_sampler()
     if "rope" in which:

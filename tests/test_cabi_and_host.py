@@ -289,6 +289,30 @@ def test_bench_starts_its_own_ranks_or_refuses_a_mismatched_launcher():
     assert r.returncode != 0 and "WORLD_SIZE=8" in (r.stderr + r.stdout)
 
 
+def test_bench_dump_outputs_and_argument_checks(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files, the whole array when it is small, else a fixed sample that is the same in every
+    run (seeded positions, ascending); --steps below 1 is refused before any device is touched."""
+    import importlib.util, subprocess, sys
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_MAX_ELEMS * 4 <= 64 << 20
+    small = torch.arange(2 * 3 * 4, dtype=torch.uint8).view(2, 3, 4)
+    big = torch.randint(0, 256, (5, 7, 11, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(3))
+    for d in ("a", "b"):
+        bench.dump_outputs({"small": small, "big": big}, str(tmp_path / d), max_elems=100)
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (2, 3, 4) and np.array_equal(s, small.numpy())
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float32 and a.shape == (100,) and np.array_equal(a, b)
+    idx = torch.randint(big.numel(), (100,), generator=torch.Generator().manual_seed(0)).sort().values
+    assert np.array_equal(a, big.reshape(-1)[idx].float().numpy())
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LD_BENCH_FORCE_DIST")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0"], env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
 def test_rank_core_plan_prefers_the_gpus_numa_node():
     """rank_core_plan: ranks get cores of their GPU's NUMA node (ranks sharing a node split it), inside the cpuset; any missing
     piece of information gives the plain contiguous cut for every rank.  gpu_numa_nodes reads a sysfs tree without HIP."""

@@ -278,14 +278,14 @@ def test_gemv_streaming_loop_variant(cuda):
 
 @pytest.mark.parametrize("launcher", ["torchrun", "self"])
 def test_bench_rccl_path_single_rank(cuda, launcher):
-    """bench.py launched the way the driver launches the N-GPU runs (torch.distributed.run, one rank per GPU) and the plain way
+    """bench.py --full launched the way the driver launches the N-GPU runs (torch.distributed.run, one rank per GPU) and the plain way
     (`python bench.py --gpus N`, which starts its own ranks as child processes), with one rank and LD_BENCH_FORCE_DIST=1: RCCL
     init, barrier, all_gather of the uint8 frames, all_reduce(MAX) of the time."""
     import json
     e = dict(os.environ); e["LD_BENCH_FORCE_DIST"] = "1"; e.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LD_BENCH_DRY_SPAWN"):
         e.pop(k, None)
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--tiny", "--no-cpu-baseline"]
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0", "--tiny", "--no-cpu-baseline", "--full"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                "--master-port", "29517"] + tail
@@ -317,3 +317,37 @@ def test_bench_rccl_path_single_rank(cuda, launcher):
     assert len(pr["calibration"]) == 1 and pr["calibration"][0]["mfma_tflops"] == res["calibration"]["mfma_tflops"]
     assert pr["calibration"][0]["hbm_gbs"] > 500 and "timed_region_sclk_mhz" in pr["calibration"][0]
     assert pr["frames_per_s_normalised"] == pytest.approx(pr["frames_per_s"], rel=1e-3)      # one rank: the mean is its own rate
+
+
+def test_bench_plain_line_and_dumped_outputs(cuda, tmp_path):
+    """A plain bench.py run (no --full) runs --warmup + --steps pipeline calls and nothing more (counted by a wrapper around
+    LanDiffPipeline.__call__), prints the headline keys and none of what --full adds, and --dump-outputs writes the last step's
+    frames: the whole tiny video in float32, the values of uint8 frames."""
+    import json
+    import numpy as np
+    e = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LD_BENCH_DRY_SPAWN", "LD_BENCH_FORCE_DIST"):
+        e.pop(k, None)
+    out = tmp_path / "outputs"
+    bench = os.path.join(ROOT, "bench.py")
+    counted = (f"import atexit, runpy, sys\nsys.path.insert(0, {ROOT!r})\nfrom landiff_amd.pipeline import LanDiffPipeline\n"
+               "calls = [0]\ncall = LanDiffPipeline.__call__\n"
+               "def counting(self, *a, **k):\n    calls[0] += 1\n    return call(self, *a, **k)\n"
+               "LanDiffPipeline.__call__ = counting\n"
+               "atexit.register(lambda: print('PIPELINE_CALLS', calls[0], file=sys.stderr))\n"
+               f"sys.argv = [{bench!r}] + sys.argv[1:]\nrunpy.run_path({bench!r}, run_name='__main__')\n")
+    r = subprocess.run([sys.executable, "-c", counted, "--gpus", "1", "--steps", "2", "--warmup", "1", "--tiny",
+                        "--dump-outputs", str(out)], env=e, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert "PIPELINE_CALLS 3" in r.stderr, r.stderr[-2000:]          # 1 warm-up + 2 timed steps
+    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert k in res, k
+    for k in ("roofline", "roofline_stages", "calibration", "frac_of_box_ceiling", "per_rank", "cpu_baseline"):
+        assert k not in res, k
+    assert res["steps"] == 2 and res["warmup"] == 1 and res["unit"] == "frames/s" and res["dtype"] == "bf16"
+    assert res["ms_per_step"] > 0 and res["value"] == pytest.approx(res["config"]["frames"] * 1e3 / res["ms_per_step"], rel=1e-6)
+    assert sorted(os.listdir(out)) == ["frames.npy"]
+    f = np.load(out / "frames.npy")
+    assert f.dtype == np.float32 and f.shape == (1, res["config"]["frames"], res["config"]["height"], res["config"]["width"], 3)
+    assert f.min() >= 0 and f.max() <= 255 and np.array_equal(f, np.round(f)) and f.std() > 0
