@@ -27,8 +27,9 @@ extern "C" {
  * compares ld_version() with the LD_ABI_VERSION it was built against before anything else (landiff_amd/_lib.py does).
  * 6: ld_reset and ld_attn_queue_poke were added.  7: ld_conv_cl_bf16_gn, ld_conv_gn_partials_size and
  * ld_groupnorm_stats_from_conv were added.  8: ld_gemm_qkv_heads_mxfp8 was added.
- * 9: ld_attn_fwd_bf16_exact was added.  10: ld_attn_last_fallbacks was added. */
-#define LD_ABI_VERSION 10
+ * 9: ld_attn_fwd_bf16_exact was added.  10: ld_attn_last_fallbacks was added.  11: ld_vae_enc_place_input,
+ * ld_vae_enc_downsample and ld_vae_posterior were added. */
+#define LD_ABI_VERSION 11
 
 int ld_version(void);
 const char* ld_last_error(void);
@@ -448,6 +449,31 @@ int ld_to_uint8(const void* x, int64_t ldx, uint8_t* out, float* video, int64_t 
  * (dif_infer.py:251 `1/scale_factor * latent` on the bf16 samples). */
 int ld_latent_to_cl(const float* x, void* out, int64_t T, int64_t C, int64_t H, int64_t W, int64_t Cpad, float mul,
                     int32_t src_tchw, void* stream);
+
+/* ---- 3D-VAE encoder (ld_vae_enc.hip; ContextParallelEncoder3D, cp_enc_dec.py:785-911, + DiagonalGaussianRegularizer,
+ * regularizers.py:10-28,96-114).  Its convolutions, GroupNorms and residual adds are ld_conv_cl_bf16[_gn] / ld_groupnorm_*. ---- */
+
+/* Frames [F][H][W][3] (uint8 when frames_u8: x / 127.5 - 1, else f32 in [-1, 1]) -> conv_in's input: bf16
+ * [F+2][H+2][W+2][Cpad], EVERY element written -- zero spatial border, channels 3.. zero, time frames 0 and 1 copies of
+ * frame 0 (the causal halo without a cache, _fake_cp_pass_from_previous_rank, cp_enc_dec.py:249-300).  Cpad % 8 == 0. */
+int ld_vae_enc_place_input(const void* frames, int32_t frames_u8, void* out_padded, int64_t F, int64_t H, int64_t W,
+                           int64_t Cpad, void* stream);
+
+/* DownSample3D (cp_enc_dec.py:634-681) up to its conv: x bf16 [T][H][W][C] -> bf16 [To][H/2+2][W/2+2][4C] (every element
+ * written), out[t][a][b][(2p+q)*C + c] = x'[t][2a+p][2b+q][c], zero where 2a+p >= H or 2b+q >= W (the (0,1,0,1) pad and one
+ * more zero row / column, for ld_conv_cl_bf16's odd kernel sizes).  x' = x,
+ * or with compress_time and T > 1 the time pool: frame 0 kept and pairs averaged for odd T, pairs for even T (To = (T+1)/2 or
+ * T/2), the mean of two bf16 values in fp32 rounded once.  The 3x3 stride-2 conv is then ld_conv_cl_bf16 as a stride-1 1x3x3
+ * conv over 4C channels whose weights are rearranged once, with zeros for the taps that do not exist (2x2 of the 3x3 taps
+ * carry weights; landiff_amd/vae_encoder.py: s2d_conv_weight).  C % 8 == 0, H and W even. */
+int ld_vae_enc_downsample(const void* x, void* out, int64_t T, int64_t H, int64_t W, int64_t C, int32_t compress_time,
+                          void* stream);
+
+/* The posterior of conv_out's f32 output x [T*H*W][ldx] (mean = channels [0, Z), logvar = [Z, 2Z), clamped to [-30, 20]):
+ * z [T][Z][H][W] f32 = scale * (mean + exp(0.5 * logvar) * eps) with eps f32 [Z][T][H][W] (randn_like of the reference's
+ * [1, Z, T, H, W] mean), or scale * mean when eps is null.  mean / logvar (optional, [T][Z][H][W] f32) get the unscaled values. */
+int ld_vae_posterior(const float* x, int64_t ldx, const float* eps, float* z, float* mean, float* logvar, int64_t T,
+                     int64_t Z, int64_t H, int64_t W, float scale, void* stream);
 
 /* ---- T5 text encoders (HF transformers T5EncoderModel called from
  * landiff/llm/modules/text_encoder.py:36-42,82-112 and landiff/diffusion/sgm/modules/encoders/modules.py:249-292) ---- */

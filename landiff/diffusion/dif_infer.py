@@ -16,7 +16,7 @@ from landiff_amd.dit import ControlDiTRunner
 from landiff_amd.sampler import DiffusionSampler
 from landiff_amd.text import encode_t5_v11
 from landiff_amd.vae import VAEDecoder
-from landiff_amd.weights import load_diffusion_states, load_tokenizer_encoder_state, resolve_ckpt_path
+from landiff_amd.weights import load_diffusion_states, load_tokenizer_encoder_state, load_vae_encoder_state, resolve_ckpt_path
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_INFER_CFG = "landiff/diffusion/configs/infer_cfgs/2b.yaml"
@@ -73,6 +73,8 @@ class CogWrapper(torch.nn.Module):
         self.sampler = DiffusionSampler(cfg.sampler)
         self.vae = VAEDecoder(st["vae"], cfg.vae, device)
         self._encoder = None            # tokenizer encoder half: built on the first video-conditioned call
+        self._vae_encoder = None        # 3D-VAE encoder: built on the first encode_first_stage call
+        self._ckpt_path = ckpt_path
 
     def _context(self, text: str) -> torch.Tensor:
         """FrozenT5Embedder on the prompt, padded to text_length, pad positions not masked (encoders/modules.py:246-295); the
@@ -116,6 +118,27 @@ class CogWrapper(torch.nn.Module):
             self._encoder = TokenizerEncoder(load_tokenizer_encoder_state(resolve_ckpt_path(self.cfg.tokenizer_ckpt)), tc, self.device_)
         tokens = self._encoder.encode_to_index(feats.to(self.device_))
         return self.detok.semantic_condition(tokens)
+
+    @torch.no_grad()
+    def encode_first_stage(self, x: torch.Tensor) -> torch.Tensor:
+        """SATVideoDiffusionEngine.encode_first_stage (diffusion_video.py:233-254) with the reference's regularizer:
+        x [B, 3, T, H, W] in [-1, 1] -> scale_factor * posterior.sample() [B, 16, (T+3)//4, H/8, W/8] fp32, the sample drawn
+        with randn_like on the device's global generator.  Permuted to [B, T', 16, h, w] it is the `vae_feature_prefix`
+        forward() takes.  The encoder's weights: 'encoder.*' of the VAE checkpoint, then of the diffusion checkpoint's
+        first_stage_model (weights.load_vae_encoder_state)."""
+        if self._vae_encoder is None:
+            from landiff_amd.vae_encoder import VAEEncoder
+            sd = load_vae_encoder_state(None, vae_ckpt=self.cfg.vae_ckpt, diffusion_dir=resolve_ckpt_path(self._ckpt_path))
+            self._vae_encoder = VAEEncoder(sd, self.cfg.vae, self.device_)
+        B, _, T, H, W = x.shape
+        enc = self._vae_encoder
+        # one randn_like over the whole [B, 16, T', h, w] posterior, as the reference draws it
+        eps = torch.randn(B, enc.cfg.z_channels, enc.latent_frames(T), H // 8, W // 8, device=self.device_, dtype=torch.float32)
+        out = []
+        for b in range(B):
+            frames = x[b].permute(1, 2, 3, 0).to(self.device_, torch.float32).contiguous()      # [T, H, W, 3]
+            out.append(enc.encode(frames, sample=True, eps=eps[b:b + 1]).permute(0, 2, 1, 3, 4))
+        return torch.cat(out, dim=0)
 
     @torch.no_grad()
     def forward(self, inputs: dict, seed: int | None = None, semantic_token: torch.Tensor | None = None,

@@ -8,6 +8,7 @@ from landiff.diffusion.dif_infer import CogModelInferWrapper, VideoTask
 from landiff.llm.llm_cfg import build_llm
 from landiff.llm.llm_infer import ArModelInferWrapper, ARSampleCfg, CodeTask
 from landiff.utils import save_video_tensor
+from landiff_amd.pipeline import STREAM_PREFIX_FRAMES
 
 
 def parse_args(argv=None):
@@ -21,6 +22,15 @@ def parse_args(argv=None):
     parser.add_argument("--cfg", type=float, default=7.5, help="CFG scale for the video generation.")
     parser.add_argument("--motion_score", type=float, default=0.1, help="Motion score for the video generation.")
     parser.add_argument("--seed", type=int, default=42, help="Random seed for video generation.")
+    parser.add_argument("--extend_video", type=str, default=None,
+                        help="Continue this clip instead of generating from scratch: a uint8 [F, H, W, 3] .npy (the format "
+                             "save_video_tensor falls back to) or an mp4 when imageio can read it.")
+    parser.add_argument("--extend_chunks", type=int, default=1, help="Chunks appended to --extend_video.")
+    parser.add_argument("--extend_prefix_frames", type=int, default=STREAM_PREFIX_FRAMES,
+                        help="Latent frames of the previous chunk pinned as each new chunk's prefix.")
+    parser.add_argument("--extend_tokens", type=str, default=None,
+                        help="The clip's own semantic tokens (.npy of llm_infer, one segment): the AR decode continues from "
+                             "them instead of sampling every segment from the prompt.")
     return parser.parse_args(argv)
 
 
@@ -51,6 +61,65 @@ def infer_diffusion(args, semantic_token):
     print(f"save video to {task.save_file_name}")
 
 
+def load_clip(path: str) -> torch.Tensor:
+    """uint8 frames [F, H, W, 3] from a .npy (save_video_tensor's fallback format) or, through imageio, a video file."""
+    if path.endswith(".npy"):
+        arr = np.load(path)
+    else:
+        try:
+            import imageio
+        except ImportError as e:
+            raise ValueError(f"{path}: reading a video file needs imageio; give the uint8 frames as .npy instead") from e
+        arr = np.stack(list(imageio.get_reader(path)))
+    if arr.dtype != np.uint8 or arr.ndim != 4 or arr.shape[-1] != 3:
+        raise ValueError(f"{path}: expected uint8 frames [F, H, W, 3], got {arr.dtype} {arr.shape}")
+    return torch.from_numpy(np.ascontiguousarray(arr))
+
+
+def build_continuation(args):
+    """The pipeline and prompt inputs --extend_video runs: the diffusion stage's YAML files and checkpoint tree (as
+    CogModelInferWrapper reads them), the VAE encoder's weights ('encoder.*' of the VAE checkpoint, then of the diffusion
+    checkpoint's first stage), the LLM checkpoint, and the prompt through both T5 encoders.  -> (LanDiffPipeline, PromptInputs)."""
+    from landiff.diffusion.dif_infer import DEFAULT_INFER_CFG, DEFAULT_MODEL_CFG, _cfg_path
+    from landiff_amd.config import load_diffusion_config
+    from landiff_amd.pipeline import LanDiffPipeline, PromptInputs, stream_plan
+    from landiff_amd.text import encode_flan_t5, encode_t5_v11
+    from landiff_amd.weights import load_diffusion_states, load_llm_state, load_vae_encoder_state, resolve_ckpt_path
+    dcfg = load_diffusion_config(_cfg_path(DEFAULT_MODEL_CFG), _cfg_path(DEFAULT_INFER_CFG))
+    cfg = dcfg.pipeline(build_llm()).check()
+    dev = torch.device(f"cuda:{torch.cuda.current_device()}")
+    ckpt = resolve_ckpt_path(args.diffusion_ckpt)
+    st = load_diffusion_states(ckpt, None, base_dit_ckpt=dcfg.base_dit_ckpt, vae_ckpt=dcfg.vae_ckpt,
+                               tokenizer_ckpt=dcfg.tokenizer_ckpt or None)
+    st["vae"] = {**st["vae"], **load_vae_encoder_state(None, vae_ckpt=dcfg.vae_ckpt, diffusion_dir=ckpt)}
+    st["llm"] = load_llm_state(args.llm_ckpt)
+    c = cfg.llm
+    # the clip is chunk 0 of the stream: its multi-segment AR decode needs n_seg segments of KV cache
+    _, _, n_seg = stream_plan(cfg, args.extend_chunks + 1, args.extend_prefix_frames)
+    pipe = LanDiffPipeline(cfg, st, dev, max_llm_frames=n_seg * c.segment_length)
+    text = encode_flan_t5([args.prompt], dev, max_length=c.max_cond_tokens, model_path=c.text_encoder_path)[0]
+    ctx = encode_t5_v11([args.prompt], resolve_ckpt_path(dcfg.t5_dir), cfg.dit.text_len, dev)
+    inp = PromptInputs(text, ctx, seed=args.seed, cfg=args.cfg, motion_score=args.motion_score)
+    return pipe, inp
+
+
+def extend_diffusion(args):
+    """--extend_video: LanDiffPipeline.extend_video on the clip -- its last 4T-3 frames encoded, the chunks after it run as
+    generate_stream runs its later chunks (sliding semantic windows of one multi-segment AR decode, the prefix latents pinned,
+    the decode continued against the VAE caches); --extend_tokens forces the decode's first segment to the clip's own tokens.
+    Writes the clip followed by the new frames."""
+    clip = load_clip(args.extend_video)
+    pipe, inp = build_continuation(args)
+    clip_tokens = torch.from_numpy(np.load(args.extend_tokens)).reshape(-1) if args.extend_tokens else None
+    new = pipe.extend_video(inp, args.extend_chunks, frames=clip, clip_tokens=clip_tokens,
+                            prefix_frames=args.extend_prefix_frames)
+    frames = torch.cat([clip, new.cpu()], dim=0)
+    path = f"{args.save_file_name}.mp4"
+    save_video_tensor(frames, path, fps=8)
+    print(f"save video to {path} ({frames.shape[0]} frames, {new.shape[0]} new)")
+    return frames
+
+
 def main():
     import os
 
@@ -60,6 +129,9 @@ def main():
         from landiff_amd.pipeline import pin_rank_cores
         pin_rank_cores(local_rank, int(os.environ["LOCAL_WORLD_SIZE"]))
     torch.cuda.set_device(local_rank)
+    if args.extend_video:
+        extend_diffusion(args)
+        return
     infer_diffusion(args, llm_infer(args))
 
 

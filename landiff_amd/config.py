@@ -296,6 +296,22 @@ def _cls(target: str) -> str:
     return target.rsplit(".", 1)[-1]
 
 
+def check_vae_encoder_config(enc_cfg: dict, vae: VAEConfig) -> None:
+    """first_stage_config.params.encoder_config (ContextParallelEncoder3D, cp_enc_dec.py:785-911) must describe the encoder
+    VAEEncoder builds from `vae`: same widths and depth, a double_z posterior, 3 input channels, no attention.  gather_norm
+    (ContextParallelGroupNorm) is the plain GroupNorm on one rank."""
+    assert _cls(enc_cfg["target"]) == "ContextParallelEncoder3D", enc_cfg["target"]
+    e = enc_cfg.get("params", {})
+    want = {"ch": vae.ch, "ch_mult": tuple(vae.ch_mult), "num_res_blocks": vae.num_res_blocks, "z_channels": vae.z_channels,
+            "in_channels": 3, "double_z": True, "temporal_compress_times": vae.temporal_compress_times}
+    got = {"ch": e.get("ch"), "ch_mult": tuple(e.get("ch_mult", ())), "num_res_blocks": e.get("num_res_blocks"),
+           "z_channels": e.get("z_channels"), "in_channels": e.get("in_channels", 3), "double_z": bool(e.get("double_z", True)),
+           "temporal_compress_times": e.get("temporal_compress_times", 4)}
+    bad = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
+    if bad or e.get("attn_resolutions"):
+        raise ValueError(f"encoder_config disagrees with the VAE config (got, expected): {bad or 'attn_resolutions'}")
+
+
 def load_diffusion_config(model_cfg_path: str, infer_cfg_path: str) -> DiffusionInferConfig:
     """Reads the reference's model YAML (cogvideox_2b_control_theia_interpolate_video_vq.yaml :1-243) and inference YAML
     (infer_cfgs/2b.yaml :1-13) with PyYAML.  Only the `target:` classes of the shipped configuration are accepted; every
@@ -357,6 +373,8 @@ def load_diffusion_config(model_cfg_path: str, infer_cfg_path: str) -> Diffusion
     assert _cls(fs["decoder_config"]["target"]) == "ContextParallelDecoder3D" and not dec.get("gather_norm", False) and not dec.get("attn_resolutions")
     vae = VAEConfig(ch=dec["ch"], ch_mult=tuple(dec["ch_mult"]), num_res_blocks=dec["num_res_blocks"], z_channels=dec["z_channels"],
                     out_ch=dec["out_ch"], temporal_compress_times=n["time_compressed_rate"], scale_factor=float(m["scale_factor"]))
+    if "encoder_config" in fs:      # (the reference's YAML has it; the shipped copy does not: the encoder then takes the decoder's values)
+        check_vae_encoder_config(fs["encoder_config"], vae)
     # sampler stack
     smp = m["sampler_config"]
     kind = _cls(smp["target"])

@@ -282,12 +282,15 @@ class LLMRunner:
                temperature: float = 1.0, seed: int | None = None, generator=None, use_graph: bool = False,
                teacher_fed=None, logits_log=None, top_k: int | None = None, top_p: float | None = None,
                first_frame_tokens: torch.Tensor | None = None, on_segment=None, segment_tokens: int | None = None,
-               mode: str | None = None) -> torch.Tensor:
+               mode: str | None = None, prefix_tokens: torch.Tensor | None = None) -> torch.Tensor:
         """Returns the clamped visual token ids, int64 [n_visual] on the device (lm_model.py:509-516).
         top_k / top_p filter the unrestricted positions inside the sampling kernel (lm_model.py:441-447).
         first_frame_tokens (int64 [iframe_len], e.g. from TokenizerEncoder.encode_to_index): use_gt_first_frame of the
         reference (lm_model.py:332-352) -- the given I-frame tokens, END_OF_IFrame and the first START_OF_PFrame join the
         prefilled prefix, sampling (and the RNG stream) starts at the first P token, the result begins with the given ids.
+        prefix_tokens (int64 [num_latent_tokens]: one whole segment, e.g. the .npy llm_infer saves next to a video): the same
+        for the first segment of a multi-segment decode -- its ids, with the markers forced_token_schedule puts between them,
+        and the next segment's START_OF_IFrame join the prefilled prefix; sampling starts at that segment's first I token.
         on_segment(s): called on the host right after the step that emits the last of every `segment_tokens` visual tokens
         has been QUEUED (tokens [s * segment_tokens, (s + 1) * segment_tokens) of self.out_tokens are then final in stream
         order) -- lets a streaming caller start on segment s while later segments are still being decoded."""
@@ -322,6 +325,23 @@ class LLMRunner:
             feats = torch.cat([feats, self.emb[ids].to(BF)[None].expand(2, -1, -1)], 1)
             S_last = S + c.iframe_len + 2
             n_visual -= c.iframe_len
+        n_prefix = 0
+        if prefix_tokens is not None:
+            assert first_frame_tokens is None, "prefix_tokens already holds the first I frame"
+            block = c.iframe_len + (c.segment_length - 1) * c.pframe_len + 2 * c.segment_length
+            if full_len - 1 <= S + block:
+                raise ValueError("prefix_tokens: one whole segment, and at least one more segment to sample")
+            tmpl = torch.tensor([forced.get(q, -1) for q in range(S + 1, S + block + 1)], dtype=torch.int64)
+            slots = tmpl < 0
+            vis = prefix_tokens.reshape(-1).to(dev, torch.int64)
+            if vis.numel() != int(slots.sum()):
+                raise ValueError(f"prefix_tokens: {vis.numel()} ids, a segment holds {int(slots.sum())}")
+            ids = tmpl.to(dev)
+            ids[slots.to(dev)] = vis
+            feats = torch.cat([feats, self.emb[ids].to(BF)[None].expand(2, -1, -1)], 1)
+            S_last = S + block
+            n_prefix = vis.numel()
+            n_visual -= n_prefix
         ft = torch.full((self.Lmax + 2,), -1, dtype=torch.int32)
         al = torch.zeros(self.Lmax + 2, 4, dtype=torch.int32)
         for p, t in forced.items():
@@ -343,7 +363,7 @@ class LLMRunner:
             emitted += 1
             if emitted % segment_tokens == 0:
                 on_segment(emitted // segment_tokens - 1)
-        assert on_segment is None or (segment_tokens and first_frame_tokens is None)
+        assert on_segment is None or (segment_tokens and first_frame_tokens is None and prefix_tokens is None)
         self._prefill(feats)
         self.pos.fill_(S_last)
         self._sample_and_advance(guided, guidance_scale, temperature, generator)
@@ -389,6 +409,8 @@ class LLMRunner:
         out = self.out_tokens[:n_visual]
         if first_frame_tokens is not None:
             out = torch.cat([first_frame_tokens.reshape(-1).to(dev, torch.int64), out])
+        if n_prefix:
+            out = torch.cat([prefix_tokens.reshape(-1).to(dev, torch.int64), out])
         return out.clamp(0, c.visual_vocab - 1)
 
     def _raise_on_wait_timeout(self):

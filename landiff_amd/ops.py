@@ -543,6 +543,43 @@ def latent_to_cl(x, out, T, C, H, W, Cpad, mul, src_tchw):
           "ld_latent_to_cl")
 
 
+
+# ---- 3D-VAE encoder (ld_vae_enc.hip) ----------------------------------------------------------------
+def vae_enc_place_input(frames, out_padded):
+    """frames uint8 / f32 [F, H, W, 3] -> out_padded bf16 [F+2, H+2, W+2, Cpad] (every element written)."""
+    assert frames.dtype in (torch.uint8, torch.float32) and frames.is_contiguous() and frames.shape[-1] == 3
+    F, H, W, _ = frames.shape
+    _bf16(out_padded, "out_padded")
+    assert out_padded.is_contiguous() and tuple(out_padded.shape[:3]) == (F + 2, H + 2, W + 2)
+    check(_lib.load().ld_vae_enc_place_input(_ptr(frames), int(frames.dtype == torch.uint8), _ptr(out_padded), F, H, W,
+                                             out_padded.shape[3], _stream()), "ld_vae_enc_place_input")
+    return out_padded
+
+
+def vae_enc_downsample_out_frames(T: int, compress_time: bool) -> int:
+    return ((T + 1) // 2 if T % 2 else T // 2) if compress_time and T > 1 else T
+
+
+def vae_enc_downsample(x, out, T, H, W, C, compress_time):
+    """x bf16 [T*H*W, C] -> out bf16 [To, H/2+2, W/2+2, 4C] (time pool + space-to-depth; every element written)."""
+    _bf16(x, "x"); _bf16(out, "out")
+    To = vae_enc_downsample_out_frames(T, compress_time)
+    assert x.is_contiguous() and x.numel() == T * H * W * C and out.is_contiguous()
+    assert tuple(out.shape) == (To, H // 2 + 2, W // 2 + 2, 4 * C), (out.shape, To, H, W, C)
+    check(_lib.load().ld_vae_enc_downsample(_ptr(x), _ptr(out), T, H, W, C, int(compress_time), _stream()),
+          "ld_vae_enc_downsample")
+    return out
+
+
+def vae_posterior(x, z, T, Z, H, W, scale, eps=None, mean=None, logvar=None):
+    """x f32 [T*H*W, >= 2Z] -> z f32 [T, Z, H, W] = scale * (mean [+ exp(0.5 logvar) * eps]); eps f32 [Z, T, H, W]."""
+    assert x.dtype == torch.float32 and x.stride(1) == 1 and x.shape[0] == T * H * W and x.shape[1] >= 2 * Z
+    for t in (z, eps, mean, logvar):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == T * Z * H * W)
+    check(_lib.load().ld_vae_posterior(_ptr(x), x.stride(0), _ptr(eps), _ptr(z), _ptr(mean), _ptr(logvar), T, Z, H, W,
+                                       float(scale), _stream()), "ld_vae_posterior")
+    return z
+
 # ---- T5 text encoders -------------------------------------------------------------------------------
 def t5_rmsnorm(x, w, out, eps):
     _bf16(x, "x"); _bf16(w, "w"); _bf16(out, "out")

@@ -21,6 +21,12 @@ from .dit import ControlDiTRunner
 from .llm import LLMRunner
 from .sampler import DiffusionSampler
 from .vae import VAEDecoder
+from .vae_encoder import VAEEncoder
+
+
+# latent frames of the previous chunk a streamed chunk pins as its prefix: the shipped sampler's "fixed_frames: 7 # 49 frames,
+# 13 latent, prefix_length=7" (cogvideox_2b_control_theia_interpolate_video_vq.yaml :213,231)
+STREAM_PREFIX_FRAMES = 7
 
 
 @dataclass
@@ -50,6 +56,10 @@ class LanDiffPipeline:
         self.dit = ControlDiTRunner(states["dit_main"], states["dit_control"], cfg.dit, self.dev, fp8_gemm=fp8_gemm)
         self.sampler = DiffusionSampler(cfg.sampler)
         self.vae = VAEDecoder(states["vae"], cfg.vae, self.dev)
+        # the 3D-VAE encoder of extend_video(frames=...): built when the VAE state carries 'encoder.*' keys
+        # (weights.load_vae_encoder_state, or a synthetic tree whose states["vae"] has them)
+        self.encoder = (VAEEncoder(states["vae"], cfg.vae, self.dev)
+                        if any(k.startswith("encoder.") for k in states["vae"]) else None)
         self.timings = {}
 
     def _t(self, name, t0):
@@ -169,14 +179,55 @@ class LanDiffPipeline:
     # ---- streaming long video (BASELINE config 3) --------------------------------
     def stream_plan(self, n_chunks: int, prefix_frames: int):
         """(latent frames per chunk, new latent frames per later chunk, LLM segments needed)."""
-        T, seg = self.cfg.dit.latent_frames, self.cfg.llm.segment_length
-        new = T - prefix_frames
-        assert 0 < prefix_frames < T and new % 2 == 0, "later chunks decode their new latent frames in pairs"
-        total = T + (n_chunks - 1) * new
-        return T, new, -(-total // seg)
+        return stream_plan(self.cfg, n_chunks, prefix_frames)
+
+    def _sem_windows(self, seg_tokens, T: int):
+        """sem_window(f0, f1): latent frames [f0, f1) of the concatenated per-segment semantic features; a segment is detokenized
+        (and timed) when a window first needs it.  seg_tokens(s) -> segment s's token ids."""
+        sem_seg = {}               # segment -> semantic features [T, C, H, W]
+        def sem_window(f0, f1):
+            parts = []
+            for sidx in range(f0 // T, (f1 - 1) // T + 1):
+                if sidx not in sem_seg:
+                    tok = seg_tokens(sidx)                 # (overlapped decode: blocks until the segment's last token is queued)
+                    t1 = time.perf_counter()
+                    sem_seg[sidx] = self.detok.semantic_condition(tok)
+                    self._t("detokenize", t1)
+                lo, hi = max(f0, sidx * T) - sidx * T, min(f1, (sidx + 1) * T) - sidx * T
+                parts.append(sem_seg[sidx][lo:hi])
+            return torch.cat(parts, dim=0).contiguous()
+        return sem_window
+
+    def _stream_chunk(self, inp: PromptInputs, c: int, sem, noise, prev, prefix_frames: int, randn_like, want_float: bool,
+                      keep: bool, latents_out=None):
+        """Chunk c of a stream: seed inp.seed + c, the sampler on semantic window `sem` (prefix = the last `prefix_frames`
+        latents of `prev`, the previous chunk's bf16 latent, unless prev is None), then the VAE decode of its new latent frames
+        against the causal-conv caches the previous chunk left (kept for the next chunk when `keep`).  -> (latent, frames)."""
+        d = self.cfg.dit
+        T = d.latent_frames
+        t0 = time.perf_counter()
+        torch.manual_seed(inp.seed + c); torch.cuda.manual_seed(inp.seed + c)
+        self.dit.set_condition(inp.dit_context, sem)
+        noise = noise.to(self.dev) if noise is not None else torch.randn(
+            1, T, d.in_channels, d.latent_h, d.latent_w, device=self.dev, dtype=torch.float32)
+        if prev is None:
+            z = self.sampler.run(self.dit.step, noise, randn_like=randn_like)
+        else:
+            z = self.sampler.run(self.dit.step, noise, randn_like=randn_like, prefix=prev[:, T - prefix_frames:],
+                                 fixed_frames=prefix_frames)
+        first = prev is None
+        prev = z.to(torch.bfloat16).float()              # samples.to(self.dtype) (diffusion_video.py:314)
+        if latents_out is not None:
+            latents_out.append(prev.clone())
+        self._t("dit", t0)
+        t0 = time.perf_counter()
+        lat = prev if first else prev[:, prefix_frames:]
+        r = self.vae.decode(lat, want_float=want_float, stream_continue=not first, stream_keep=keep)
+        self._t("vae", t0)
+        return prev, r
 
     @torch.no_grad()
-    def generate_stream(self, inp: PromptInputs, n_chunks: int, prefix_frames: int = 7, want_float: bool = False,
+    def generate_stream(self, inp: PromptInputs, n_chunks: int, prefix_frames: int = STREAM_PREFIX_FRAMES, want_float: bool = False,
                         tokens: torch.Tensor | None = None, noises=None, randn_like=torch.randn_like, overlap_decode: bool = True,
                         latents_out: list | None = None):
         """Chunked long-video generation out of the reference's streaming primitives -- the reference ships the pieces
@@ -241,18 +292,7 @@ class LanDiffPipeline:
             self._t("llm", t0)
             tokens = tokens.to(self.dev).reshape(n_seg, per_seg)
             seg_tokens = lambda sidx: tokens[sidx]
-        sem_seg = {}               # segment -> semantic features [T, C, H, W], computed when a chunk first needs them
-        def sem_window(f0, f1):    # latent frames [f0, f1) of the concatenated per-segment features
-            parts = []
-            for sidx in range(f0 // T, (f1 - 1) // T + 1):
-                if sidx not in sem_seg:
-                    tok = seg_tokens(sidx)                 # (overlapped decode: blocks until the segment's last token is queued)
-                    t1 = time.perf_counter()
-                    sem_seg[sidx] = self.detok.semantic_condition(tok)
-                    self._t("detokenize", t1)
-                lo, hi = max(f0, sidx * T) - sidx * T, min(f1, (sidx + 1) * T) - sidx * T
-                parts.append(sem_seg[sidx][lo:hi])
-            return torch.cat(parts, dim=0).contiguous()
+        sem_window = self._sem_windows(seg_tokens, T)
         outs, vids, prev = [], [], None
         for c in range(n_chunks):
             t_w = time.perf_counter()
@@ -261,24 +301,8 @@ class LanDiffPipeline:
             wait = time.perf_counter() - t_w - (self.timings.get("detokenize", 0.0) - d0)
             if decode_thread is not None:
                 self.timings["segment_wait"] = self.timings.get("segment_wait", 0.0) + wait
-            t0 = time.perf_counter()
-            torch.manual_seed(inp.seed + c); torch.cuda.manual_seed(inp.seed + c)
-            self.dit.set_condition(inp.dit_context, sem)
-            noise = noises[c].to(self.dev) if noises is not None else torch.randn(
-                1, T, d.in_channels, d.latent_h, d.latent_w, device=self.dev, dtype=torch.float32)
-            if c == 0:
-                z = self.sampler.run(self.dit.step, noise, randn_like=randn_like)
-            else:
-                z = self.sampler.run(self.dit.step, noise, randn_like=randn_like, prefix=prev[:, T - prefix_frames:],
-                                     fixed_frames=prefix_frames)
-            prev = z.to(torch.bfloat16).float()              # samples.to(self.dtype) (diffusion_video.py:314)
-            if latents_out is not None:
-                latents_out.append(prev.clone())
-            self._t("dit", t0)
-            t0 = time.perf_counter()
-            lat = prev if c == 0 else prev[:, prefix_frames:]
-            r = self.vae.decode(lat, want_float=want_float, stream_continue=c > 0, stream_keep=c < n_chunks - 1)
-            self._t("vae", t0)
+            prev, r = self._stream_chunk(inp, c, sem, noises[c] if noises is not None else None, prev, prefix_frames, randn_like,
+                                         want_float, keep=c < n_chunks - 1, latents_out=latents_out)
             if want_float:
                 outs.append(r[0]); vids.append(r[1])
             else:
@@ -290,6 +314,99 @@ class LanDiffPipeline:
             self.timings["llm_overlapped"] = self.timings.get("llm_overlapped", 0.0) + decode_state["seconds"]   # wall time of the decode thread
         frames = torch.cat(outs, dim=0)
         return (frames, torch.cat(vids, dim=1)) if want_float else frames
+
+
+    # ---- continuation of a given clip ------------------------------------------------------------------
+    @torch.no_grad()
+    def extend_video(self, inp: PromptInputs, n_chunks: int, *, frames: torch.Tensor | None = None,
+                     clip_latent: torch.Tensor | None = None, clip_tokens: torch.Tensor | None = None,
+                     tokens: torch.Tensor | None = None, prefix_frames: int = STREAM_PREFIX_FRAMES, want_float: bool = False, noises=None,
+                     latents_out: list | None = None):
+        """Continues a given clip: the clip is chunk 0 of a generate_stream run, and chunks 1..n_chunks are produced exactly as
+        generate_stream(inp, n_chunks + 1, prefix_frames, ...) produces its chunks 1.. (seed inp.seed + k, semantic window
+        [k new, k new + T), prefix = the last `prefix_frames` latents of the previous chunk, decode against the VAE caches).
+
+        The clip latent (exactly one of the two): `clip_latent` [1, T, 16, h, w] as given, or `frames` uint8 [F >= 4T-3, 8h, 8w, 3] whose LAST 4T-3
+        frames are encoded (VAEEncoder: scale_factor * posterior.sample(), the sample drawn on the device's generator seeded
+        with inp.seed, as encode_first_stage does -- diffusion_video.py:233-254); it is rounded to bf16 like a sampled latent.
+        Its T latent frames are decoded once (frames discarded) to prime the decoder's causal-conv caches.
+
+        Semantic tokens (at most one of the two): `tokens` = every segment's ids (n_seg * num_latent_tokens, as generate_stream takes them); otherwise
+        one multi-segment AR decode from the prompt, with segment 0 forced to `clip_tokens` (int64 [num_latent_tokens], e.g.
+        the .npy llm_infer saves next to a video) when given.  Without clip_tokens every segment is sampled from the prompt:
+        the prefix frames' control features then come from the prompt, not from the clip (tokens from pixels need the Theia
+        feature model, which this project does not build).
+
+        `noises[k-1]` is chunk k's initial noise.  Returns the NEW frames only, uint8 [n_chunks * 4 new, H, W, 3] (new =
+        T - prefix_frames), plus the fp32 video [3, frames, H, W] when want_float.  latents_out receives every new chunk's latent."""
+        d, lc = self.cfg.dit, self.cfg.llm
+        T, new, n_seg = self.stream_plan(n_chunks + 1, prefix_frames)
+        per_seg = self.cfg.tok.num_latent_tokens
+        if (frames is None) == (clip_latent is None):
+            raise ValueError("extend_video takes the clip as exactly one of frames and clip_latent")
+        if tokens is not None and clip_tokens is not None:
+            raise ValueError("extend_video: tokens already holds every segment; clip_tokens goes with a decode from the prompt")
+        if clip_latent is None:
+            window = continuation_window(frames, self.cfg)
+            if self.encoder is None:
+                raise ValueError("extend_video(frames=...) needs the VAE encoder's weights ('encoder.*' in the VAE state)")
+            t0 = time.perf_counter()
+            torch.manual_seed(inp.seed); torch.cuda.manual_seed(inp.seed)
+            clip_latent = self.encoder.encode(window.to(self.dev), sample=True)
+            self._t("vae_encode", t0)
+        if tuple(clip_latent.shape) != (1, T, d.in_channels, d.latent_h, d.latent_w):
+            raise ValueError(f"clip_latent must be [1, {T}, {d.in_channels}, {d.latent_h}, {d.latent_w}], got {tuple(clip_latent.shape)}")
+        if self.encoder is not None:
+            self.encoder.release()                        # its windows (13 GB at 480 x 720) are not needed by the DiT loop
+        prev = clip_latent.to(self.dev).to(torch.bfloat16).float()
+        t0 = time.perf_counter()
+        self.vae.decode(prev, stream_keep=True)           # chunk 0's decode: the caches generate_stream holds after it
+        self._t("vae", t0)
+        if tokens is None:
+            t0 = time.perf_counter()
+            torch.manual_seed(inp.seed); torch.cuda.manual_seed(inp.seed)
+            tokens = self.llm.sample(inp.llm_text_emb, motion_score=inp.motion_score, num_frames=n_seg * lc.segment_length,
+                                     guidance_scale=inp.cfg, temperature=1.0, seed=inp.seed, prefix_tokens=clip_tokens)
+            self._t("llm", t0)
+        tokens = tokens.to(self.dev).reshape(n_seg, per_seg)
+        sem_window = self._sem_windows(lambda sidx: tokens[sidx], T)
+        outs, vids = [], []
+        for k in range(1, n_chunks + 1):
+            prev, r = self._stream_chunk(inp, k, sem_window(k * new, k * new + T), noises[k - 1] if noises is not None else None,
+                                         prev, prefix_frames, torch.randn_like, want_float, keep=k < n_chunks,
+                                         latents_out=latents_out)
+            if want_float:
+                outs.append(r[0]); vids.append(r[1])
+            else:
+                outs.append(r)
+        out = torch.cat(outs, dim=0)
+        return (out, torch.cat(vids, dim=1)) if want_float else out
+
+
+def stream_plan(cfg: PipelineConfig, n_chunks: int, prefix_frames: int):
+    """(latent frames per chunk, new latent frames per later chunk, LLM segments needed) of an n_chunks stream."""
+    T, seg = cfg.dit.latent_frames, cfg.llm.segment_length
+    new = T - prefix_frames
+    assert 0 < prefix_frames < T and new % 2 == 0, "later chunks decode their new latent frames in pairs"
+    total = T + (n_chunks - 1) * new
+    return T, new, -(-total // seg)
+
+
+def continuation_window(frames, cfg: PipelineConfig):
+    """The clip frames LanDiffPipeline.extend_video encodes: the LAST 4T-3 of uint8 frames [F, 8 latent_h, 8 latent_w, 3]
+    (T = cfg.dit.latent_frames: 49 of a 480 x 720 clip in the shipped config).  A shorter clip, another frame size, dtype or
+    layout raises ValueError (resizing is not done here)."""
+    d = cfg.dit
+    n = 4 * d.latent_frames - 3
+    want = (8 * d.latent_h, 8 * d.latent_w, 3)
+    if frames.dim() != 4 or tuple(frames.shape[1:]) != want:
+        raise ValueError(f"clip frames must be [F, {want[0]}, {want[1]}, 3], got {tuple(frames.shape)}")
+    if frames.dtype != torch.uint8:
+        raise ValueError(f"clip frames must be uint8, got {frames.dtype}")
+    if frames.shape[0] < n:
+        raise ValueError(f"a clip of {frames.shape[0]} frames is too short: continuation encodes its last {n} frames "
+                         f"({d.latent_frames} latent frames)")
+    return frames[frames.shape[0] - n:]
 
 
 def synthetic_inputs(cfg: PipelineConfig, device, n_text: int = 64, seed: int = 42) -> PromptInputs:

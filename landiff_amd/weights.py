@@ -6,7 +6,7 @@ Key names are the reference's: ``llm/model.safetensors`` (Semantic1DLM), ``token
   llm  -> ''                                   tok -> '' (decoder.*, quantizer.*)
   ups  -> '<control>.semantic_conditioner.'    (upsample_model.*, conv_out.*)
   dit_main / dit_control -> 'model.{main,control}_model.diffusion_model.'
-  vae  -> '' (decoder.*)
+  vae  -> '' (decoder.*; encoder.* for VAEEncoder: load_vae_encoder_state)
 """
 from __future__ import annotations
 
@@ -223,6 +223,54 @@ def vae_spec(c: VAEConfig) -> Spec:
     return s
 
 
+def _res3d_enc(p: str, cin: int, cout: int) -> Spec:
+    """ContextParallelResnetBlock3D with plain GroupNorms (the encoder's, cp_enc_dec.py:684-782; temb_channels 0)."""
+    s = [(p + "norm1.weight", (cin,), "g"), (p + "norm1.bias", (cin,), "b"),
+         (p + "conv1.conv.weight", (cout, cin, 3, 3, 3), "w"), (p + "conv1.conv.bias", (cout,), "b"),
+         (p + "norm2.weight", (cout,), "g"), (p + "norm2.bias", (cout,), "b"),
+         (p + "conv2.conv.weight", (cout, cout, 3, 3, 3), "w"), (p + "conv2.conv.bias", (cout,), "b")]
+    if cin != cout:
+        s += [(p + "nin_shortcut.weight", (cout, cin, 1, 1, 1), "w"), (p + "nin_shortcut.bias", (cout,), "b")]
+    return s
+
+
+def vae_encoder_levels(c: VAEConfig):
+    """[(level, [(cin, cout)...], downsample: None|'space'|'space_time')] finest first (cp_enc_dec.py:815-848): num_res_blocks
+    blocks per level (the decoder has one more), time compressed by the first log2(temporal_compress_times) downsamples."""
+    tcl = {1: 0, 2: 1, 4: 2, 8: 3}[c.temporal_compress_times]
+    in_mult = (1,) + tuple(c.ch_mult)
+    out = []
+    for lvl in range(len(c.ch_mult)):
+        block_in, block_out = c.ch * in_mult[lvl], c.ch * c.ch_mult[lvl]
+        blocks = []
+        for _ in range(c.num_res_blocks):
+            blocks.append((block_in, block_out))
+            block_in = block_out
+        down = None
+        if lvl != len(c.ch_mult) - 1:
+            down = "space_time" if lvl < tcl else "space"
+        out.append((lvl, blocks, down))
+    return out
+
+
+def vae_encoder_spec(c: VAEConfig, in_channels: int = 3) -> Spec:
+    """The state-dict keys of ContextParallelEncoder3D under 'encoder.' (3d-vae.pt['state_dict'])."""
+    p = "encoder."
+    s = [(p + "conv_in.conv.weight", (c.ch, in_channels, 3, 3, 3), "w"), (p + "conv_in.conv.bias", (c.ch,), "b")]
+    last = c.ch
+    for lvl, blocks, down in vae_encoder_levels(c):
+        for j, (cin, cout) in enumerate(blocks):
+            s += _res3d_enc(p + f"down.{lvl}.block.{j}.", cin, cout)
+            last = cout
+        if down:
+            s += [(p + f"down.{lvl}.downsample.conv.weight", (last, last, 3, 3), "w"),
+                  (p + f"down.{lvl}.downsample.conv.bias", (last,), "b")]
+    s += _res3d_enc(p + "mid.block_1.", last, last) + _res3d_enc(p + "mid.block_2.", last, last)
+    s += [(p + "norm_out.weight", (last,), "g"), (p + "norm_out.bias", (last,), "b"),
+          (p + "conv_out.conv.weight", (2 * c.z_channels, last, 3, 3, 3), "w"), (p + "conv_out.conv.bias", (2 * c.z_channels,), "b")]
+    return s
+
+
 # ----------------------------------------------------------------------------------------------
 # seeded random init (synthetic weights for bench / parity tests; BASELINE.md section 3)
 # ----------------------------------------------------------------------------------------------
@@ -376,6 +424,17 @@ def load_diffusion_states(diffusion_dir: str, root: str | None = None, *, base_d
     vae = {k: v for k, v in _load_pickle(vae_path)["state_dict"].items() if k.startswith("decoder.")}    # lightning pickle
     vae.update({k: v for k, v in _sub(mod, "first_stage_model.").items() if k.startswith("decoder.")})
     return {"dit_main": main, "dit_control": ctrl, "tok": tok, "ups": ups, "vae": vae}
+
+
+def load_vae_encoder_state(root: str | None = None, *, vae_ckpt: str | None = None, diffusion_dir: str | None = None) -> dict:
+    """The encoder's state dict ('encoder.*' keys), in the precedence of the decoder's in load_diffusion_states: `vae_ckpt`
+    ['state_dict'] (default <root>/CogVideoX-2b-sat/vae/3d-vae.pt), then any 'first_stage_model.encoder.*' of the diffusion
+    checkpoint under `diffusion_dir` overrides it."""
+    vae_path = resolve_ckpt_path(vae_ckpt, root) if vae_ckpt is not None else os.path.join(root, CKPT_FILES["vae"])
+    enc = {k: v for k, v in _load_pickle(vae_path)["state_dict"].items() if k.startswith("encoder.")}
+    if diffusion_dir is not None:
+        enc.update({k: v for k, v in _sub(_sat_module(diffusion_dir), "first_stage_model.").items() if k.startswith("encoder.")})
+    return enc
 
 
 def save_checkpoint_tree(root: str, states: dict, *, iteration: str = "1", base_iteration: str = "1000",
