@@ -578,7 +578,9 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN >= 16) ? 4 : 2) void ld_gemm
   const int m0 = p.m_begin + (first_m + in_group % rows_here) * BM, n0 = (in_group / rows_here) * BN;
 
   // ---- per-thread source row offsets ----
-  uint32_t offA[A_LOADS], offW[B_LOADS];    // element offsets (< 2^31 for every shape on the path)
+  // element offsets, zero-extended where they are added to the pointers: < 2^32 for a convolution, whose padded input
+  // conv_cl keeps below CONV_MAX_BYTES = 8 GiB (a 49-frame 480 x 720 VAE-encoder level reaches 2.27e9)
+  uint32_t offA[A_LOADS], offW[B_LOADS];
 #pragma unroll
   for (int i = 0; i < A_LOADS; ++i) {
     const int r = (wave * A_LOADS + i) * 8 + (lane >> 3);

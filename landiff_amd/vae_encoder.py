@@ -19,7 +19,7 @@ import os
 
 import torch
 
-from . import ops
+from . import _lib, ops
 from .config import VAEConfig
 from .detokenizer import _conv_w, _dev
 from .weights import vae_encoder_levels, vae_encoder_spec
@@ -39,6 +39,42 @@ def s2d_conv_weight(w: torch.Tensor) -> torch.Tensor:
     wp = torch.nn.functional.pad(w, (0, 3, 0, 3))                          # [Co, C, 6, 6]: taps >= 3 are zero
     ws = wp.reshape(Co, C, 3, 2, 3, 2)                                      # [o, c, A, p, B, q]
     return ws.permute(0, 2, 4, 3, 5, 1).reshape(Co, 1, 3, 3, 4 * C).contiguous()   # [o, A, B, p, q, c]
+
+
+def encoder_convs(cfg: VAEConfig, F: int, H: int, W: int):
+    """Every convolution an F-frame H x W encode launches, in order: [(name, (T, H, W, Cin, Cout, kT, kH, kW))], the arguments
+    of ld_conv_route (the 1 x 1 x 1 shortcuts are GEMMs and are not listed)."""
+    T, C = F, cfg.ch
+    out = [("conv_in", (T, H, W, IN_PAD, C, 3, 3, 3))]
+    for lvl, blocks, down in vae_encoder_levels(cfg):
+        for j, (cin, cout) in enumerate(blocks):
+            out += [(f"down.{lvl}.block.{j}.conv1", (T, H, W, cin, cout, 3, 3, 3)),
+                    (f"down.{lvl}.block.{j}.conv2", (T, H, W, cout, cout, 3, 3, 3))]
+            C = cout
+        if down:
+            T, H, W = ops.vae_enc_downsample_out_frames(T, down == "space_time"), H // 2, W // 2
+            out.append((f"down.{lvl}.downsample", (T, H, W, 4 * C, C, 1, 3, 3)))
+    for b in ("mid.block_1", "mid.block_2"):
+        out += [(f"{b}.conv1", (T, H, W, C, C, 3, 3, 3)), (f"{b}.conv2", (T, H, W, C, C, 3, 3, 3))]
+    out.append(("conv_out", (T, H, W, C, 2 * cfg.z_channels, 3, 3, 3)))
+    return out
+
+
+def max_clip_frames(cfg: VAEConfig, H: int, W: int) -> int:
+    """The longest clip encode_moments takes at H x W: every convolution of the encode must have a route (ld_conv_route >= 0,
+    the launcher's own size rules, run dry).  The level-0 window is the first to reach the convolution's 8 GiB input limit:
+    94 frames at 480 x 720.  0 if not even one frame fits."""
+    lib = _lib.load()
+    fits = lambda F: all(lib.ld_conv_route(*shape) >= 0 for _, shape in encoder_convs(cfg, F, H, W))
+    if not fits(1):
+        return 0
+    lo, hi = 1, 2                       # fits(lo), and the input grows with F: double, then bisect
+    while fits(hi):
+        lo, hi = hi, 2 * hi
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if fits(mid) else (lo, mid)
+    return lo
 
 
 class VAEEncoder:
@@ -62,6 +98,7 @@ class VAEEncoder:
                 self.w[k] = _dev(v, self.dev)
         # same switch as the decoder's: GroupNorm statistics from the producing conv's epilogue (LD_VAE_GN_FUSE=0: a separate pass)
         self.fuse_gn_stats = os.environ.get("LD_VAE_GN_FUSE", "1") != "0"
+        self._max_frames = {}           # (H, W) -> max_clip_frames
         # zero-bordered conv inputs, one per shape, zero-filled once: every producer rewrites the whole interior (and the halo
         # frames), never the border; the encoder is a chain, so stream order is the only hazard between users of one buffer
         self._padded = {}
@@ -134,6 +171,11 @@ class VAEEncoder:
         F, H, W, _ = frames.shape
         if H % 8 or W % 8:
             raise ValueError(f"frame size {H}x{W}: height and width must be multiples of 8")
+        if (H, W) not in self._max_frames:
+            self._max_frames[H, W] = max_clip_frames(cfg, H, W)
+        if F > self._max_frames[H, W]:
+            raise ValueError(f"a {F}-frame clip at {H}x{W} is too long: the encoder takes at most {self._max_frames[H, W]} frames "
+                             f"at this size (its level-0 convolution input would pass the 8 GiB the kernels address)")
         frames = frames.to(self.dev).contiguous()
         if frames.dtype != torch.uint8:
             frames = frames.float().contiguous()

@@ -81,6 +81,28 @@ def test_conv_route_keeps_large_inputs_off_the_8_phase_kernel():
     assert lib.ld_conv_route(8, 480, 720, 128, 256, 1, 3, 3) == 0            # K = 1152: short
 
 
+def test_conv_routes_of_a_49_frame_encode():
+    """Every convolution of a 49 x 480 x 720 encode (the clip extend_video encodes), as the launcher routes it: level 0 -- 4.2 GiB
+    windows, 2.2e9 elements -- and conv_in / the level-0 downsample (just above 2 GiB) on the 128 x 128 two-stage kernel; the
+    8-phase kernel only for inputs below 2 GiB."""
+    from landiff_amd import _lib
+    from landiff_amd.config import VAEConfig
+    from landiff_amd.vae_encoder import encoder_convs
+    lib = _lib.load()
+    convs = encoder_convs(VAEConfig(), 49, 480, 720)
+    assert len(convs) == 1 + 2 * 12 + 3 + 4 + 1
+    gib = lambda T, H, W, Cin, Cout, kT, kH, kW: (T + kT - 1) * (H + kH - 1) * (W + kW - 1) * Cin * 2 / 2 ** 30
+    routes = {n: lib.ld_conv_route(*s) for n, s in convs}
+    for n, s in convs:
+        assert routes[n] in (0, 1, 2), (n, s, routes[n])
+        if n.startswith("down.0.") or n == "conv_in":
+            assert routes[n] == 0 and gib(*s) > 2, (n, gib(*s))
+        if routes[n] == 2:
+            assert gib(*s) < 2, (n, gib(*s))
+    assert gib(*dict(convs)["down.0.block.0.conv1"]) > 4 and gib(*dict(convs)["down.0.downsample"]) > 2
+    assert [routes[f"down.1.block.{j}.conv2"] for j in range(3)] == [2, 2, 2]
+
+
 def test_decode_step_forms_validate_without_gpu():
     """The alternative forms of a decode step's blocks (one persistent launch / dependent launches on two streams) reject null
     pointers and shapes outside their register forms before any HIP call: LD_ERR_INVALID (-1) / LD_ERR_UNSUPPORTED (-3).

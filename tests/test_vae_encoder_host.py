@@ -109,3 +109,40 @@ def test_load_clip(tmp_path):
     np.save(tmp_path / "bad.npy", clip.astype(np.float32))
     with pytest.raises(ValueError, match="uint8"):
         load_clip(str(tmp_path / "bad.npy"))
+
+
+@pytest.mark.parametrize("clip,slice_frames", [("odd", 2), ("odd", 3), ("even", 3)])
+def test_sliced_restatement_matches_the_whole_clip_one(gold, clip, slice_frames):
+    """The sliced mode of the restatement (activations in pieces of a few frames, each causal conv and downsample with its halo,
+    GroupNorm statistics summed in float64 over the pieces) computes what the whole-clip restatement computes: it stands in for
+    it where a whole activation would pass 2^31 elements."""
+    from vae_encoder_ref import encode_moments_ref
+    cfg = VAEConfig.tiny()
+    sd = init_state(vae_encoder_spec(cfg), seed=int(gold["weight_seed"]))
+    x = torch.from_numpy(gold[f"{clip}_x"])
+    assert x.shape[0] > 2 * slice_frames                        # at least three pieces at level 0
+    for dtype, tol in ((torch.float32, 1e-5), (torch.bfloat16, 2e-2)):
+        mean, logvar = encode_moments_ref(sd, cfg, x, dtype=dtype)
+        ms, ls = encode_moments_ref(sd, cfg, x, dtype=dtype, slice_frames=slice_frames)
+        assert ms.shape == mean.shape and ls.shape == logvar.shape
+        assert rel(ms, mean) < tol and rel(ls, logvar) < tol, (dtype, rel(ms, mean), rel(ls, logvar))
+
+
+def test_max_clip_frames():
+    """At 480 x 720 the encoder takes at most 94 frames: 95 need a 97 x 482 x 722 x 128 bf16 level-0 window (8.05 GiB), beyond
+    the 8 GiB ld_conv_cl_bf16 addresses.  encode_moments refuses a longer clip before it allocates or launches anything."""
+    from landiff_amd import _lib
+    from landiff_amd.vae_encoder import VAEEncoder, encoder_convs, max_clip_frames
+    cfg = VAEConfig()
+    lib = _lib.load()
+    assert max_clip_frames(cfg, 480, 720) == 94
+    assert all(lib.ld_conv_route(*s) >= 0 for _, s in encoder_convs(cfg, 94, 480, 720))
+    refused = [n for n, s in encoder_convs(cfg, 95, 480, 720) if lib.ld_conv_route(*s) < 0]
+    assert refused == [f"down.0.block.{j}.conv{i}" for j in range(3) for i in (1, 2)]
+    assert 97 * 482 * 722 * 128 * 2 >= 2 ** 33 > 96 * 482 * 722 * 128 * 2
+    enc = VAEEncoder.__new__(VAEEncoder)                        # no weights needed: the check comes first
+    enc.cfg, enc.dev, enc._max_frames, enc._padded = cfg, torch.device("cpu"), {}, {}
+    clip = torch.zeros(1, 1, 1, 3, dtype=torch.uint8).expand(95, 480, 720, 3)
+    with pytest.raises(ValueError, match="at most 94 frames"):
+        enc.encode_moments(clip)
+    assert enc._padded == {}
