@@ -28,8 +28,9 @@ extern "C" {
  * 6: ld_reset and ld_attn_queue_poke were added.  7: ld_conv_cl_bf16_gn, ld_conv_gn_partials_size and
  * ld_groupnorm_stats_from_conv were added.  8: ld_gemm_qkv_heads_mxfp8 was added.
  * 9: ld_attn_fwd_bf16_exact was added.  10: ld_attn_last_fallbacks was added.  11: ld_vae_enc_place_input,
- * ld_vae_enc_downsample and ld_vae_posterior were added. */
-#define LD_ABI_VERSION 11
+ * ld_vae_enc_downsample and ld_vae_posterior were added.  12: ld_vit_patch_rows, ld_vit_embed and ld_vit_tail were added,
+ * ld_qkv_split gained mode 2. */
+#define LD_ABI_VERSION 12
 
 int ld_version(void);
 const char* ld_last_error(void);
@@ -388,7 +389,8 @@ int ld_layernorm(const void* x, int64_t ldx, int32_t x_f32, const void* w, const
 
 /* qkv [B*N][3*H*64] (thirds q|k|v, sat SelfAttention layout) -> Q,K [B][H][Npad][64] (zero padded) and
  * V^T [B][H][64][Npad].  mode 0: LayerNorm(64, eps) on q,k heads (dit_video_concat.py:649-653);
- * mode 1: interleaved-pair RoPE with cos/sin [N][32] (blocks.py:172-180, pos_emb.py:16-46). */
+ * mode 1: interleaved-pair RoPE with cos/sin [N][32] (blocks.py:172-180, pos_emb.py:16-46);
+ * mode 2: the plain split, no normalisation or rotation (HF ViTSelfAttention of the Theia backbone; no weights needed). */
 int ld_qkv_split(const void* qkv, void* Q, void* K, void* Vt, int64_t B, int64_t N, int64_t H, int64_t Npad,
                  int32_t mode, const void* q_w, const void* q_b, const void* k_w, const void* k_b, float eps,
                  const float* cos_t, const float* sin_t, void* stream);
@@ -474,6 +476,30 @@ int ld_vae_enc_downsample(const void* x, void* out, int64_t T, int64_t H, int64_
  * [1, Z, T, H, W] mean), or scale * mean when eps is null.  mean / logvar (optional, [T][Z][H][W] f32) get the unscaled values. */
 int ld_vae_posterior(const float* x, int64_t ldx, const float* eps, float* z, float* mean, float* logvar, int64_t T,
                      int64_t Z, int64_t H, int64_t W, float scale, void* stream);
+
+/* ---- Theia feature extractor (ld_theia.hip; DeiT-base = HF ViTModel, theia_model.py:441-451 + theia_extractor.py:88-139,
+ * run with interpolate=True under bf16 autocast).  Its linears are ld_gemm_bf16, its LayerNorms ld_layernorm, its head split
+ * ld_qkv_split mode 2 and its attention ld_attn_fwd_bf16 (B = frames in one launch). ---- */
+
+/* The patch Conv2d's im2col rows: out bf16 [T*P][768], P = (S/16)^2 (integer division), row t*P + py*(S/16) + px, column c*256 + kh*16 + kw
+ * (the Conv2d weight's (c, kh, kw) order) = bf16((u - 127.5f) / 127.5f) of pixel (16py + kh, 16px + kw) of channel c
+ * (DeiT.yax_processor, theia_model.py:446-451).  nhwc = 0: frames uint8 [T][3][S][S] (H = W = S); nhwc = 1: frames uint8
+ * [T][H][W][3] with H, W <= S, padded right and bottom with 127 to S x S as pad_to_square does (condition.py:15-27) without
+ * materialising the square.  S >= 16; the last S % 16 rows / columns are dropped, as by the stride-16 Conv2d. */
+int ld_vit_patch_rows(const void* frames, int32_t nhwc, void* out, int64_t T, int64_t H, int64_t W, int64_t S, void* stream);
+
+/* ViTEmbeddings after the patch Conv2d: x f32 [T][1+P][C] <- row 0 of each frame pos[0] (CLS + its position, added once on the
+ * host), row 1+p float(patch[t*P + p]) + pos[1+p]; patch bf16 [T*P][C] (the Conv2d's bf16 output), pos f32 [1+P][C] the
+ * interpolated position table.  C % 4 == 0. */
+int ld_vit_embed(const void* patch, const float* pos, float* x, int64_t T, int64_t P, int64_t C, void* stream);
+
+/* The extractor's end: final LayerNorm (fp32 weights, eps) of x f32 [T][N = 1 + s*s][C], CLS dropped, then
+ * TheiaExtractor's output_shape rule on the s x s grid: position (i, j) of the (gh, gw) output = token 1 + i*s + j when
+ * i < s and j < s, else 0 (the crop branch and the zero-pad-then-crop branch agree on a square grid).  Outputs (either may be
+ * null): feat f32 [T][C][gh][gw] (the feature_extractor contract) and cl bf16 [T*gh*gw][C] = bf16((y - mean[c]) / (std[c] +
+ * 1e-8)), exactly ld_feature_norm_cl of feat, the TiTok encoder's input rows. */
+int ld_vit_tail(const float* x, const float* ln_w, const float* ln_b, float eps, int64_t T, int64_t N, int64_t s,
+                int64_t gh, int64_t gw, int64_t C, float* feat, void* cl, const float* mean, const float* stdv, void* stream);
 
 /* ---- T5 text encoders (HF transformers T5EncoderModel called from
  * landiff/llm/modules/text_encoder.py:36-42,82-112 and landiff/diffusion/sgm/modules/encoders/modules.py:249-292) ---- */

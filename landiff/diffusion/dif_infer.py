@@ -61,11 +61,17 @@ class CogWrapper(torch.nn.Module):
     used only when forward() gets no seed (then hashed with the prompt, :190-194)."""
 
     def __init__(self, cfg: DiffusionInferConfig, ckpt_path: str, device, seed: int = 1234, text_encoder=None,
-                 feature_extractor=None):
+                 feature_extractor=None, theia_ckpt: str | None = None):
         super().__init__()
+        if feature_extractor is not None and theia_ckpt is not None:
+            raise ValueError("give the Theia extractor as one of feature_extractor and theia_ckpt")
         self.cfg, self.device_, self.seed = cfg, device, seed
         self.image_size = list(cfg.image_size)
         self.text_encoder, self.feature_extractor = text_encoder, feature_extractor
+        self.theia = None               # landiff_amd.theia.TheiaExtractor of theia_ckpt
+        if theia_ckpt is not None:
+            from landiff_amd.theia import build_theia
+            self.theia = build_theia(theia_ckpt, cfg.tok, device)
         st = load_diffusion_states(resolve_ckpt_path(ckpt_path), None, base_dit_ckpt=cfg.base_dit_ckpt, vae_ckpt=cfg.vae_ckpt,
                                    tokenizer_ckpt=cfg.tokenizer_ckpt or None)
         self.detok = Detokenizer(st["tok"], st["ups"], cfg.tok, cfg.ups, device)
@@ -93,12 +99,13 @@ class CogWrapper(torch.nn.Module):
         """Control signal from a conditioning video (ControlDiffusionTransformer.forward :960-975 -> SemanticCond.forward(visual)
         :112-137 -> VideoVQWrap.forward(images) vq_warp.py:88-118): t equally spaced frames, [-1,1] -> uint8, padded to a square
         with grey 127, Theia features -> tokenizer encoder -> nearest code -> tokenizer decoder -> upsampler.  The Theia backbone
-        is a Hugging Face remote-code model that this package does not build: `feature_extractor` supplies it."""
-        if self.feature_extractor is None:
+        is `feature_extractor` (any callable), or the HIP extractor of `theia_ckpt` (landiff_amd.theia), which makes the square
+        padding inside its first kernel and hands the tokenizer encoder channels-last rows."""
+        if self.feature_extractor is None and self.theia is None:
             raise NotImplementedError(
                 "VideoTask.mp4 (video-conditioned generation) needs the Theia feature extractor (landiff/tokenizer/models/"
-                "feature_extractor/theia_extractor.py), a Hugging Face remote-code model that is not built here: pass "
-                "CogModelInferWrapper(..., feature_extractor=callable uint8 [T,3,S,S] -> features [T,C,h,w]) or give semantic_token")
+                "feature_extractor/theia_extractor.py): pass CogModelInferWrapper(..., theia_ckpt=<Theia model.safetensors>) or "
+                "CogModelInferWrapper(..., feature_extractor=callable uint8 [T,3,S,S] -> features [T,C,h,w]), or give semantic_token")
         d, tc = self.cfg.dit, self.cfg.tok
         v = mp4_btchw[0]
         idx = torch.linspace(0, v.shape[0] - 1, d.latent_frames).long().to(v.device)
@@ -107,17 +114,25 @@ class CogWrapper(torch.nn.Module):
         # torchvision v2.functional.to_dtype(uint8, scale=True) on a float image: image.mul(255 + 1 - 1e-3).to(uint8), i.e.
         # truncation of x * 255.999 (torchvision is not in this image: restated from its float -> int conversion rule)
         v = v.float().mul(255.0 + 1.0 - 1e-3).to(torch.uint8)
+        if self.theia is not None:
+            self.theia.encoder = self._tokenizer_encoder()
+            tokens = self.theia.tokenize_video(v.permute(0, 2, 3, 1).contiguous())       # [T, H, W, 3], padded by the kernel
+            return self.detok.semantic_condition(tokens)
         H, W = v.shape[-2:]
         S = max(H, W)
         sq = torch.full((v.shape[0], v.shape[1], S, S), 127, dtype=torch.uint8, device=v.device)
         sq[..., :H, :W] = v                                                # pad_to_square: right / bottom (condition.py:14-27)
         feats = self.feature_extractor(sq)
         assert feats.shape == (tc.temporal, tc.out_channels, tc.grid_h, tc.grid_w), f"feature_extractor returned {tuple(feats.shape)}"
+        tokens = self._tokenizer_encoder().encode_to_index(feats.to(self.device_))
+        return self.detok.semantic_condition(tokens)
+
+    def _tokenizer_encoder(self):
         if self._encoder is None:
             from landiff_amd.tokenizer_encoder import TokenizerEncoder
-            self._encoder = TokenizerEncoder(load_tokenizer_encoder_state(resolve_ckpt_path(self.cfg.tokenizer_ckpt)), tc, self.device_)
-        tokens = self._encoder.encode_to_index(feats.to(self.device_))
-        return self.detok.semantic_condition(tokens)
+            self._encoder = TokenizerEncoder(load_tokenizer_encoder_state(resolve_ckpt_path(self.cfg.tokenizer_ckpt)),
+                                             self.cfg.tok, self.device_)
+        return self._encoder
 
     @torch.no_grad()
     def encode_first_stage(self, x: torch.Tensor) -> torch.Tensor:
@@ -174,15 +189,17 @@ class CogModelInferWrapper(torch.nn.Module):
     """CogModelInferWrapper(ckpt_path, infer_cfg_path, model_cfg_path)(VideoTask) -> VideoTask with .result FloatTensor
     [3, 4T-3, H, W] in [0,1] on CPU (dif_infer.py:274-302).
     text_encoder: optional callable prompts -> [1, text_length, 4096] T5 states (pre-computed embeddings) replacing the
-    T5-v1.1-XXL run; feature_extractor: the Theia backbone for VideoTask.mp4 (see CogWrapper._semantic_from_video)."""
+    T5-v1.1-XXL run; feature_extractor: the Theia backbone for VideoTask.mp4 (see CogWrapper._semantic_from_video), or
+    theia_ckpt: a Theia model.safetensors (or its directory) that the HIP extractor is built from (landiff_amd.theia)."""
 
     def __init__(self, ckpt_path: str, infer_cfg_path: str = DEFAULT_INFER_CFG, model_cfg_path: str = DEFAULT_MODEL_CFG,
-                 device="cuda", text_encoder=None, feature_extractor=None):
+                 device="cuda", text_encoder=None, feature_extractor=None, theia_ckpt: str | None = None):
         super().__init__()
         self.infer_cfg_path, self.model_cfg_path, self.ckpt_path = infer_cfg_path, model_cfg_path, ckpt_path
         cfg = load_diffusion_config(_cfg_path(model_cfg_path), _cfg_path(infer_cfg_path))
         dev = torch.device(device if device != "cuda" else f"cuda:{torch.cuda.current_device()}")
-        self.init_infer_model = CogWrapper(cfg, ckpt_path, dev, text_encoder=text_encoder, feature_extractor=feature_extractor)
+        self.init_infer_model = CogWrapper(cfg, ckpt_path, dev, text_encoder=text_encoder, feature_extractor=feature_extractor,
+                                           theia_ckpt=theia_ckpt)
 
     @torch.no_grad()
     def forward(self, x: VideoTask) -> VideoTask:

@@ -31,17 +31,67 @@ def parse_args(argv=None):
     parser.add_argument("--extend_tokens", type=str, default=None,
                         help="The clip's own semantic tokens (.npy of llm_infer, one segment): the AR decode continues from "
                              "them instead of sampling every segment from the prompt.")
+    parser.add_argument("--theia_ckpt", type=str, default=None,
+                        help="Theia model.safetensors (or its directory).  With --extend_video and no --extend_tokens the clip's "
+                             "own tokens, from its frames, are the decode's first segment.  Also where --first_frame looks "
+                             "(default: $LANDIFF_THEIA_CKPT, then a local Hugging Face cache snapshot; never downloaded).")
+    parser.add_argument("--first_frame", type=str, default=None,
+                        help="Image-guided generation (use_gt_first_frame): a uint8 [H, W, 3] .npy or an image imageio can "
+                             "read, tokenized by the Theia extractor; its I-frame tokens start the AR decode.")
     return parser.parse_args(argv)
+
+
+def load_image(path: str) -> torch.Tensor:
+    """uint8 image [H, W, 3] from a .npy or, through imageio, an image file."""
+    if path.endswith(".npy"):
+        arr = np.load(path)
+    else:
+        try:
+            import imageio
+        except ImportError as e:
+            raise ValueError(f"{path}: reading an image file needs imageio; give the uint8 [H, W, 3] pixels as .npy instead") from e
+        arr = np.asarray(imageio.imread(path))
+        if arr.ndim == 3 and arr.shape[-1] == 4:
+            arr = arr[..., :3]
+    if arr.dtype != np.uint8 or arr.ndim != 3 or arr.shape[-1] != 3:
+        raise ValueError(f"{path}: expected a uint8 image [H, W, 3], got {arr.dtype} {arr.shape}")
+    return torch.from_numpy(np.ascontiguousarray(arr))
+
+
+def build_theia_tokenizer(args, dev):
+    """The Theia extractor (--theia_ckpt, else $LANDIFF_THEIA_CKPT / the HF cache) with the tokenizer's encoder half attached
+    (tokenizer_ckpt of the diffusion stage's YAML), its output grid the tokenizer's."""
+    from landiff.diffusion.dif_infer import DEFAULT_INFER_CFG, DEFAULT_MODEL_CFG, _cfg_path
+    from landiff_amd.config import load_diffusion_config
+    from landiff_amd.theia import build_theia
+    from landiff_amd.tokenizer_encoder import TokenizerEncoder
+    from landiff_amd.weights import load_tokenizer_encoder_state, resolve_ckpt_path
+    dcfg = load_diffusion_config(_cfg_path(DEFAULT_MODEL_CFG), _cfg_path(DEFAULT_INFER_CFG))
+    enc = TokenizerEncoder(load_tokenizer_encoder_state(resolve_ckpt_path(dcfg.tokenizer_ckpt)), dcfg.tok, dev)
+    return build_theia(args.theia_ckpt, dcfg.tok, dev, encoder=enc)
+
+
+def first_frame_tokens(args) -> torch.Tensor:
+    """--first_frame: the image's semantic tokens (TheiaExtractor.tokenize_image; the LLM keeps the I-frame ones)."""
+    img = load_image(args.first_frame)
+    dev = torch.device(f"cuda:{torch.cuda.current_device()}")
+    theia = build_theia_tokenizer(args, dev)
+    tokens = theia.tokenize_image(img.to(dev)).cpu()
+    del theia
+    torch.cuda.empty_cache()
+    return tokens
 
 
 def llm_infer(args):
     llm_model_cfg = build_llm()
+    first = first_frame_tokens(args) if args.first_frame else None
     llm = ArModelInferWrapper(args.llm_ckpt, llm_model_cfg)
     # one segment of semantic frames = one 49-frame clip: 13 for the shipped configuration (ARSampleCfg's default, which the
     # reference's llm_infer relies on); a configuration with another segment length (BASELINE configs[0]: 8) decodes its own
     task = CodeTask(save_file_name=f"{args.save_file_name}.npy", prompt=args.prompt, seed=args.seed,
                     sample_cfg=ARSampleCfg(temperature=1.0, cfg=args.cfg, motion_score=args.motion_score,
-                                           num_frames=llm_model_cfg.segment_length))
+                                           num_frames=llm_model_cfg.segment_length, use_gt_first_frame=first is not None),
+                    first_frame_tokens=first)
     task = llm(task)
     tokens = task.result.reshape(-1)
     path = Path(task.save_file_name)
@@ -100,17 +150,23 @@ def build_continuation(args):
     text = encode_flan_t5([args.prompt], dev, max_length=c.max_cond_tokens, model_path=c.text_encoder_path)[0]
     ctx = encode_t5_v11([args.prompt], resolve_ckpt_path(dcfg.t5_dir), cfg.dit.text_len, dev)
     inp = PromptInputs(text, ctx, seed=args.seed, cfg=args.cfg, motion_score=args.motion_score)
+    if args.theia_ckpt and not args.extend_tokens:
+        pipe.theia = build_theia_tokenizer(args, dev)
     return pipe, inp
 
 
 def extend_diffusion(args):
     """--extend_video: LanDiffPipeline.extend_video on the clip -- its last 4T-3 frames encoded, the chunks after it run as
     generate_stream runs its later chunks (sliding semantic windows of one multi-segment AR decode, the prefix latents pinned,
-    the decode continued against the VAE caches); --extend_tokens forces the decode's first segment to the clip's own tokens.
+    the decode continued against the VAE caches); --extend_tokens forces the decode's first segment to the clip's own tokens, and
+    so does --theia_ckpt without --extend_tokens, with the tokens computed from the clip's frames.
     Writes the clip followed by the new frames."""
     clip = load_clip(args.extend_video)
     pipe, inp = build_continuation(args)
-    clip_tokens = torch.from_numpy(np.load(args.extend_tokens)).reshape(-1) if args.extend_tokens else None
+    if args.extend_tokens:
+        clip_tokens = torch.from_numpy(np.load(args.extend_tokens)).reshape(-1)
+    else:
+        clip_tokens = "from_frames" if args.theia_ckpt else None
     new = pipe.extend_video(inp, args.extend_chunks, frames=clip, clip_tokens=clip_tokens,
                             prefix_frames=args.extend_prefix_frames)
     frames = torch.cat([clip, new.cpu()], dim=0)

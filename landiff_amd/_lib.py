@@ -44,7 +44,7 @@ class LlmLayer(Structure):
 
 
 _lib = None
-ABI_VERSION = 11         # LD_ABI_VERSION of include/landiff_hip.h that SIGNATURES below were written against
+ABI_VERSION = 12         # LD_ABI_VERSION of include/landiff_hip.h that SIGNATURES below were written against
 
 I64 = c_int64
 I32 = c_int32
@@ -104,6 +104,9 @@ SIGNATURES: dict[str, list] = {
     "ld_vae_enc_place_input": [P, I32, P, I64, I64, I64, I64, P],
     "ld_vae_enc_downsample": [P, P, I64, I64, I64, I64, I32, P],
     "ld_vae_posterior": [P, I64, P, P, P, P, I64, I64, I64, I64, c_float, P],
+    "ld_vit_patch_rows": [P, I32, P, I64, I64, I64, I64, P],
+    "ld_vit_embed": [P, P, P, I64, I64, I64, P],
+    "ld_vit_tail": [P, P, P, c_float, I64, I64, I64, I64, I64, I64, P, P, P, P, P],
     "ld_t5_rmsnorm": [P, P, P, I64, I64, c_float, P],
     "ld_t5_attn": [P, P, P, P, I64, P, P, I64, I64, P],
 }

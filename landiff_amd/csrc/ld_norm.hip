@@ -451,7 +451,8 @@ __global__ __launch_bounds__(256) void ld_layernorm_mx_kernel(LnParams p, unsign
 
 // ---------------------------------------------------------------------------------------------
 // qkv [B*N][3*H*64] (thirds q|k|v) -> Q,K [B][H][Npad][64] and V^T [B][H][64][Npad].
-// mode 0: per-head LayerNorm(64) on q and k (DiT);  mode 1: interleaved-pair RoPE with a [N][32] table (TiTok).
+// mode 0: per-head LayerNorm(64) on q and k (DiT);  mode 1: interleaved-pair RoPE with a [N][32] table (TiTok);
+// mode 2: the plain split (ViT of the Theia extractor: biased q/k/v, no QK-LN, no RoPE).
 // One workgroup = 64 tokens x 1 head.
 // ---------------------------------------------------------------------------------------------
 struct SplitParams {
@@ -500,7 +501,7 @@ __global__ __launch_bounds__(256) void ld_qkv_split_kernel(SplitParams p) {
       const bf16_t* bb = which ? p.kb : p.qb;
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[e] = (v[e] - mean) * rstd * bf2f(w[sub * 8 + e]) + bf2f(bb[sub * 8 + e]);
-    } else if (valid) {
+    } else if (p.mode == 1 && valid) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float c = p.cos_t[(long)n * 32 + sub * 4 + e], s = p.sin_t[(long)n * 32 + sub * 4 + e];
@@ -861,7 +862,9 @@ LD_API int ld_qkv_split(const void* qkv, void* Q, void* K, void* Vt, int64_t B, 
                         const float* cos_t, const float* sin_t, void* stream) {
   LD_REQUIRE(qkv && Q && K && Vt, "ld_qkv_split: null pointer");
   LD_REQUIRE(Npad % 64 == 0 && Npad >= N, "ld_qkv_split: Npad must be a multiple of 64 and >= N");
-  LD_REQUIRE(mode == 0 ? (q_w && q_b && k_w && k_b) : (cos_t && sin_t), "ld_qkv_split: missing LN weights / RoPE table");
+  LD_REQUIRE(mode >= 0 && mode <= 2, "ld_qkv_split: mode must be 0, 1 or 2");
+  LD_REQUIRE(mode == 0 ? (q_w && q_b && k_w && k_b) : mode == 1 ? (cos_t && sin_t) : true,
+             "ld_qkv_split: missing LN weights / RoPE table");
   SplitParams p{};
   p.qkv = (const bf16_t*)qkv; p.Q = (bf16_t*)Q; p.K = (bf16_t*)K; p.Vt = (bf16_t*)Vt;
   p.qw = (const bf16_t*)q_w; p.qb = (const bf16_t*)q_b; p.kw = (const bf16_t*)k_w; p.kb = (const bf16_t*)k_b;

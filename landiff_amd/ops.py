@@ -464,8 +464,10 @@ def gemm_qkv_heads_mxfp8(a8, sa, w8, sw, bias, q, k, vt, B, N, H, Npad, ln, eps=
 
 
 def qkv_split(qkv, q, k, vt, B, N, H, Npad, *, ln=None, rope=None, eps=1e-6):
-    """ln = (q_w, q_b, k_w, k_b) for the DiT QK-LayerNorm, or rope = (cos, sin) [N,32] fp32 for TiTok."""
-    mode = 0 if ln is not None else 1
+    """ln = (q_w, q_b, k_w, k_b) for the DiT QK-LayerNorm, or rope = (cos, sin) [N,32] fp32 for TiTok; neither: the plain
+    split (mode 2, the Theia ViT)."""
+    assert ln is None or rope is None
+    mode = 0 if ln is not None else 1 if rope is not None else 2
     lw = ln if ln is not None else (None,) * 4
     rp = rope if rope is not None else (None, None)
     check(_lib.load().ld_qkv_split(_ptr(qkv), _ptr(q), _ptr(k), _ptr(vt), B, N, H, Npad, mode, _ptr(lw[0]), _ptr(lw[1]),
@@ -596,3 +598,45 @@ def t5_attn(q, k, v, out, bias_table, bucket, H):
     check(_lib.load().ld_t5_attn(_ptr(q), _ptr(k), _ptr(v), _ptr(out), ld, _ptr(bias_table), _ptr(bucket), N, H, _stream()),
           "ld_t5_attn")
     return out
+
+
+# ---- Theia feature extractor (ld_theia.hip) ----------------------------------------------------------------
+def vit_patch_rows(frames, out, S, nhwc):
+    """uint8 frames [T,3,S,S] (nhwc=False) or [T,H,W,3] with H, W <= S (nhwc=True, grey-127 square padding made on the fly)
+    -> out bf16 [T*(S/16)^2, 768] im2col rows of the patch Conv2d, bf16((u - 127.5) / 127.5)."""
+    assert frames.dtype == torch.uint8 and frames.is_contiguous() and frames.dim() == 4
+    _bf16(out, "out")
+    T = frames.shape[0]
+    H, W = (frames.shape[1], frames.shape[2]) if nhwc else (frames.shape[2], frames.shape[3])
+    assert (frames.shape[3] == 3) if nhwc else (frames.shape[1] == 3)
+    assert out.is_contiguous() and tuple(out.shape) == (T * (S // 16) ** 2, 768)
+    check(_lib.load().ld_vit_patch_rows(_ptr(frames), int(nhwc), _ptr(out), T, H, W, S, _stream()), "ld_vit_patch_rows")
+    return out
+
+
+def vit_embed(patch, pos, x, T, P):
+    """patch bf16 [T*P, C], pos f32 [1+P, C] (row 0 = CLS + its position) -> x f32 [T*(1+P), C]."""
+    _bf16(patch, "patch")
+    C = patch.shape[1]
+    assert patch.is_contiguous() and patch.shape[0] == T * P
+    assert pos.dtype == torch.float32 and pos.is_contiguous() and tuple(pos.shape) == (1 + P, C)
+    assert x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == (T * (1 + P), C)
+    check(_lib.load().ld_vit_embed(_ptr(patch), _ptr(pos), _ptr(x), T, P, C, _stream()), "ld_vit_embed")
+    return x
+
+
+def vit_tail(x, ln_w, ln_b, eps, T, s, gh, gw, feat=None, cl=None, mean=None, std=None):
+    """x f32 [T*(1+s*s), C] -> final LayerNorm, CLS dropped, crop / zero pad of the s x s grid to (gh, gw): feat f32 [T,C,gh,gw]
+    and / or cl bf16 [T*gh*gw, C] = bf16((feat - mean) / (std + 1e-8)) channels-last."""
+    C = x.shape[1]
+    N = 1 + s * s
+    assert x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == (T * N, C)
+    assert ln_w.dtype == torch.float32 and ln_b.dtype == torch.float32 and ln_w.numel() == C and ln_b.numel() == C
+    if feat is not None:
+        assert feat.dtype == torch.float32 and feat.is_contiguous() and tuple(feat.shape) == (T, C, gh, gw)
+    if cl is not None:
+        _bf16(cl, "cl")
+        assert cl.is_contiguous() and tuple(cl.shape) == (T * gh * gw, C)
+        assert mean.dtype == torch.float32 and std.dtype == torch.float32 and mean.numel() == C and std.numel() == C
+    check(_lib.load().ld_vit_tail(_ptr(x), _ptr(ln_w), _ptr(ln_b), float(eps), T, N, s, gh, gw, C, _ptr(feat), _ptr(cl),
+                                  _ptr(mean), _ptr(std), _stream()), "ld_vit_tail")

@@ -41,7 +41,7 @@ class PromptInputs:
 
 class LanDiffPipeline:
     def __init__(self, cfg: PipelineConfig, states: dict, device="cuda:0", max_llm_frames: int | None = None,
-                 fp8_gemm: bool = False):
+                 fp8_gemm: bool = False, theia=None):
         if not torch.cuda.is_available():
             raise _lib.LandiffHipError("LanDiffPipeline needs an MI355X GPU: there is no CPU fallback")
         _lib.load()
@@ -60,6 +60,9 @@ class LanDiffPipeline:
         # (weights.load_vae_encoder_state, or a synthetic tree whose states["vae"] has them)
         self.encoder = (VAEEncoder(states["vae"], cfg.vae, self.dev)
                         if any(k.startswith("encoder.") for k in states["vae"]) else None)
+        # the Theia extractor of extend_video(clip_tokens="from_frames"): a landiff_amd.theia.TheiaExtractor whose `encoder` is
+        # the tokenizer's encoder half (optional; nothing else uses it)
+        self.theia = theia
         self.timings = {}
 
     def _t(self, name, t0):
@@ -333,9 +336,10 @@ class LanDiffPipeline:
 
         Semantic tokens (at most one of the two): `tokens` = every segment's ids (n_seg * num_latent_tokens, as generate_stream takes them); otherwise
         one multi-segment AR decode from the prompt, with segment 0 forced to `clip_tokens` (int64 [num_latent_tokens], e.g.
-        the .npy llm_infer saves next to a video) when given.  Without clip_tokens every segment is sampled from the prompt:
-        the prefix frames' control features then come from the prompt, not from the clip (tokens from pixels need the Theia
-        feature model, which this project does not build).
+        the .npy llm_infer saves next to a video) when given.  clip_tokens="from_frames": the clip's own tokens, from the Theia
+        extractor (`theia`) on T frames of the encoded window picked as CogWrapper._semantic_from_video picks them (linspace),
+        timed as "theia".  Without clip_tokens every segment is sampled from the prompt: the prefix frames' control features
+        then come from the prompt, not from the clip.
 
         `noises[k-1]` is chunk k's initial noise.  Returns the NEW frames only, uint8 [n_chunks * 4 new, H, W, 3] (new =
         T - prefix_frames), plus the fp32 video [3, frames, H, W] when want_float.  latents_out receives every new chunk's latent."""
@@ -346,6 +350,14 @@ class LanDiffPipeline:
             raise ValueError("extend_video takes the clip as exactly one of frames and clip_latent")
         if tokens is not None and clip_tokens is not None:
             raise ValueError("extend_video: tokens already holds every segment; clip_tokens goes with a decode from the prompt")
+        if isinstance(clip_tokens, str):
+            if clip_tokens != "from_frames":
+                raise ValueError(f"extend_video: clip_tokens must be a tensor or 'from_frames', got {clip_tokens!r}")
+            if frames is None or self.theia is None:
+                raise ValueError("extend_video(clip_tokens='from_frames') needs frames= and a pipeline built with theia=")
+            t0 = time.perf_counter()
+            clip_tokens = self.tokenize_frames(continuation_window(frames, self.cfg))
+            self._t("theia", t0)
         if clip_latent is None:
             window = continuation_window(frames, self.cfg)
             if self.encoder is None:
@@ -381,6 +393,18 @@ class LanDiffPipeline:
                 outs.append(r)
         out = torch.cat(outs, dim=0)
         return (out, torch.cat(vids, dim=1)) if want_float else out
+
+
+    @torch.no_grad()
+    def tokenize_frames(self, frames: torch.Tensor) -> torch.Tensor:
+        """uint8 frames [F, H, W, 3] -> the clip's semantic token ids int64 [num_latent_tokens]: T = tok.temporal equally spaced
+        frames (theia.select_frames) through the Theia extractor and the tokenizer encoder."""
+        from .theia import select_frames
+        if self.theia is None:
+            raise ValueError("tokenize_frames needs a pipeline built with theia= (landiff_amd.theia.TheiaExtractor)")
+        if self.theia.encoder is None:
+            raise ValueError("tokenize_frames: the Theia extractor has no tokenizer encoder attached")
+        return self.theia.tokenize_video(select_frames(frames.to(self.dev), self.cfg.tok.temporal))
 
 
 def stream_plan(cfg: PipelineConfig, n_chunks: int, prefix_frames: int):

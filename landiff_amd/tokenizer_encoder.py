@@ -3,9 +3,9 @@
 Mirrors VideoVQ.encode_to_index(features=...) (landiff/tokenizer/models/video_titok_vq.py:172-202): norm_features (:226-231)
 -> TiTokEncoder.forward (landiff/tokenizer/modules/blocks.py:570-656; patch_size 1, 3D RoPE, inside_latent_tokens) with
 VideoEncoderMask (landiff/tokenizer/modules/flex_attention_mask.py:36-190) -> VectorQuantize.forward in eval
-(vector-quantize-pytorch 1.19.2: project_in, first code at minimum Euclidean distance).  The Theia extractor itself
-(theia_extractor.py: a Hugging Face `trust_remote_code` model) is not part of this image and stays outside: the entry point
-takes its feature maps, exactly as the reference's `features=` argument does.
+(vector-quantize-pytorch 1.19.2: project_in, first code at minimum Euclidean distance).  The entry point takes Theia feature
+maps, exactly as the reference's `features=` argument does, or (encode_rows) the channels-last rows that
+landiff_amd/theia.py's extractor writes straight from its last kernel.
 
 HBM layout: one [visual (T*h*w) | latent (I + (T-1)*P)] x width matrix with an fp32 residual stream, as in the decoder.
 
@@ -106,11 +106,19 @@ class TokenizerEncoder:
     def encode(self, features: torch.Tensor) -> torch.Tensor:
         """features [T, C, h, w] (fp32 or bf16, on the device) -> latent tokens [L, token_size] bf16."""
         tc, dev = self.tc, self.dev
-        w, N, H, nv = tc.width, self.N, tc.heads, tc.n_visual
         T, C, gh, gw = features.shape
         assert (T, C, gh, gw) == (tc.temporal, tc.out_channels, tc.grid_h, tc.grid_w), features.shape
-        xin = torch.empty(nv, C, device=dev, dtype=BF)
+        xin = torch.empty(tc.n_visual, C, device=dev, dtype=BF)
         ops.feature_norm_cl(features.contiguous(), self.mean, self.std, xin, T, C, gh * gw)       # norm_features (identity by default) -> bf16, channels-last
+        return self.encode_rows(xin)
+
+    @torch.no_grad()
+    def encode_rows(self, xin: torch.Tensor) -> torch.Tensor:
+        """encode() from its channels-last input rows xin bf16 [T*h*w, C] = feature_norm_cl(features) (what
+        theia.TheiaExtractor.encoder_rows writes) -> latent tokens [L, token_size] bf16."""
+        tc, dev = self.tc, self.dev
+        w, N, H, nv = tc.width, self.N, tc.heads, tc.n_visual
+        assert xin.dtype == BF and tuple(xin.shape) == (nv, tc.out_channels) and xin.is_contiguous(), tuple(xin.shape)
         x0 = torch.empty(N, w, device=dev, dtype=BF)
         ops.gemm(xin, self.patch_w, out=x0[:nv], bias=self.patch_b)                               # 1x1 patch embedding
         x0[nv:] = self.latent
@@ -151,3 +159,8 @@ class TokenizerEncoder:
     def encode_to_index(self, features: torch.Tensor) -> torch.Tensor:
         """Theia feature maps [T, C, h, w] -> semantic token ids int64 [L] (VideoVQ.encode_to_index, batch 1)."""
         return self.nearest_code(self.encode(features))
+
+    @torch.no_grad()
+    def encode_rows_to_index(self, xin: torch.Tensor) -> torch.Tensor:
+        """encode_to_index from the channels-last input rows (encode_rows)."""
+        return self.nearest_code(self.encode_rows(xin))

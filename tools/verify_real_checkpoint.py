@@ -21,7 +21,12 @@ this script
      be observed in the product's arithmetic;
   D. checks the VQ codebook: shapes of `_codebook.embed` / `project_out`, whether every code is its own nearest code under the
      Euclidean rule the product uses, and whether the rows are unit-norm (a cosine-similarity codebook would need another rule).
-Exit status 1 when a key or shape does not match (A); B-D print verdicts for a human.  `--config config0|tiny` checks a synthetic
+  E. (--theia FILE_OR_DIR, or $LANDIFF_THEIA_CKPT / a local HF-cache snapshot when the flag is given without a value) audits the
+     Theia checkpoint against the transformers 4.x ViTModel layout landiff_amd.theia reads (backbone.model.embeddings.*,
+     encoder.layer.{i}.attention.attention.{query,key,value}, .attention.output.dense, .intermediate.dense, .output.dense,
+     .layernorm_{before,after}, layernorm) at DeiT-base shapes, lists the key groups it ignores (translator.*, pooler.*), and
+     loads it through load_theia_state.
+Exit status 1 when a key or shape does not match (A, E); B-D print verdicts for a human.  `--config config0|tiny` checks a synthetic
 tree written by landiff_amd.weights.save_checkpoint_tree (what tests/test_cabi_and_host.py does).
 """
 from __future__ import annotations
@@ -128,10 +133,53 @@ def vq_check(sd: dict, tc):
           + ("  <- unit-norm rows: a cosine-similarity codebook? the product searches by Euclidean distance" if (norms - 1).abs().max() < 1e-3 else ""))
 
 
+def theia_spec(width: int = 768, layers: int = 12, pos: int = 197):
+    """(key, shape, None) of the DeiT-base backbone below backbone.model. (landiff_amd.theia.theia_keys)."""
+    from landiff_amd.theia import theia_keys
+    fixed = {"embeddings.cls_token": (1, 1, width), "embeddings.position_embeddings": (1, pos, width),
+             "embeddings.patch_embeddings.projection.weight": (width, 3, 16, 16)}
+    out = []
+    for k in theia_keys(layers):
+        if k in fixed:
+            sh = fixed[k]
+        elif k.endswith("intermediate.dense.weight"):
+            sh = (4 * width, width)
+        elif k.endswith("intermediate.dense.bias"):
+            sh = (4 * width,)
+        elif k.endswith(".output.dense.weight") and ".attention." not in k:
+            sh = (width, 4 * width)
+        elif k.endswith(".weight") and "layernorm" not in k:
+            sh = (width, width)
+        else:
+            sh = (width,)
+        out.append(("backbone.model." + k, sh, None))
+    return out
+
+
+def theia_check(path: str | None) -> bool:
+    from safetensors.torch import load_file
+    from landiff_amd.theia import load_theia_state, resolve_theia_path, theia_dims
+    f = resolve_theia_path(path)
+    sd = load_file(f)
+    groups = {}
+    for k in sd:
+        if not k.startswith("backbone.model.") or k.startswith("backbone.model.pooler."):
+            g = ".".join(k.split(".")[:3 if k.startswith("backbone.") else 1])
+            groups[g] = groups.get(g, 0) + 1
+    print(f"[E] Theia {f}: {len(sd)} tensors; ignored groups {dict(sorted(groups.items()))}")
+    ok = audit("Theia backbone (DeiT-base, transformers 4.x ViTModel names)", {k: v for k, v in sd.items()}, theia_spec())
+    if ok:
+        print(f"      load_theia_state: {theia_dims(load_theia_state(f))}")
+    return ok
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--ckpt", required=True, help="the checkpoint root (ckpts/LanDiff of the reference layout)")
     ap.add_argument("--config", default="full", choices=["full", "config0", "tiny"])
+    ap.add_argument("--theia", nargs="?", const="", default=None,
+                    help="also audit the Theia checkpoint (a model.safetensors or its directory; without a value: "
+                         "$LANDIFF_THEIA_CKPT, then a local Hugging Face cache snapshot)")
     args = ap.parse_args()
     from landiff_amd.config import PipelineConfig
     from landiff_amd.weights import (CKPT_FILES, dit_spec, llm_spec, load_diffusion_states, load_llm_state, tokenizer_spec, upsampler_spec, vae_spec)
@@ -153,6 +201,8 @@ def main():
     verdicts = [qkv_layout(st["dit_main"], cfg.dit, i) for i in sorted({0, cfg.dit.layers_main // 2, cfg.dit.layers_main - 1})]
     ln_epsilon(st["dit_main"], cfg.dit)
     vq_check(st["tok"], cfg.tok)
+    if args.theia is not None:
+        ok &= theia_check(args.theia or None)
     print("SUMMARY: keys/shapes " + ("OK" if ok else "MISMATCH") + "; qkv layout " +
           ("undecidable" if all(v is None for v in verdicts) else "confirmed" if all(v in (True, None) for v in verdicts) else "CONTRADICTED"))
     return 0 if ok else 1
