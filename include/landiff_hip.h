@@ -29,8 +29,8 @@ extern "C" {
  * ld_groupnorm_stats_from_conv were added.  8: ld_gemm_qkv_heads_mxfp8 was added.
  * 9: ld_attn_fwd_bf16_exact was added.  10: ld_attn_last_fallbacks was added.  11: ld_vae_enc_place_input,
  * ld_vae_enc_downsample and ld_vae_posterior were added.  12: ld_vit_patch_rows, ld_vit_embed and ld_vit_tail were added,
- * ld_qkv_split gained mode 2. */
-#define LD_ABI_VERSION 12
+ * ld_qkv_split gained mode 2.  13: ld_gemm_route was added. */
+#define LD_ABI_VERSION 13
 
 int ld_version(void);
 const char* ld_last_error(void);
@@ -84,6 +84,20 @@ int ld_gemm_bf16(const void* A, int64_t lda, const void* W, void* out, int64_t l
 int ld_gemm_qkv_heads(const void* A, int64_t lda, const void* W, const void* bias, int64_t M, int64_t K,
                       void* Q, void* Kh, void* Vt, int64_t B, int64_t Ntok, int64_t heads, int64_t Npad,
                       const void* q_w, const void* q_b, const void* k_w, const void* k_b, float eps, void* stream);
+
+/* Which kernel ld_gemm_bf16 runs for a shape and epilogue, without launching anything (no GPU needed; the pointers of `epi` are
+ * only tested for null).  Returns the route code of ld_conv_route below -- 0 = 128x128 two-stage, 1 = 256x256 two-stage,
+ * 2 = 256x256 8-phase on every tile -- or one of the two split forms (the last, partial round of 256x256 tiles on 256 CUs run by a
+ * second launch):
+ *   6 = 8-phase on the whole rounds, the remaining tiles as 256x128 half tiles (remainder at most half a round, K <= 2048),
+ *   7 = 8-phase on the top tile rows, the rows below as 128x128 tiles (remainder at most 60 % of a round, not the case above);
+ * negative = the shape is refused.  *epilogue_kind (may be null) = the epilogue the kernels are specialised for:
+ * 0 = bias (act none), 1 = bias + GELU-tanh, 2 = gate + bf16 residual (+ add2; rows_per_batch >= 512), 3 = generic (everything
+ * else: other activations, mul, fp32 residual or output, N or a leading dimension not a multiple of 8).  The fused qkv split
+ * (ld_gemm_qkv_heads, epilogue 5) takes the route of ld_gemm_route(M, 3 * heads * 64, K, ...).  As for convolutions, the routes
+ * give bit-identical outputs: the 8-phase rounds, the half-tile tail and the row tail equal 256-row slices of the same GEMM run on
+ * the 128x128 route, bit for bit (measured at the DiT's shapes, tests/test_gpu_gemm_routes.py).  Host logic only. */
+int ld_gemm_route(int64_t M, int64_t N, int64_t K, int64_t ldo, const ld_epilogue_t* epi, int32_t* epilogue_kind);
 
 /* Channels-last implicit-GEMM convolution, stride 1.
  * in_padded: bf16 [T+kT-1][H+kH-1][W+kW-1][Cin] with the zero spatial border and the causal time

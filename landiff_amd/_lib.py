@@ -44,7 +44,7 @@ class LlmLayer(Structure):
 
 
 _lib = None
-ABI_VERSION = 12         # LD_ABI_VERSION of include/landiff_hip.h that SIGNATURES below were written against
+ABI_VERSION = 13         # LD_ABI_VERSION of include/landiff_hip.h that SIGNATURES below were written against
 
 I64 = c_int64
 I32 = c_int32
@@ -60,6 +60,7 @@ SIGNATURES: dict[str, list] = {
     "ld_conv_cl_bf16_gn": [P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, POINTER(Epilogue), P, P],
     "ld_conv_gn_partials_size": [I64, I64],
     "ld_conv_route": [I64, I64, I64, I64, I64, I64, I64, I64],
+    "ld_gemm_route": [I64, I64, I64, I64, POINTER(Epilogue), POINTER(I32)],
     "ld_calib_mfma_bf16": [P, I64, P, I64, I64, POINTER(c_double), P],
     "ld_calib_stream_read": [P, I64, P, P],
     "ld_attn_fwd_bf16": [P, P, P, P, I64, I64, I64, I64, I64, I64, I64, c_float, P, P, P, P, P],

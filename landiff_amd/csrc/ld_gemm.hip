@@ -2687,9 +2687,10 @@ long conv_input_bytes(const GemmParams& p) {
 constexpr long CONV_8P_MAX_BYTES = 0x7fffffffL;
 constexpr long CONV_MAX_BYTES = 1L << 33;
 
-enum { ROUTE_128_2STAGE = 0, ROUTE_256_2STAGE = 1, ROUTE_256_8PHASE = 2, ROUTE_256_W4R = 3, ROUTE_512_8PHASE = 4, ROUTE_NARROW = 5 };   // (documented at ld_conv_route in landiff_hip.h)
-thread_local int g_last_route = -1;   // what launch() picked last ON THIS HOST THREAD (ld_conv_route's dry run reads it; the
-                                      // pipeline runs launches from a helper thread too)
+enum { ROUTE_128_2STAGE = 0, ROUTE_256_2STAGE = 1, ROUTE_256_8PHASE = 2, ROUTE_256_W4R = 3, ROUTE_512_8PHASE = 4, ROUTE_NARROW = 5,
+       ROUTE_8P_HALF_TAIL = 6, ROUTE_8P_ROW_TAIL = 7 };   // (documented at ld_conv_route and ld_gemm_route in landiff_hip.h)
+thread_local int g_last_route = -1;   // what launch() picked last ON THIS HOST THREAD (the dry runs of ld_conv_route / ld_gemm_route
+                                      // read it; the pipeline runs launches from a helper thread too)
 
 int launch(const GemmParams& p, bool conv, hipStream_t stream, bool dry_run = false) {
   // LD_GEMM_TILE (tuning knob): 1 = 128x128 / 4 waves, 3 = 256x256 / 8 waves (both 2-stage, barrier-drained, 16x16x32 MFMAs
@@ -2783,6 +2784,7 @@ int launch(const GemmParams& p, bool conv, hipStream_t stream, bool dry_run = fa
     a.tile_begin = 0; a.tile_end = (int)(full * ncu);
     b.tile_begin = (int)(full * ncu); b.tile_end = 0;
     const int rc = big(a);
+    g_last_route = ROUTE_8P_HALF_TAIL;      // (main_is_8p and !conv: big() took the 8-phase kernel)
     if (rc || dry_run) return rc;
     return launch_8p_n128(b, stream);
   }
@@ -2794,6 +2796,7 @@ int launch(const GemmParams& p, bool conv, hipStream_t stream, bool dry_run = fa
       a.M = rows_main * 256;
       b.m_begin = rows_main * 256;
       const int rc = big(a);
+      if (g_last_route == ROUTE_256_8PHASE) g_last_route = ROUTE_8P_ROW_TAIL;     // (LD_GEMM_8P=0: stays 1, the two-stage main part)
       if (rc || dry_run) return rc;
       return launch_cfg<128, 128, 2, 2, 2>(b, conv, stream);
     }
@@ -3046,6 +3049,19 @@ LD_API int ld_conv_route(int64_t T, int64_t H, int64_t W, int64_t Cin, int64_t C
   if (ld_conv_narrow_try(nullptr, nullptr, nullptr, nullptr, Cout, T, H, W, Cin, Cout, kT, kH, kW, true, nullptr, true) == 0) return ROUTE_NARROW;
   g_last_route = -1;
   const int rc = launch(p, true, nullptr, /*dry_run=*/true);
+  return rc ? rc : g_last_route;
+}
+
+LD_API int ld_gemm_route(int64_t M, int64_t N, int64_t K, int64_t ldo, const ld_epilogue_t* epi, int32_t* epilogue_kind) {
+  if (M <= 0 || N <= 0 || K <= 0 || K % BK || M >= (1LL << 31) || N >= (1LL << 31) || M * N >= (1LL << 40))
+    return ld_set_error(LD_ERR_INVALID, "ld_gemm_route: bad shape M=%ld N=%ld K=%ld", (long)M, (long)N, (long)K);
+  GemmParams p{};
+  p.M = (int)M; p.N = (int)N; p.K = (int)K; p.ldo = ldo;
+  int rc = fill_epilogue(p, epi);
+  if (rc) return rc;
+  if (epilogue_kind) *epilogue_kind = pick_epilogue(p);
+  g_last_route = -1;
+  rc = launch(p, false, nullptr, /*dry_run=*/true);
   return rc ? rc : g_last_route;
 }
 

@@ -103,6 +103,60 @@ def test_conv_routes_of_a_49_frame_encode():
     assert [routes[f"down.1.block.{j}.conv2"] for j in range(3)] == [2, 2, 2]
 
 
+def _gemm_route(lib, M, N, K, ldo=None, **epi):
+    """(route, epilogue kind) of ld_gemm_bf16 for a shape; epilogue pointers are placeholders (only tested for null)."""
+    from landiff_amd import _lib
+    e = _lib.Epilogue()
+    for k, v in epi.items():
+        setattr(e, k, v)
+    kind = ctypes.c_int32(-1)
+    return lib.ld_gemm_route(M, N, K, N if ldo is None else ldo, ctypes.byref(e), ctypes.byref(kind)), kind.value
+
+
+def test_gemm_route_table():
+    """ld_gemm_route is ld_gemm_bf16's launcher run dry: the four DiT GEMMs land on the routes their tuning was measured on, and
+    every decision boundary of launch() sits where its comments say.  Routes: 0 = 128x128 two-stage, 2 = 256x256 8-phase,
+    6 = 8-phase + half-tile tail, 7 = 8-phase + 128x128 row tail.  Epilogues: 0 bias, 1 bias + GELU-tanh, 2 gate, 3 generic."""
+    from landiff_amd import _lib
+    lib = _lib.load()
+    p, M, d, rows, text = 16, 2 * 17776, 1920, 17776, 226           # (p: a non-null placeholder pointer)
+    gate = dict(gate=p, rows_per_batch=rows, text_len=text, resid=p, ldr=d)
+    # the DiT block at 480 x 720 x 49 frames (B = 2): 139 tile rows; the fused qkv split runs on the route of its N = 3 d
+    assert _gemm_route(lib, M, 3 * d, d, bias=p) == (6, 0)                   # 3197 tiles = 12 rounds + 125
+    assert _gemm_route(lib, M, d, d, bias=p, **gate) == (6, 2)               # dense: 4 rounds + 88
+    assert _gemm_route(lib, M, 4 * d, d, bias=p, act=1) == (6, 1)           # h4: 16 rounds + 74
+    assert _gemm_route(lib, M, d, 4 * d, bias=p, add2=p, ldadd=d, **gate) == (7, 2)     # h1: K = 7680 > 2048
+    # 256x256 tiles from 512 of them on, and only for K >= 1024 (N = 256: one tile column)
+    assert _gemm_route(lib, 511 * 256, 256, 1024)[0] == 0 and _gemm_route(lib, 512 * 256, 256, 1024)[0] == 2
+    assert _gemm_route(lib, 512 * 256, 256, 960)[0] == 0 and _gemm_route(lib, 512 * 256, 256, 1024)[0] == 2
+    # half a round left over: half tiles up to K = 2048, the row tail beyond
+    assert _gemm_route(lib, 640 * 256, 256, 2048)[0] == 6 and _gemm_route(lib, 640 * 256, 256, 2112)[0] == 7
+    # the remainder: none -> 8-phase alone; <= 128 tiles -> half tiles; <= 60 % of 256 (153.6) -> row tail; beyond -> no split
+    routes = {rem: _gemm_route(lib, (512 + rem) * 256, 256, 1920)[0] for rem in (0, 1, 128, 129, 153, 154, 255)}
+    assert routes == {0: 2, 1: 6, 128: 6, 129: 7, 153: 7, 154: 2, 255: 2}, routes
+    # a split needs two whole rounds (one round and a bit is under 512 tiles: the 128x128 route anyway)
+    assert _gemm_route(lib, (256 + 64) * 256, 256, 1920)[0] == 0 and _gemm_route(lib, (512 + 64) * 256, 256, 1920)[0] == 6
+    # the route depends on (M, N, K) alone; the epilogue only picks the specialisation
+    for epi in (dict(), dict(act=2), dict(mul=p, ldmul=d), dict(resid=p, ldr=d, resid_f32=1, out_f32=1)):
+        assert _gemm_route(lib, M, d, 4 * d, **epi)[0] == 7
+    # EPI_GATE needs a batch of >= 512 rows (one boundary per wave tile), N % 8 == 0, a bf16 residual and no mul
+    assert _gemm_route(lib, M, d, d, **dict(gate, rows_per_batch=512))[1] == 2
+    assert _gemm_route(lib, M, d, d, **dict(gate, rows_per_batch=511))[1] == 3
+    assert _gemm_route(lib, M, d - 4, d, **dict(gate, ldr=d - 4))[1] == 3
+    assert _gemm_route(lib, M, d, d, ldo=d + 4, **gate)[1] == 3
+    assert _gemm_route(lib, M, d, d, **dict(gate, resid_f32=1))[1] == 3
+    assert _gemm_route(lib, M, d, d, mul=p, ldmul=d, **gate)[1] == 3
+    assert _gemm_route(lib, M, d, d, out_f32=1, **gate)[1] == 3
+    # the other specialisations and their fall-backs
+    assert _gemm_route(lib, M, d, d)[1] == 0 and _gemm_route(lib, M, d, d, act=1)[1] == 1
+    assert [_gemm_route(lib, M, d, d, act=a)[1] for a in (2, 3, 4)] == [3, 3, 3]
+    assert _gemm_route(lib, M, d, d, act=1, mul=p, ldmul=d)[1] == 3 and _gemm_route(lib, M, d, d, resid=p, ldr=d)[1] == 3
+    # refused shapes: negative, nothing written
+    for bad in ((0, 64, 64), (64, 64, 96), (64, 0, 64), (1 << 31, 64, 64)):
+        rc, kind = _gemm_route(lib, *bad)
+        assert rc < 0 and kind == -1 and b"bad shape" in lib.ld_last_error(), bad
+
+
 def test_decode_step_forms_validate_without_gpu():
     """The alternative forms of a decode step's blocks (one persistent launch / dependent launches on two streams) reject null
     pointers and shapes outside their register forms before any HIP call: LD_ERR_INVALID (-1) / LD_ERR_UNSUPPORTED (-3).

@@ -155,13 +155,17 @@ def test_conv_groupnorm_partials(cuda, T, H, W, Cin, Cout, route, resid):
         ops.conv_cl(xp, wcl[:12].contiguous(), T, H, W, gn_partials=True, bias=bias[:12].contiguous())
 
 
-@pytest.mark.parametrize("B,N,H,K", [(2, 456, 3, 128), (1, 1000, 2, 192), (2, 4440, 5, 320)])
+@pytest.mark.parametrize("B,N,H,K", [(2, 456, 3, 128), (1, 1000, 2, 192), (2, 4440, 5, 320), (2, 17776, 30, 1920)])
 def test_gemm_qkv_heads_fused_split(cuda, B, N, H, K):
     """ld_gemm_qkv_heads (qkv Linear with QK-LayerNorm / head split / V transpose in its epilogue) against the two-launch
     path it replaces (ld_gemm_bf16 + ld_qkv_split) and against a torch fp32 restatement of dit_video_concat.py:636-653.
     Shapes: token counts that are not multiples of the 128-row wave tile (batch boundary inside a tile), a column count
-    that leaves dead waves in the last tile column, and one large enough for the 256x256 kernel + 128x128 tail launch."""
-    from landiff_amd import ops
+    that leaves dead waves in the last tile column -- all three on the 128x128 route (fewer than 512 256x256 tiles) -- and the
+    DiT's own (480 x 720 x 49 frames, B = 2): the 8-phase kernel on 12 whole rounds + 125 half tiles (route 6 of ld_gemm_route)."""
+    import ctypes
+    from landiff_amd import _lib, ops
+    route = 6 if N == 17776 else 0
+    assert _lib.load().ld_gemm_route(B * N, 3 * H * 64, K, 3 * H * 64, None, ctypes.POINTER(ctypes.c_int32)()) == route
     g = torch.Generator(device="cpu").manual_seed(B * 1000 + N)
     Npad = (N + 127) // 128 * 128
     a = torch.randn(B * N, K, generator=g).to(cuda, torch.bfloat16)
