@@ -139,14 +139,14 @@ __global__ __launch_bounds__(256, 1) void ld_conv_narrow_kernel(NarrowParams p) 
 // Called by ld_conv_cl_bf16 (ld_gemm.hip).  Returns 1 when the shape is not this kernel's (the caller takes the GEMM route), 0 after
 // a launch, negative on error.  LD_CONV_NARROW=0 disables the route (A/B timing).
 int ld_conv_narrow_try(const void* in_padded, const void* w, const void* bias, void* out, long ldo, long T, long H, long W, long Cin,
-                       long Cout, long kT, long kH, long kW, bool plain_bias_epilogue, hipStream_t stream, bool dry_run) {
+                       long Cout, long kT, long kH, long kW, bool plain_bias_epilogue, hipStream_t stream, bool query_only) {
   static int k_on = LD_KNOB_UNSET;
   if (ld_knob("LD_CONV_NARROW", 1, &k_on) == 0) return 1;
   if (!(kT == 3 && kH == 3 && kW == 3 && Cin == CN_C && Cout >= 1 && Cout <= 4 && H % CN_TH == 0 && W % CN_TW == 0 && plain_bias_epilogue))
     return 1;
   const long bytes = (T + 2) * (H + 2) * (W + 2) * CN_C * 2;
   if (bytes >= 0x7fffffffL || ldo < Cout) return 1;
-  if (dry_run) return 0;
+  if (query_only) return 0;
   NarrowParams p{(const bf16_t*)in_padded, (const bf16_t*)w, (const bf16_t*)bias, (bf16_t*)out, (int)T, (int)H, (int)W, (int)Cout, ldo, (int)bytes};
   static thread_local LdSmemCache cache{};
   if (int rc = ld_ensure_dyn_smem((const void*)ld_conv_narrow_kernel, CN_SMEM, &cache)) return rc;

@@ -630,7 +630,7 @@ __global__ __launch_bounds__(64) void ld_gn_stats_reduce_kernel(const double* pa
   if (lane == 0) { stats[(long)fg * 2] = s; stats[(long)fg * 2 + 1] = ss; }
 }
 
-// The same statistics from what the producing convolution's epilogue left behind (ld_conv_cl_bf16_gn, ld_gemm.hip): fp32
+// The same statistics from what the producing convolution's epilogue left behind (ld_conv_cl_bf16_gn, ld_gemm.hip; the sums: gemm_epilogue_core in ld_gemm.h): fp32
 // (sum, sum of squares) of every 64-row x 4-channel patch, part [U][C / 4][2].  Workgroup b folds units [b * upb, (b + 1) * upb)
 // into double partials [nblk][G][2] -- thread = (row lane, quad), coalesced rows of C / 4 pairs, row lanes and quads summed in
 // index order -- and ld_gn_stats_reduce_kernel finishes as above.  11 MB instead of the 708 MB activation at 8 x 480 x 720 x 128.

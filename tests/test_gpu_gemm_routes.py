@@ -1,6 +1,6 @@
 """ld_gemm_bf16 on every shipped route x every epilogue, element by element.
 
-launch() (ld_gemm.hip) sends a linear GEMM to one of four routes by (M, N, K): 0 = 128x128 two-stage, 2 = 256x256 8-phase,
+plan() (ld_gemm.hip) sends a linear GEMM to one of four routes by (M, N, K): 0 = 128x128 two-stage, 2 = 256x256 8-phase,
 6 = 8-phase on the whole rounds + 256x128 half-tile tail, 7 = 8-phase on the top tile rows + 128x128 row tail (m_begin).  The DiT's
 four GEMMs all run a split form (6 or 7).  Every case first asserts its route and epilogue kind through ld_gemm_route, so a retune
 that moves a shape elsewhere fails here instead of losing the coverage.

@@ -1,5 +1,5 @@
 #!/bin/bash
-# builds landiff_amd/variants/lib_<name>.so = the library with extra -D flags on ld_gemm.hip (compile-time experiments; tools only)
+# builds landiff_amd/variants/lib_<name>.so = the library with extra -D flags on one file, e.g. ld_gemm_8p.hip (compile-time experiments; tools only)
 # usage: tools/build_variant.sh <name> <file.hip> -DFLAG ...
 set -e
 name=$1; file=$2; shift 2

@@ -16,8 +16,8 @@ if len(sys.argv) > 1 and sys.argv[1] == "build":
     os.makedirs(os.path.dirname(LIB), exist_ok=True)
     csrc = os.path.join(ROOT, "landiff_amd", "csrc")
     subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-unused-result",
-                    "-DLD_GEMM_TRACE", "-c", "ld_gemm.hip", "-o", "/tmp/gemm_trace.o"], check=True, cwd=csrc)
-    objs = [os.path.join(csrc, "obj", f) for f in os.listdir(os.path.join(csrc, "obj")) if f.endswith(".o") and f != "ld_gemm.o"]
+                    "-DLD_GEMM_TRACE", "-c", "ld_gemm_8p.hip", "-o", "/tmp/gemm_trace.o"], check=True, cwd=csrc)
+    objs = [os.path.join(csrc, "obj", f) for f in os.listdir(os.path.join(csrc, "obj")) if f.endswith(".o") and f != "ld_gemm_8p.o"]
     subprocess.run(["hipcc", "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB, "/tmp/gemm_trace.o"] + objs, check=True)
     print("built", LIB)
     sys.exit(0)
