@@ -30,7 +30,7 @@ extern "C" {
  * 9: ld_attn_fwd_bf16_exact was added.  10: ld_attn_last_fallbacks was added.  11: ld_vae_enc_place_input,
  * ld_vae_enc_downsample and ld_vae_posterior were added.  12: ld_vit_patch_rows, ld_vit_embed and ld_vit_tail were added,
  * ld_qkv_split gained mode 2.  13: ld_gemm_route was added. */
-#define LD_ABI_VERSION 13
+#define LD_ABI_VERSION 14
 
 int ld_version(void);
 const char* ld_last_error(void);
@@ -268,6 +268,20 @@ int ld_gemv(const void* x, int64_t ldx, int32_t x_f32, const void* W, const void
             int64_t B, int64_t N, int64_t K, int32_t in_act, int32_t act, const float* norm_w, float norm_eps,
             void* stream);
 
+/* ld_gemv for P = B / 2 pairs of activation rows, 1 <= P <= LD_LLM_MAX_PAIRS: the P (cond, uncond) pairs of P samples of one
+ * prompt decoded side by side (Semantic1DLM.sample once per seed, lm_model.py:417-508, through the cached blocks of
+ * transformer_blocks.py:128-236).  Same arguments as ld_gemv.  Rows (2p, 2p+1) of the output are BIT-IDENTICAL to ld_gemv with
+ * B = 2 on those two rows, in every form (fused RMSNorm, gated GELU, residual -- also in place, out == resid --, fp32 head).
+ * The bf16 forms the decode uses (K <= 4096, or K <= 12288 without W2) are one launch that reads every weight row from HBM once:
+ * the register-resident kernel of the B = 2 route with the same chunk ownership per K and all 2P activation rows in registers.
+ * Other forms (fp32 weights: the 17 MB head; fp32 x; in_act; longer K) run the B = 2 route once per pair.
+ * LD_ERR_INVALID: odd B, null pointers, K % 8; LD_ERR_UNSUPPORTED: P > LD_LLM_MAX_PAIRS -- nothing is launched. */
+#define LD_LLM_MAX_PAIRS 4
+int ld_gemv_pairs(const void* x, int64_t ldx, int32_t x_f32, const void* W, const void* W2, int32_t w_f32,
+                  const void* bias, const void* resid, int64_t ldr, void* out, int64_t ldo, int32_t out_f32,
+                  int64_t B, int64_t N, int64_t K, int32_t in_act, int32_t act, const float* norm_w, float norm_eps,
+                  void* stream);
+
 /* RMSNorm (transformer_blocks.py:22-40): bf16 rows [rows][D], fp32 weight, fp32 math, bf16 out. */
 int ld_rmsnorm_bf16(const void* x, const float* w, void* out, int64_t rows, int64_t D, float eps, void* stream);
 
@@ -316,6 +330,21 @@ int ld_llm_decode_forward(const ld_llm_layer* layers, int64_t n_layers, const fl
                           const float* cos_t, const float* sin_t, const float* lnf_w, const float* lnf_b, float* lnf_out,
                           const float* head_w, float* logits, int64_t B, int64_t hidden, int64_t heads, int64_t mlp,
                           int64_t vocab, int64_t Lmax, int64_t nsplit, float rms_eps, float ln_eps, void* stream);
+
+/* ld_llm_decode_forward for P = B / 2 samples of ONE prompt decoded side by side (same text, same prefix, so one shared position
+ * and forced-token schedule; lm_model.py:417-508 per sample over transformer_blocks.py:128-236): B = 2P rows, pair p = rows
+ * (2p, 2p+1) of x / qkv / att / gate / lnf_out / logits and of every layer's k_cache / v_cache [B][Lmax][heads][128]; token [P]
+ * (emb_table == NULL: x already holds the rows, written by ld_llm_sample_advance_pairs); pos: the position word (word 0 of the
+ * per-sample position array).  The GEMVs go through ld_gemv_pairs (each weight matrix streamed once for all pairs), attention
+ * through the key-split kernel over (B * heads, split): pair p gets exactly the bits ld_llm_decode_forward gives a B = 2 caller
+ * with the same Lmax and nsplit -- nsplit MUST be the B = 2 caller's value (the split rule is part of the bits); attn_ws:
+ * B*heads*(nsplit*130 + 1) words, the last B*heads zero.  LD_ERR_INVALID: odd B, null pointers, head_dim != 128;
+ * LD_ERR_UNSUPPORTED: P > LD_LLM_MAX_PAIRS -- checked before anything is launched. */
+int ld_llm_decode_forward_pairs(const ld_llm_layer* layers, int64_t n_layers, const float* emb_table, const int64_t* token,
+                                const int32_t* pos, int32_t pos_value, void* x, void* qkv, void* att, void* gate, float* attn_ws,
+                                const float* cos_t, const float* sin_t, const float* lnf_w, const float* lnf_b, float* lnf_out,
+                                const float* head_w, float* logits, int64_t B, int64_t hidden, int64_t heads, int64_t mlp,
+                                int64_t vocab, int64_t Lmax, int64_t nsplit, float rms_eps, float ln_eps, void* stream);
 
 /* ---- Entry points of the VARIANTS build only (landiff_amd/variants/liblandiff_hip_variants.so, built by
  * `LD_BUILD_VARIANTS=1 landiff_amd/csrc/build.sh` with -DLD_VARIANTS): two other forms of the decode step that were built, are
@@ -384,6 +413,17 @@ int ld_llm_sample_advance(const float* logits, float* probs, float* cfg_logits, 
                           int32_t top_k, float top_p, const float* noise, const int32_t* forced, int64_t* token,
                           int64_t* out_tokens, int32_t* out_count, int64_t* sampled, const float* emb_table, void* x,
                           int64_t B, int64_t D, void* stream);
+
+/* ld_llm_sample_advance for P samples (1 <= P <= LD_LLM_MAX_PAIRS) in one launch of P workgroups (lm_model.py:417-508 per
+ * sample): workgroup p does what ld_llm_sample_advance does on logits rows (2p, 2p+1) of [2P][V] with noise / probs / cfg_logits
+ * row p of [P][V], pos[p], token[p], out_tokens[p * out_stride ..], out_count[p], sampled[p] and x rows (2p, 2p+1) of [2P][D].
+ * forced / allowed are the one shared schedule.  pos holds one word per sample, all equal: each workgroup reads and advances
+ * its own, so no workgroup's increment races another's read (the forward pass reads word 0). */
+int ld_llm_sample_advance_pairs(const float* logits, float* probs, float* cfg_logits, int64_t V, int32_t guided, float scale,
+                                float temperature, int32_t* pos, const int32_t* allowed, int64_t allowed_stride,
+                                int32_t top_k, float top_p, const float* noise, const int32_t* forced, int64_t* token,
+                                int64_t* out_tokens, int64_t out_stride, int32_t* out_count, int64_t* sampled,
+                                const float* emb_table, void* x, int64_t P, int64_t D, void* stream);
 
 /* After torch.multinomial: forced-token override (forced[*pos + 1] >= 0), record sampled visual tokens, ++*pos
  * (the elif chain of lm_model.py:455-508). */

@@ -22,6 +22,9 @@ def parse_args(argv=None):
     parser.add_argument("--cfg", type=float, default=7.5, help="CFG scale for the video generation.")
     parser.add_argument("--motion_score", type=float, default=0.1, help="Motion score for the video generation.")
     parser.add_argument("--seed", type=int, default=42, help="Random seed for video generation.")
+    parser.add_argument("--num_samples", type=int, default=1,
+                        help="Candidates of the prompt (1-4), seeds --seed .. --seed + N - 1, their tokens from ONE batched AR decode; "
+                             "N > 1 writes <save_file_name>_<i>.mp4 / _<i>.npy, each what --seed (seed + i) alone produces.")
     parser.add_argument("--extend_video", type=str, default=None,
                         help="Continue this clip instead of generating from scratch: a uint8 [F, H, W, 3] .npy (the format "
                              "save_video_tensor falls back to) or an mp4 when imageio can read it.")
@@ -38,7 +41,14 @@ def parse_args(argv=None):
     parser.add_argument("--first_frame", type=str, default=None,
                         help="Image-guided generation (use_gt_first_frame): a uint8 [H, W, 3] .npy or an image imageio can "
                              "read, tokenized by the Theia extractor; its I-frame tokens start the AR decode.")
-    return parser.parse_args(argv)
+    args = parser.parse_args(argv)
+    if not 1 <= args.num_samples <= 4:
+        parser.error("--num_samples must be between 1 and 4")
+    if args.num_samples > 1 and args.extend_video:
+        parser.error("--num_samples applies to generation from a prompt, not to --extend_video")
+    if args.num_samples > 1 and not all(args.seed + i for i in range(args.num_samples)):
+        parser.error("--num_samples needs non-zero seeds (--seed .. --seed + N - 1)")
+    return args
 
 
 def load_image(path: str) -> torch.Tensor:
@@ -100,6 +110,41 @@ def llm_infer(args):
     del llm
     torch.cuda.empty_cache()
     return tokens.cuda()
+
+
+def sample_names(args) -> list:
+    """(seed, file stem) per candidate: --num_samples 1 is the plain name, N > 1 numbers them."""
+    if args.num_samples == 1:
+        return [(args.seed, args.save_file_name)]
+    return [(args.seed + i, f"{args.save_file_name}_{i}") for i in range(args.num_samples)]
+
+
+def llm_infer_samples(args):
+    """--num_samples N > 1: llm_infer for seeds seed .. seed + N - 1 from one batched decode -> tokens [N, n_visual] (cuda)."""
+    llm_model_cfg = build_llm()
+    first = first_frame_tokens(args) if args.first_frame else None
+    llm = ArModelInferWrapper(args.llm_ckpt, llm_model_cfg, max_samples=args.num_samples)
+    names = sample_names(args)
+    task = CodeTask(save_file_name=f"{args.save_file_name}.npy", prompt=args.prompt, seed=args.seed,
+                    sample_cfg=ARSampleCfg(temperature=1.0, cfg=args.cfg, motion_score=args.motion_score,
+                                           num_frames=llm_model_cfg.segment_length, use_gt_first_frame=first is not None),
+                    first_frame_tokens=first)
+    tokens = llm(task, seeds=[s for s, _ in names]).result
+    for row, (_, stem) in zip(tokens, names):
+        path = Path(f"{stem}.npy")
+        path.parent.mkdir(parents=True, exist_ok=True)
+        np.save(path, row.numpy())
+    del llm
+    torch.cuda.empty_cache()
+    return tokens.cuda()
+
+
+def infer_diffusion_samples(args, tokens):
+    model = CogModelInferWrapper(ckpt_path=args.diffusion_ckpt)
+    for row, (seed, stem) in zip(tokens, sample_names(args)):
+        task = model(VideoTask(save_file_name=f"{stem}.mp4", prompt=args.prompt, seed=seed, fps=8, semantic_token=row))
+        save_video_tensor(task.result, task.save_file_name, fps=task.fps)
+        print(f"save video to {task.save_file_name}")
 
 
 def infer_diffusion(args, semantic_token):
@@ -187,6 +232,9 @@ def main():
     torch.cuda.set_device(local_rank)
     if args.extend_video:
         extend_diffusion(args)
+        return
+    if args.num_samples > 1:
+        infer_diffusion_samples(args, llm_infer_samples(args))
         return
     infer_diffusion(args, llm_infer(args))
 

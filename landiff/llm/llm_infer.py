@@ -70,7 +70,7 @@ class ArModelInferWrapper(torch.nn.Module):
     text_encoder: optional callable prompts -> list of [n_i, text_dim] states replacing the FLAN-T5-XXL run (pre-computed
     embeddings, as `load_weights=False` does in the reference's text encoder, text_encoder.py:126-131)."""
 
-    def __init__(self, ckpt_path: str, model_cfg: LLMConfig, device="cuda", text_encoder=None):
+    def __init__(self, ckpt_path: str, model_cfg: LLMConfig, device="cuda", text_encoder=None, max_samples: int = 1):
         super().__init__()
         assert Path(ckpt_path).exists(), f"ckpt_path: {ckpt_path} does not exist"
         assert Path(ckpt_path).suffix == ".safetensors", f"ckpt_path: {ckpt_path} is not a safetensors file"
@@ -84,10 +84,12 @@ class ArModelInferWrapper(torch.nn.Module):
         assert not missing, f"load_state_dict(strict=True): missing keys {missing[:5]}{'...' if len(missing) > 5 else ''}"
         bad = [k for k in want if tuple(sd[k].shape) != want[k]]
         assert not bad, f"checkpoint / model_cfg shape mismatch at {bad[:3]}: {[tuple(sd[k].shape) for k in bad[:3]]} vs {[want[k] for k in bad[:3]]}"
-        self.runner = LLMRunner(sd, model_cfg, self.device_, max_text=model_cfg.max_cond_tokens)
+        self.runner = LLMRunner(sd, model_cfg, self.device_, max_text=model_cfg.max_cond_tokens, max_samples=max_samples)
 
     @torch.no_grad()
-    def forward(self, code_task: CodeTask) -> CodeTask:
+    def forward(self, code_task: CodeTask, seeds=None) -> CodeTask:
+        """seeds (optional, non-zero ints, at most the wrapper's max_samples): that many samples of the prompt from one batched
+        decode (LLMRunner.sample_many) -- .result is then LongTensor [len(seeds), n_visual], row i what seed seeds[i] alone gives."""
         sc, c = code_task.sample_cfg, self.config
         first = None
         if sc.use_gt_first_frame:
@@ -110,6 +112,14 @@ class ArModelInferWrapper(torch.nn.Module):
             # is present, so the config default is not consulted, and no null embedding is configured)
             raise ValueError("Condition key motion_score not found in data, and a default is not given, and null default is not set.")
         set_seed_for_single_process(code_task.seed)
+        if seeds is not None:
+            if fed is not None:
+                raise ValueError("teacher_forcing decodes one token stream: no seeds")
+            tokens = self.runner.sample_many(text, seeds, motion_score=sc.motion_score, num_frames=sc.num_frames,
+                                             guidance_scale=sc.cfg, temperature=sc.temperature, top_k=sc.top_k, top_p=sc.top_p,
+                                             first_frame_tokens=first)
+            code_task.result = tokens.cpu()
+            return code_task
         tokens = self.runner.sample(text, motion_score=sc.motion_score,
                                     num_frames=sc.num_frames, guidance_scale=sc.cfg, temperature=sc.temperature,
                                     seed=code_task.seed, top_k=sc.top_k, top_p=sc.top_p, first_frame_tokens=first,

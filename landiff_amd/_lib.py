@@ -44,7 +44,7 @@ class LlmLayer(Structure):
 
 
 _lib = None
-ABI_VERSION = 13         # LD_ABI_VERSION of include/landiff_hip.h that SIGNATURES below were written against
+ABI_VERSION = 14         # LD_ABI_VERSION of include/landiff_hip.h that SIGNATURES below were written against
 
 I64 = c_int64
 I32 = c_int32
@@ -70,6 +70,7 @@ SIGNATURES: dict[str, list] = {
     "ld_reset": [P],
     "ld_attn_queue_poke": [I32, c_uint32, P],
     "ld_gemv": [P, I64, I32, P, P, I32, P, P, I64, P, I64, I32, I64, I64, I64, I32, I32, P, c_float, P],
+    "ld_gemv_pairs": [P, I64, I32, P, P, I32, P, P, I64, P, I64, I32, I64, I64, I64, I32, I32, P, c_float, P],
     "ld_rmsnorm_bf16": [P, P, P, I64, I64, c_float, P],
     "ld_layernorm_bf16_to_f32": [P, I64, P, P, P, I64, I64, c_float, P],
     "ld_llm_rope_append": [P, P, P, P, P, P, P, I64, I64, I64, I64, P],
@@ -86,9 +87,13 @@ SIGNATURES: dict[str, list] = {
     "ld_vq_nearest": [P, I64, P, P, I64, I64, I64, P],
     "ld_llm_decode_forward": [P, I64, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64,
                               c_float, c_float, P],
+    "ld_llm_decode_forward_pairs": [P, I64, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64,
+                                    c_float, c_float, P],
     "ld_llm_logits_to_probs": [P, P, P, I64, I32, c_float, c_float, P, P, I64, I32, c_float, P],
     "ld_llm_decode_advance": [P, P, P, P, P, P, P],
     "ld_llm_sample_advance": [P, P, P, I64, I32, c_float, c_float, P, P, I64, I32, c_float, P, P, P, P, P, P, P, P, I64, I64, P],
+    "ld_llm_sample_advance_pairs": [P, P, P, I64, I32, c_float, c_float, P, P, I64, I32, c_float, P, P, P, P, I64, P, P, P, P, I64, I64,
+                                    P],
     "ld_layernorm": [P, I64, I32, P, P, P, I64, I32, I64, I64, c_float, P, I64, I64, I64, I64, I64, I64, I64, P],
     "ld_qkv_split": [P, P, P, P, I64, I64, I64, I64, I32, P, P, P, P, c_float, P, P, P],
     "ld_groupnorm_stats_blocks": [I64],

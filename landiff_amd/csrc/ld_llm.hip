@@ -719,6 +719,14 @@ __global__ void ld_embed_kernel(const float* table, const long* token, bf16_t* o
   out[i] = f2bf(table[t * D + (i % D)]);
 }
 
+// the same for P samples decoded side by side: rows (2p, 2p+1) take the embedding of token[p]
+__global__ void ld_embed_pairs_kernel(const float* table, const long* token, bf16_t* out, int B, int D) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * D) return;
+  const long t = token[(i / D) >> 1];
+  out[i] = f2bf(table[t * D + (i % D)]);
+}
+
 // logits [2][V] (cond, uncond) or [1][V] -> probs [V]: CFG, /temperature, optional restriction, optional top-k,
 // softmax, optional top-p.  Single block; V <= LD_SAMPLE_MAXV.  (lm_model.py:417-454, utils.py:345-359)
 #define LD_SAMPLE_MAXV 4096
@@ -739,6 +747,7 @@ struct SampleArgs {
   const float* noise;      // [V] Exp(1) draws
   const int* forced; int* pos; long* token; long* out_tokens; int* out_count; long* sampled;
   const float* emb; bf16_t* x; int B, D;
+  long out_stride;         // ld_llm_sample_advance_pairs: out_tokens row stride of workgroup (= sample) blockIdx.x
 };
 template <bool SAMPLE>
 __global__ __launch_bounds__(1024) void ld_logits_to_probs_kernel(const float* logits, float* probs, float* cfg_logits,
@@ -751,6 +760,19 @@ __global__ __launch_bounds__(1024) void ld_logits_to_probs_kernel(const float* l
   __shared__ float ss[LD_SAMPLE_MAXV];     // values in descending order (top-p)
   __shared__ float thr_s;
   const int tid = threadIdx.x, nt = blockDim.x;
+  if constexpr (SAMPLE) {
+    // ld_llm_sample_advance_pairs: workgroup p is sample p -- logits rows (2p, 2p+1), its own noise / probs row, position word,
+    // token, out_tokens row, out_count, sampled slot and x rows (2p, 2p+1); forced / allowed are the shared schedule.  Every
+    // workgroup reads and advances only ITS position word (all hold the same value), so no workgroup's ++ races another's read.
+    if (const long wg = blockIdx.x) {
+      logits += wg * 2 * V; pos_ptr += wg;
+      if (probs) probs += wg * V;
+      if (cfg_logits) cfg_logits += wg * V;
+      sa.noise += wg * V; sa.pos += wg; sa.token += wg; sa.out_tokens += wg * sa.out_stride; sa.out_count += wg;
+      if (sa.sampled) sa.sampled += wg;
+      sa.x += wg * sa.B * sa.D;
+    }
+  }
   const int* al = nullptr;
   int nal = 0;
   if (allowed) {
@@ -912,9 +934,51 @@ int launch_gemv_reg_j(const GemvParams& p, int R, hipStream_t st) {
   return norm ? launch_gemv_reg_r<B, J, false, true>(p, R, st) : launch_gemv_reg_r<B, J, false, false>(p, R, st);
 }
 
+int gemv_mode() {
+  static const int mode = getenv("LD_GEMV_MODE") ? atoi(getenv("LD_GEMV_MODE")) : 0;     // 1 = streaming-loop kernel only
+  return mode;
+}
+
+// J of the register form launch_gemv_b<2> takes for these operands (0: it takes the LDS-staged kernel).  J fixes the bits of a
+// row's dot product (chunk ownership c = j * 256 + tid, the order of a thread's dot2 chain, the RMSNorm partial sums); R and B
+// do not: every (weight row, activation row) has its own accumulator, wave_sum_multi pairs lanes 32, 16, ..., 1 apart for any V.
+int gemv_pair_reg_j(const GemvParams& p) {
+  const int nchunk = p.K >> 3;
+  if (gemv_mode() == 1 || p.w_f32 || p.x_f32 || p.in_act) return 0;
+  if (nchunk <= 256) return 1;
+  if (nchunk <= 512) return 2;
+  if (nchunk <= 1536 && !p.W2) return 6;
+  return 0;
+}
+
+// ld_gemv_pairs, B = 2 P in {4, 6, 8}: ld_gemv_reg_kernel at the B = 2 route's J with all B activation rows in registers (B * J
+// 16-byte chunks per thread; 8 x 11008 bf16 would not fit the LDS) -- a batch of R weight rows is requested once, held in
+// registers and consumed by every pair, so the matrix is streamed from HBM once per call whatever P is.  R: rows per batch, by the
+// register budget of one workgroup per CU (B * J * 4 for x, 2 * R * J * 4 (x2 gated) for two batches of weights, R * B (x2)
+// partial sums).
+template <int B>
+int launch_gemv_pairs_b(const GemvParams& p, int J, hipStream_t st) {
+  const bool gated = p.W2 != nullptr, norm = p.norm_w != nullptr;
+  if (J == 1) {
+    if (gated) return norm ? launch_gemv_reg<B, 4, 1, true, true>(p, st) : launch_gemv_reg<B, 4, 1, true, false>(p, st);
+    return norm ? launch_gemv_reg<B, 4, 1, false, true>(p, st) : launch_gemv_reg<B, 4, 1, false, false>(p, st);
+  }
+  if (J == 2) {
+    if (gated) return norm ? launch_gemv_reg<B, 2, 2, true, true>(p, st) : launch_gemv_reg<B, 2, 2, true, false>(p, st);
+    return norm ? launch_gemv_reg<B, 4, 2, false, true>(p, st) : launch_gemv_reg<B, 4, 2, false, false>(p, st);
+  }
+  constexpr int R6 = B <= 4 ? 2 : 1;
+  if constexpr (B <= 4) { if (norm) return launch_gemv_reg<B, R6, 6, false, true>(p, st); }
+  return launch_gemv_reg<B, R6, 6, false, false>(p, st);     // (B > 4 with the norm: not here, see gemv_pairs_in_one_launch)
+}
+
+// J = 6 with the fused RMSNorm (gains in registers too) does not fit the register file beyond two pairs without spilling: those
+// calls (no decode shape: the K = mlp projection has no norm in front) take the B = 2 route per pair like the non-register forms
+bool gemv_pairs_in_one_launch(const GemvParams& p, int J) { return p.B > 2 && J != 0 && !(J == 6 && p.norm_w && p.B > 4); }
+
 template <int B>
 int launch_gemv_b(const GemvParams& p, hipStream_t st) {
-  static const int mode = getenv("LD_GEMV_MODE") ? atoi(getenv("LD_GEMV_MODE")) : 0;     // 1 = streaming-loop kernel only
+  const int mode = gemv_mode();
   static const int forced_r = getenv("LD_GEMV_R") ? atoi(getenv("LD_GEMV_R")) : 0;
   const int nchunk = p.K >> 3;
   const bool gated = p.W2 != nullptr;
@@ -970,6 +1034,44 @@ LD_API int ld_gemv(const void* x, int64_t ldx, int32_t x_f32, const void* W, con
     case 3: return launch_gemv_b<3>(p, st);
     default: return launch_gemv_b<4>(p, st);
   }
+}
+
+// ld_gemv for P = B / 2 pairs of activation rows (P samples of one prompt decoded side by side): rows (2p, 2p+1) come out with
+// the bits ld_gemv(B = 2) gives for them.  Register forms: one launch, every weight row read once.  Everything else (the fp32
+// head, LD_GEMV_MODE=1, K beyond the register forms): the B = 2 route once per pair.
+LD_API int ld_gemv_pairs(const void* x, int64_t ldx, int32_t x_f32, const void* W, const void* W2, int32_t w_f32,
+                         const void* bias, const void* resid, int64_t ldr, void* out, int64_t ldo, int32_t out_f32,
+                         int64_t B, int64_t N, int64_t K, int32_t in_act, int32_t act, const float* norm_w, float norm_eps,
+                         void* stream) {
+  LD_REQUIRE(x && W && out, "ld_gemv_pairs: null pointer");
+  LD_REQUIRE(B >= 2 && B % 2 == 0, "ld_gemv_pairs: %ld rows are not pairs", (long)B);
+  if (B > 2 * LD_LLM_MAX_PAIRS) return ld_set_error(LD_ERR_UNSUPPORTED, "ld_gemv_pairs: %ld pairs, at most %d", (long)(B / 2), LD_LLM_MAX_PAIRS);
+  LD_REQUIRE(N >= 1 && K >= 8 && K % 8 == 0 && ldx % 8 == 0, "ld_gemv_pairs: K and ldx must be multiples of 8");
+  LD_REQUIRE((size_t)2 * K * (w_f32 ? 4 : 2) + 64 <= 160 * 1024, "ld_gemv_pairs: K too large for the LDS-staged activations");
+  LD_REQUIRE(!(w_f32 && W2), "ld_gemv_pairs: gated form needs bf16 weights");
+  LD_REQUIRE(!w_f32 || (x_f32 && out_f32), "ld_gemv_pairs: fp32 weights need fp32 in/out");
+  LD_REQUIRE(!norm_w || (!x_f32 && !w_f32), "ld_gemv_pairs: fused RMSNorm needs bf16 x and weights");
+  GemvParams p{};
+  p.x = x; p.W = W; p.W2 = W2; p.bias = (const bf16_t*)bias; p.resid = resid; p.out = out;
+  p.B = (int)B; p.N = (int)N; p.K = (int)K; p.ldx = ldx; p.ldo = ldo; p.ldr = ldr;
+  p.x_f32 = x_f32; p.w_f32 = w_f32; p.out_f32 = out_f32; p.in_act = in_act; p.act = act;
+  p.norm_w = norm_w; p.norm_eps = norm_eps;
+  hipStream_t st = (hipStream_t)stream;
+  const int J = gemv_pair_reg_j(p);
+  if (gemv_pairs_in_one_launch(p, J)) {
+    switch (B) {
+      case 4: return launch_gemv_pairs_b<4>(p, J, st);
+      case 6: return launch_gemv_pairs_b<6>(p, J, st);
+      default: return launch_gemv_pairs_b<8>(p, J, st);
+    }
+  }
+  const long xs = x_f32 ? 4 : 2, os = out_f32 ? 4 : 2;
+  for (int64_t b = 0; b < B; b += 2) {
+    const int rc = ld_gemv((const char*)x + b * ldx * xs, ldx, x_f32, W, W2, w_f32, bias, resid ? (const char*)resid + b * ldr * os : nullptr,
+                           ldr, (char*)out + b * ldo * os, ldo, out_f32, 2, N, K, in_act, act, norm_w, norm_eps, stream);
+    if (rc) return rc;
+  }
+  return 0;
 }
 
 LD_API int ld_rmsnorm_bf16(const void* x, const float* w, void* out, int64_t rows, int64_t D, float eps, void* stream) {
@@ -1085,6 +1187,58 @@ LD_API int ld_llm_decode_forward(const ld_llm_layer* layers, int64_t n_layers, c
                  nullptr, 0.f, stream);
 }
 
+// ld_llm_decode_forward for P = B / 2 samples of one prompt (lm_model.py:417-508 once per sample, the cached blocks of
+// transformer_blocks.py:128-236): the same launches with B = 2 P rows -- ld_gemv_pairs streams every weight matrix once for all
+// pairs, the key-split attention is a grid over (B * heads, split) at the one shared position.  token: [P] (rows 2p, 2p+1 embed
+// token[p]).  Pair p of every buffer gets the bits ld_llm_decode_forward gives a B = 2 caller with the same Lmax and nsplit.
+LD_API int ld_llm_decode_forward_pairs(const ld_llm_layer* layers, int64_t n_layers, const float* emb_table, const int64_t* token,
+                                       const int32_t* pos, int32_t pos_value, void* x, void* qkv, void* att, void* gate, float* attn_ws,
+                                       const float* cos_t, const float* sin_t, const float* lnf_w, const float* lnf_b,
+                                       float* lnf_out, const float* head_w, float* logits, int64_t B, int64_t hidden,
+                                       int64_t heads, int64_t mlp, int64_t vocab, int64_t Lmax, int64_t nsplit, float rms_eps,
+                                       float ln_eps, void* stream) {
+  LD_REQUIRE(layers && n_layers > 0 && (emb_table == nullptr || token) && pos && x && qkv && att && gate && attn_ws && cos_t && sin_t &&
+             lnf_w && lnf_b && lnf_out && head_w && logits, "ld_llm_decode_forward_pairs: null pointer");
+  LD_REQUIRE(B >= 2 && B % 2 == 0, "ld_llm_decode_forward_pairs: %ld rows are not (cond, uncond) pairs", (long)B);
+  if (B > 2 * LD_LLM_MAX_PAIRS)
+    return ld_set_error(LD_ERR_UNSUPPORTED, "ld_llm_decode_forward_pairs: %ld samples, at most %d", (long)(B / 2), LD_LLM_MAX_PAIRS);
+  LD_REQUIRE(hidden == heads * 128, "ld_llm_decode_forward_pairs: head_dim must be 128 (hidden=%ld heads=%ld)", (long)hidden, (long)heads);
+  LD_REQUIRE(mlp >= 8 && mlp % 8 == 0 && vocab >= 1, "ld_llm_decode_forward_pairs: mlp must be a multiple of 8");
+  LD_REQUIRE(nsplit > 1 && (Lmax + nsplit - 1) / nsplit <= 16 * KV_MAXIT,
+             "ld_llm_decode_forward_pairs: the decode path is the key-split attention (nsplit > 1, <= 256 keys per split)");
+  LD_REQUIRE(pos_value < Lmax, "ld_llm_decode_forward_pairs: pos_value %d outside [0, Lmax)", (int)pos_value);
+  for (int64_t i = 0; i < n_layers; ++i) {
+    const ld_llm_layer& w = layers[i];
+    LD_REQUIRE(w.wqkv && w.wo && w.w1 && w.w3 && w.w2 && w.n0 && w.n1 && w.k_cache && w.v_cache,
+               "ld_llm_decode_forward_pairs: layer %ld has a null pointer", (long)i);
+  }
+  int rc = 0;
+  if (emb_table) {
+    hipLaunchKernelGGL(ld_embed_pairs_kernel, dim3((B * hidden + 255) / 256), dim3(256), 0, (hipStream_t)stream, emb_table,
+                       (const long*)token, (bf16_t*)x, (int)B, (int)hidden);
+    rc = ld_check_launch("ld_llm_decode_forward_pairs(embed)");
+  }
+  for (int64_t i = 0; i < n_layers && rc == 0; ++i) {
+    const ld_llm_layer& w = layers[i];
+    rc = ld_gemv_pairs(x, hidden, 0, w.wqkv, nullptr, 0, nullptr, nullptr, 0, qkv, 3 * hidden, 0, B, 3 * hidden, hidden, 0, 0,
+                       w.n0, rms_eps, stream);
+    if (rc) break;
+    rc = kv_attn_impl(nullptr, w.k_cache, w.v_cache, pos, pos_value, att, B, 1, heads, Lmax, attn_ws, nsplit, qkv, cos_t, sin_t, stream);
+    if (rc) break;
+    rc = ld_gemv_pairs(att, hidden, 0, w.wo, nullptr, 0, nullptr, x, hidden, x, hidden, 0, B, hidden, hidden, 0, 0, nullptr, 0.f, stream);
+    if (rc) break;
+    rc = ld_gemv_pairs(x, hidden, 0, w.w1, w.w3, 0, nullptr, nullptr, 0, gate, mlp, 0, B, mlp, hidden, 0, LD_ACT_GELU_TANH,
+                       w.n1, rms_eps, stream);
+    if (rc) break;
+    rc = ld_gemv_pairs(gate, mlp, 0, w.w2, nullptr, 0, nullptr, x, hidden, x, hidden, 0, B, hidden, mlp, 0, 0, nullptr, 0.f, stream);
+  }
+  if (rc) return rc;
+  rc = ld_layernorm_bf16_to_f32(x, hidden, lnf_w, lnf_b, lnf_out, B, hidden, ln_eps, stream);
+  if (rc) return rc;
+  return ld_gemv_pairs(lnf_out, hidden, 1, head_w, nullptr, 1, nullptr, nullptr, 0, logits, vocab, 1, B, vocab, hidden, 0, 0,
+                       nullptr, 0.f, stream);
+}
+
 #ifdef LD_VARIANTS   // the dependent-launch form of a decode step: measured slower, only in the variants build
 namespace {
 // the register GEMV in its dependent-launch form (B = 2): variant choice of launch_gemv_b, <= 128 registers, <= 512 workgroups
@@ -1185,6 +1339,25 @@ LD_API int ld_llm_sample_advance(const float* logits, float* probs, float* cfg_l
                      (int)V, guided, scale, temperature, (const int*)pos, (const int*)allowed, (int)allowed_stride,
                      (int)top_k, top_p, sa);
   return ld_check_launch("ld_llm_sample_advance");
+}
+
+// ld_llm_sample_advance for P samples in one launch of P workgroups (lm_model.py:417-508 per sample): workgroup p works on logits
+// rows (2p, 2p+1), noise / probs / cfg_logits row p, pos[p], token[p], out_tokens[p][..], out_count[p], sampled[p], x rows (2p, 2p+1).
+LD_API int ld_llm_sample_advance_pairs(const float* logits, float* probs, float* cfg_logits, int64_t V, int32_t guided, float scale,
+                                       float temperature, int32_t* pos, const int32_t* allowed, int64_t allowed_stride,
+                                       int32_t top_k, float top_p, const float* noise, const int32_t* forced, int64_t* token,
+                                       int64_t* out_tokens, int64_t out_stride, int32_t* out_count, int64_t* sampled,
+                                       const float* emb_table, void* x, int64_t P, int64_t D, void* stream) {
+  LD_REQUIRE(logits && V > 0 && V <= LD_SAMPLE_MAXV, "ld_llm_sample_advance_pairs: bad args (V=%ld, max %d)", (long)V, LD_SAMPLE_MAXV);
+  LD_REQUIRE(pos && noise && forced && token && out_tokens && out_count && emb_table && x, "ld_llm_sample_advance_pairs: null pointer");
+  LD_REQUIRE(P >= 1 && D >= 1 && out_stride >= 0, "ld_llm_sample_advance_pairs: P=%ld D=%ld out_stride=%ld", (long)P, (long)D, (long)out_stride);
+  if (P > LD_LLM_MAX_PAIRS) return ld_set_error(LD_ERR_UNSUPPORTED, "ld_llm_sample_advance_pairs: %ld samples, at most %d", (long)P, LD_LLM_MAX_PAIRS);
+  SampleArgs sa{noise, (const int*)forced, (int*)pos, (long*)token, (long*)out_tokens, (int*)out_count, (long*)sampled,
+                emb_table, (bf16_t*)x, 2, (int)D, (long)out_stride};
+  hipLaunchKernelGGL(ld_logits_to_probs_kernel<true>, dim3((unsigned)P), dim3(1024), 0, (hipStream_t)stream, logits, probs, cfg_logits,
+                     (int)V, guided, scale, temperature, (const int*)pos, (const int*)allowed, (int)allowed_stride,
+                     (int)top_k, top_p, sa);
+  return ld_check_launch("ld_llm_sample_advance_pairs");
 }
 
 LD_API int ld_llm_decode_advance(const int64_t* sampled, const int32_t* forced, int32_t* pos, int64_t* token,

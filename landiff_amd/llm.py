@@ -68,8 +68,11 @@ def forced_token_schedule(cfg: LLMConfig, S: int, num_frames: int):
 class LLMRunner:
     B = 2   # (cond, uncond)
 
-    def __init__(self, sd: dict, cfg: LLMConfig, device, max_text: int = 512, max_frames: int = 13):
-        self.cfg, self.dev = cfg, device
+    def __init__(self, sd: dict, cfg: LLMConfig, device, max_text: int = 512, max_frames: int = 13, max_samples: int = 1):
+        """max_samples > 1: sample_many() decodes up to that many samples of one prompt side by side (KV cache and step buffers
+        for 2 * max_samples rows; sample() keeps working on the first pair of them).  1: nothing extra is allocated."""
+        assert 1 <= max_samples <= ops.LLM_MAX_PAIRS, f"max_samples {max_samples} outside [1, {ops.LLM_MAX_PAIRS}]"
+        self.cfg, self.dev, self.max_samples = cfg, device, max_samples
         c = cfg
         g = lambda k, dt=BF: sd[k].detach().to(device=device, dtype=dt).contiguous()
         self.blocks = []
@@ -96,8 +99,14 @@ class LLMRunner:
         self.cos, self.sin = cis.real.contiguous().to(device), cis.imag.contiguous().to(device)
         # state in HBM
         B, H, D = self.B, c.heads, c.head_dim
-        self.kc = [torch.zeros(B, self.Lmax, H, D, device=device, dtype=BF) for _ in range(c.num_layers)]
-        self.vc = [torch.zeros(B, self.Lmax, H, D, device=device, dtype=BF) for _ in range(c.num_layers)]
+        if max_samples == 1:
+            self.kc = [torch.zeros(B, self.Lmax, H, D, device=device, dtype=BF) for _ in range(c.num_layers)]
+            self.vc = [torch.zeros(B, self.Lmax, H, D, device=device, dtype=BF) for _ in range(c.num_layers)]
+        else:
+            # rows (2p, 2p+1) = sample p; the first pair is the cache sample() and the prefill use (same address, same layout)
+            self.kc_all = [torch.zeros(B * max_samples, self.Lmax, H, D, device=device, dtype=BF) for _ in range(c.num_layers)]
+            self.vc_all = [torch.zeros(B * max_samples, self.Lmax, H, D, device=device, dtype=BF) for _ in range(c.num_layers)]
+            self.kc, self.vc = [t[:B] for t in self.kc_all], [t[:B] for t in self.vc_all]
         self.pos = torch.zeros(1, device=device, dtype=torch.int32)
         self.pos0 = torch.zeros(1, device=device, dtype=torch.int32)
         self.token = torch.zeros(1, device=device, dtype=torch.int64)
@@ -126,6 +135,18 @@ class LLMRunner:
         self.top_k, self.top_p = None, None
         # partial results [B*H][nsplit][130] + B*H arrival counters (zero between launches: the last split to arrive merges)
         self.attn_ws = torch.zeros(B * H * (self.nsplit * 130 + 1), device=device, dtype=torch.float32)
+        if max_samples > 1:
+            Pm, Bm = max_samples, B * max_samples
+            self.m_x, self.m_qkv, self.m_att, self.m_gate = e(Bm, c.hidden), e(Bm, 3 * c.hidden), e(Bm, c.hidden), e(Bm, c.mlp)
+            self.m_lnf, self.m_logits = e(Bm, c.hidden, dt=torch.float32), e(Bm, c.vocab, dt=torch.float32)
+            self.m_cfg_logits, self.m_noise = e(Pm, c.vocab, dt=torch.float32), e(Pm, c.vocab, dt=torch.float32)
+            self.m_pos = torch.zeros(Pm, device=device, dtype=torch.int32)        # one word per sample (all equal; word 0 is "the" position)
+            self.m_token = torch.zeros(Pm, device=device, dtype=torch.int64)
+            self.m_sampled = torch.zeros(Pm, device=device, dtype=torch.int64)
+            self.m_out_tokens = torch.zeros(Pm, self.Lmax, device=device, dtype=torch.int64)
+            self.m_out_count = torch.zeros(Pm, device=device, dtype=torch.int32)
+            # same nsplit as the two-row decode (the split rule is part of the bits), workspace for all rows
+            self.m_attn_ws = torch.zeros(Bm * H * (self.nsplit * 130 + 1), device=device, dtype=torch.float32)
         self._graph = None
         self._layer_table = None
         # Three forms of a decode step's blocks, identical bits (tests/variants/variant_cases.py):
@@ -276,40 +297,34 @@ class LLMRunner:
         torch.multinomial(self.probs, num_samples=1, generator=generator, out=self.sampled)
         ops.llm_decode_advance(self.sampled, self.forced, self.pos, self.token, self.out_tokens, self.out_count)
 
-    # ---- decode loop -----------------------------------------------------------------------------
-    @torch.no_grad()
-    def sample(self, text_emb: torch.Tensor, *, motion_score: float = 0.1, num_frames: int = 13, guidance_scale: float = 7.5,
-               temperature: float = 1.0, seed: int | None = None, generator=None, use_graph: bool = False,
-               teacher_fed=None, logits_log=None, top_k: int | None = None, top_p: float | None = None,
-               first_frame_tokens: torch.Tensor | None = None, on_segment=None, segment_tokens: int | None = None,
-               mode: str | None = None, prefix_tokens: torch.Tensor | None = None) -> torch.Tensor:
-        """Returns the clamped visual token ids, int64 [n_visual] on the device (lm_model.py:509-516).
-        top_k / top_p filter the unrestricted positions inside the sampling kernel (lm_model.py:441-447).
-        first_frame_tokens (int64 [iframe_len], e.g. from TokenizerEncoder.encode_to_index): use_gt_first_frame of the
-        reference (lm_model.py:332-352) -- the given I-frame tokens, END_OF_IFrame and the first START_OF_PFrame join the
-        prefilled prefix, sampling (and the RNG stream) starts at the first P token, the result begins with the given ids.
-        prefix_tokens (int64 [num_latent_tokens]: one whole segment, e.g. the .npy llm_infer saves next to a video): the same
-        for the first segment of a multi-segment decode -- its ids, with the markers forced_token_schedule puts between them,
-        and the next segment's START_OF_IFrame join the prefilled prefix; sampling starts at that segment's first I token.
-        on_segment(s): called on the host right after the step that emits the last of every `segment_tokens` visual tokens
-        has been QUEUED (tokens [s * segment_tokens, (s + 1) * segment_tokens) of self.out_tokens are then final in stream
-        order) -- lets a streaming caller start on segment s while later segments are still being decoded."""
+    def _decode_forward_many(self, P: int, pos_value: int):
+        """_decode_forward for P samples (rows (2p, 2p+1) of the m_* buffers): the embedding rows of their tokens, left in m_x by
+        the sampling launch, at position pos_value -> logits [2P, V]; one native call, every weight matrix streamed once."""
+        c, B = self.cfg, 2 * P
+        if self._layer_table is None:
+            self._layer_table = ops.llm_layer_table(self.blocks, self.kc, self.vc)      # (kc[i] is the head of kc_all[i]: same address)
+        ops.llm_decode_forward_pairs(self._layer_table, None, self.m_token[:P], self.m_pos[:P], self.m_x[:B], self.m_qkv[:B], self.m_att[:B],
+                                     self.m_gate[:B], self.m_attn_ws, self.cos, self.sin, self.ln_w, self.ln_b, self.m_lnf[:B], self.head,
+                                     self.m_logits[:B], c.heads, self.Lmax, self.nsplit, c.rms_eps, c.ln_eps, pos_value=pos_value)
+
+    def _sample_and_advance_many(self, gens, guided, scale, temperature, top_k=None, top_p=None, logits_log=None):
+        """_sample_and_advance for len(gens) samples: generator p draws the [vocab] Exp(1) row sample() draws from it at this
+        step (and nothing else), then one launch samples, records and advances every sample and embeds its next token."""
+        P = len(gens)
+        noise, cfg_logits = self.m_noise[:P], self.m_cfg_logits[:P]
+        for p in range(P):
+            noise[p].exponential_(1.0, generator=gens[p])
+        ops.llm_sample_advance_pairs(self.m_logits[:2 * P], None, cfg_logits, guided, scale, temperature, self.m_pos[:P], self.allowed, noise,
+                                     self.forced, self.m_token[:P], self.m_out_tokens[:P], self.m_out_count[:P], self.m_sampled[:P],
+                                     self.emb, self.m_x[:2 * P], top_k=top_k, top_p=top_p)
+        if logits_log is not None:
+            logits_log.append(cfg_logits.clone())
+
+    def _decode_plan(self, text_emb, motion_score, num_frames, first_frame_tokens, prefix_tokens):
+        """What sample() / sample_many() do before the prefill: the prefix features (with the given first frame / first segment
+        appended), the forced / restricted schedule uploaded to the device tables.
+        -> (feats, S_last = position of the last prefilled token, full_len, forced, n_visual still to sample, n_prefix)."""
         c, dev = self.cfg, self.dev
-        self.top_k, self.top_p = top_k, top_p
-        # mode: the form of a decode step's blocks ("chain" / "chained" / "fused", see __init__; None: the runner's default);
-        # an unsupported shape falls back to "chain"
-        mode = self.decode_mode if mode is None else mode
-        assert mode in ("chain", "chained", "fused"), mode
-        if mode != "chain" and not _lib.has_variants():
-            raise _lib.LandiffHipError(f"decode mode {mode!r} needs the variants build of the library (LD_BUILD_VARIANTS=1 "
-                                       f"landiff_amd/csrc/build.sh, then LANDIFF_HIP_LIB={_lib.VARIANTS_LIB_PATH}); the shipped library "
-                                       "has the per-operation chain only")
-        if (mode == "fused" and not self.fused_supported) or (mode == "chained" and (not self.chained_supported or use_graph)):
-            mode = "chain"
-        self._mode = mode
-        guided = guidance_scale > 0 and guidance_scale != 1
-        # unguided (ARSampleCfg's dataclass default cfg=0.0, lm_model.py:311-319): the conditional row is independent of the
-        # second row, so the resident two-row buffers are kept and the sampling kernel reads row 0 only.
         feats = self.prefix_features(text_emb, float(num_frames), motion_score)
         S = feats.shape[1] - 1
         full_len, forced, restricted, n_visual = forced_token_schedule(c, S, num_frames)
@@ -350,6 +365,44 @@ class LLMRunner:
             al[p, 0] = len(ids)
             al[p, 1:1 + len(ids)] = torch.tensor(ids, dtype=torch.int32)
         self.forced.copy_(ft); self.allowed.copy_(al)
+        return feats, S_last, full_len, forced, n_visual, n_prefix
+
+    # ---- decode loop -----------------------------------------------------------------------------
+    @torch.no_grad()
+    def sample(self, text_emb: torch.Tensor, *, motion_score: float = 0.1, num_frames: int = 13, guidance_scale: float = 7.5,
+               temperature: float = 1.0, seed: int | None = None, generator=None, use_graph: bool = False,
+               teacher_fed=None, logits_log=None, top_k: int | None = None, top_p: float | None = None,
+               first_frame_tokens: torch.Tensor | None = None, on_segment=None, segment_tokens: int | None = None,
+               mode: str | None = None, prefix_tokens: torch.Tensor | None = None) -> torch.Tensor:
+        """Returns the clamped visual token ids, int64 [n_visual] on the device (lm_model.py:509-516).
+        top_k / top_p filter the unrestricted positions inside the sampling kernel (lm_model.py:441-447).
+        first_frame_tokens (int64 [iframe_len], e.g. from TokenizerEncoder.encode_to_index): use_gt_first_frame of the
+        reference (lm_model.py:332-352) -- the given I-frame tokens, END_OF_IFrame and the first START_OF_PFrame join the
+        prefilled prefix, sampling (and the RNG stream) starts at the first P token, the result begins with the given ids.
+        prefix_tokens (int64 [num_latent_tokens]: one whole segment, e.g. the .npy llm_infer saves next to a video): the same
+        for the first segment of a multi-segment decode -- its ids, with the markers forced_token_schedule puts between them,
+        and the next segment's START_OF_IFrame join the prefilled prefix; sampling starts at that segment's first I token.
+        on_segment(s): called on the host right after the step that emits the last of every `segment_tokens` visual tokens
+        has been QUEUED (tokens [s * segment_tokens, (s + 1) * segment_tokens) of self.out_tokens are then final in stream
+        order) -- lets a streaming caller start on segment s while later segments are still being decoded."""
+        c, dev = self.cfg, self.dev
+        self.top_k, self.top_p = top_k, top_p
+        # mode: the form of a decode step's blocks ("chain" / "chained" / "fused", see __init__; None: the runner's default);
+        # an unsupported shape falls back to "chain"
+        mode = self.decode_mode if mode is None else mode
+        assert mode in ("chain", "chained", "fused"), mode
+        if mode != "chain" and not _lib.has_variants():
+            raise _lib.LandiffHipError(f"decode mode {mode!r} needs the variants build of the library (LD_BUILD_VARIANTS=1 "
+                                       f"landiff_amd/csrc/build.sh, then LANDIFF_HIP_LIB={_lib.VARIANTS_LIB_PATH}); the shipped library "
+                                       "has the per-operation chain only")
+        if (mode == "fused" and not self.fused_supported) or (mode == "chained" and (not self.chained_supported or use_graph)):
+            mode = "chain"
+        self._mode = mode
+        guided = guidance_scale > 0 and guidance_scale != 1
+        # unguided (ARSampleCfg's dataclass default cfg=0.0, lm_model.py:311-319): the conditional row is independent of the
+        # second row, so the resident two-row buffers are kept and the sampling kernel reads row 0 only.
+        feats, S_last, full_len, forced, n_visual, n_prefix = self._decode_plan(text_emb, motion_score, num_frames, first_frame_tokens,
+                                                                                prefix_tokens)
         self._x_from_tail = self.fused_tail and teacher_fed is None          # (a teacher-fed token is written by the host: re-embed it)
         self.out_count.zero_()
         if generator is None and seed:
@@ -411,6 +464,87 @@ class LLMRunner:
             out = torch.cat([first_frame_tokens.reshape(-1).to(dev, torch.int64), out])
         if n_prefix:
             out = torch.cat([prefix_tokens.reshape(-1).to(dev, torch.int64), out])
+        return out.clamp(0, c.visual_vocab - 1)
+
+    @torch.no_grad()
+    def sample_many(self, text_emb: torch.Tensor, seeds, *, motion_score: float = 0.1, num_frames: int = 13, guidance_scale: float = 7.5,
+                    temperature: float = 1.0, use_graph: bool = False, teacher_fed=None, logits_log=None, top_k: int | None = None,
+                    top_p: float | None = None, first_frame_tokens: torch.Tensor | None = None, on_segment=None,
+                    segment_tokens: int | None = None, mode: str | None = None, prefix_tokens: torch.Tensor | None = None) -> torch.Tensor:
+        """len(seeds) samples of ONE prompt from one weight stream: int64 [P, n_visual], row p exactly the ids
+        sample(..., seed=seeds[p]) returns.  The samples share the text, the motion score and any first_frame_tokens /
+        prefix_tokens, hence the prefill (run once for the (cond, uncond) pair, its KV rows and first logits copied to the other
+        pairs), the position and the forced / restricted schedule; each has its own torch.Generator seeded as sample() seeds it
+        and drawing only its own noise row per step, its own token, KV rows and output row.  A step is one
+        ld_llm_decode_forward_pairs (every weight matrix streamed once for all 2P rows) and one ld_llm_sample_advance_pairs.
+        The per-operation "chain" form only, no graph capture, no teacher feeding.  Keywords as sample(); logits_log receives
+        [P, vocab] per step; on_segment(s) fires when segment s of EVERY sample is queued (self.m_out_tokens[p])."""
+        c, dev = self.cfg, self.dev
+        seeds = [int(s) for s in seeds]
+        P = len(seeds)
+        mode = "chain" if mode is None else mode
+        if mode != "chain":
+            raise ValueError(f"sample_many: decode mode {mode!r} is not supported (the batched decode is the per-operation 'chain' form)")
+        if use_graph:
+            raise ValueError("sample_many: graph capture is not supported")
+        if teacher_fed is not None:
+            raise ValueError("sample_many: teacher_fed is not supported (teacher forcing has one token stream)")
+        if not 1 <= P <= self.max_samples:
+            raise ValueError(f"sample_many: {P} seeds, this runner was built with max_samples={self.max_samples} "
+                             f"(LLMRunner(..., max_samples=N), N <= {ops.LLM_MAX_PAIRS})")
+        if not all(seeds):
+            raise ValueError("sample_many needs a non-zero seed per sample (sample() draws a zero seed from the shared default generator)")
+        if self.max_samples == 1:
+            return self.sample(text_emb, motion_score=motion_score, num_frames=num_frames, guidance_scale=guidance_scale,
+                               temperature=temperature, seed=seeds[0], logits_log=logits_log, top_k=top_k, top_p=top_p,
+                               first_frame_tokens=first_frame_tokens, on_segment=on_segment, segment_tokens=segment_tokens,
+                               mode="chain", prefix_tokens=prefix_tokens)[None]
+        self._mode = "chain"
+        guided = guidance_scale > 0 and guidance_scale != 1
+        feats, S_last, full_len, forced, n_visual, n_prefix = self._decode_plan(text_emb, motion_score, num_frames, first_frame_tokens,
+                                                                                prefix_tokens)
+        gens = []
+        for s in seeds:
+            g = torch.Generator(device=dev)
+            g.manual_seed(s)                                # lm_model.py:398-402, once per sample
+            gens.append(g)
+        B = 2 * P
+        out_tokens, out_count = self.m_out_tokens[:P], self.m_out_count[:P]
+        sample_and_advance = lambda: self._sample_and_advance_many(gens, guided, guidance_scale, temperature, top_k, top_p, logits_log)
+
+        emitted = 0
+        def note_position(q):              # the token of position q has just been queued (for every sample)
+            nonlocal emitted
+            if on_segment is None or q in forced:
+                return
+            emitted += 1
+            if emitted % segment_tokens == 0:
+                on_segment(emitted // segment_tokens - 1)
+        assert on_segment is None or (segment_tokens and first_frame_tokens is None and prefix_tokens is None)
+        out_count.zero_()
+        self.m_attn_ws.zero_()             # (its counter words sit where another P's partial results were)
+        self._prefill(feats)
+        n_pre = S_last + 1                 # prefilled positions
+        for cache in self.kc_all + self.vc_all:
+            for p in range(1, P):
+                cache[2 * p:2 * p + 2, :n_pre].copy_(cache[:2, :n_pre])
+        self.m_logits[:B].view(P, 2, c.vocab).copy_(self.logits[None].expand(P, -1, -1))
+        self.m_pos.fill_(S_last)
+        sample_and_advance()
+        note_position(S_last + 1)
+        steps = full_len - (S_last + 1) - 1
+        t_enq = time.perf_counter()
+        for it in range(steps):
+            self._decode_forward_many(P, S_last + 1 + it)
+            sample_and_advance()
+            note_position(S_last + 2 + it)
+        self.host_enqueue_s = time.perf_counter() - t_enq
+        counts = out_count.tolist()
+        assert counts == [n_visual] * P, (counts, n_visual)
+        out = out_tokens[:, :n_visual]
+        head = [t.reshape(1, -1).to(dev, torch.int64).expand(P, -1) for t in (prefix_tokens, first_frame_tokens) if t is not None]
+        if head:
+            out = torch.cat(head + [out], 1)
         return out.clamp(0, c.visual_vocab - 1)
 
     def _raise_on_wait_timeout(self):

@@ -41,7 +41,7 @@ class PromptInputs:
 
 class LanDiffPipeline:
     def __init__(self, cfg: PipelineConfig, states: dict, device="cuda:0", max_llm_frames: int | None = None,
-                 fp8_gemm: bool = False, theia=None):
+                 fp8_gemm: bool = False, theia=None, max_samples: int = 1):
         if not torch.cuda.is_available():
             raise _lib.LandiffHipError("LanDiffPipeline needs an MI355X GPU: there is no CPU fallback")
         _lib.load()
@@ -49,8 +49,9 @@ class LanDiffPipeline:
         self.dev = torch.device(device)
         torch.cuda.set_device(self.dev)
         # max_llm_frames > segment_length sizes the KV cache / position tables for multi-segment (streaming) decodes
-        self.llm = LLMRunner(states["llm"], cfg.llm, self.dev,
-                             max_frames=max_llm_frames or cfg.llm.segment_length) if "llm" in states else None
+        # max_samples > 1: generate_samples decodes that many samples of a prompt side by side (LLMRunner.sample_many)
+        self.llm = LLMRunner(states["llm"], cfg.llm, self.dev, max_frames=max_llm_frames or cfg.llm.segment_length,
+                             max_samples=max_samples) if "llm" in states else None
         self.detok = Detokenizer(states["tok"], states["ups"], cfg.tok, cfg.ups, self.dev)
         # fp8_gemm: BASELINE configs[4] (e4m3 operands for the DiT's four large linears); never the headline configuration
         self.dit = ControlDiTRunner(states["dit_main"], states["dit_control"], cfg.dit, self.dev, fp8_gemm=fp8_gemm)
@@ -110,6 +111,19 @@ class LanDiffPipeline:
         self._t("llm", t0)
         z = self.generate_latent(tokens, inp)
         return self.decode(z, want_float=want_float)
+
+    @torch.no_grad()
+    def generate_samples(self, inp: PromptInputs, seeds, want_float: bool = False) -> list:
+        """Several candidates of one prompt: result i is identical to `self(replace(inp, seed=seeds[i]))`.  The AR decode of all
+        seeds is one LLMRunner.sample_many (the LLM's weights streamed once per step for all of them; needs
+        LanDiffPipeline(..., max_samples >= len(seeds)) and non-zero seeds); detokenize, DiT and VAE then run per sample."""
+        from dataclasses import replace
+        t0 = time.perf_counter()
+        tokens = self.llm.sample_many(inp.llm_text_emb, seeds, motion_score=inp.motion_score, num_frames=self.cfg.llm.segment_length,
+                                      guidance_scale=inp.cfg, temperature=1.0)
+        self._t("llm", t0)
+        return [self.decode(self.generate_latent(tokens[i], replace(inp, seed=int(s))), want_float=want_float)
+                for i, s in enumerate(seeds)]
 
 
     # ---- several prompts on one GPU: prompt-level software pipeline ---------------------------------------
