@@ -29,8 +29,9 @@ extern "C" {
  * ld_groupnorm_stats_from_conv were added.  8: ld_gemm_qkv_heads_mxfp8 was added.
  * 9: ld_attn_fwd_bf16_exact was added.  10: ld_attn_last_fallbacks was added.  11: ld_vae_enc_place_input,
  * ld_vae_enc_downsample and ld_vae_posterior were added.  12: ld_vit_patch_rows, ld_vit_embed and ld_vit_tail were added,
- * ld_qkv_split gained mode 2.  13: ld_gemm_route was added. */
-#define LD_ABI_VERSION 14
+ * ld_qkv_split gained mode 2.  13: ld_gemm_route was added.  14: ld_gemv_pairs, ld_llm_decode_forward_pairs and
+ * ld_llm_sample_advance_pairs were added.  15: ld_llm_token_logprobs and ld_llm_head_f32 were added. */
+#define LD_ABI_VERSION 15
 
 int ld_version(void);
 const char* ld_last_error(void);
@@ -429,6 +430,39 @@ int ld_llm_sample_advance_pairs(const float* logits, float* probs, float* cfg_lo
  * (the elif chain of lm_model.py:455-508). */
 int ld_llm_decode_advance(const int64_t* sampled, const int32_t* forced, int32_t* pos, int64_t* token,
                           int64_t* out_tokens, int32_t* out_count, void* stream);
+
+/* ---- scoring of token sequences (ld_llm_score.hip) ---- */
+
+/* Largest vocabulary of the single-workgroup sampling / scoring kernels (ld_llm_logits_to_probs, ld_llm_sample_advance*,
+ * ld_llm_token_logprobs). */
+#define LD_SAMPLE_MAXV 4096
+
+/* Log-probability of target[r] under the distribution ld_llm_logits_to_probs builds from logits row r (lm_model.py:417-454:
+ * CFG `u + s*(c-u)` when guided, / temperature, restriction to allowed[pos + 1], top-k and top-p at unrestricted positions with
+ * the same tie, stable-rank and sequential-cumsum rules), n rows, one workgroup each.  Row r's conditional logits are
+ * cond + r * cond_stride and its unconditional ones uncond + r * uncond_stride (fp32, V <= LD_SAMPLE_MAXV each; uncond may be NULL
+ * when not guided): [2][n][V] is (base, base + n * ld, stride ld), the decode's [2P][V] pairs are (base, base + V, stride 2V).
+ * Position of row r: pos[r * pos_stride] + pos_bias when pos != NULL (a device word; after a sampling launch has advanced it,
+ * pos_bias = -1 names the position that launch sampled at), else pos_bias + r.  allowed ([n_pos][allowed_stride], as
+ * ld_llm_logits_to_probs) and forced ([n_pos], as ld_llm_decode_advance) are the shared schedule, either may be NULL; a row whose
+ * pos + 1 is outside [0, n_pos) gets NaN and valid 0 without a table read.
+ * logprob[r] = (l_t - max) - log(sum exp(l - max)) [- log(kept mass) under top-p], taken in the log domain: finite wherever the
+ * target is in the support, however small its probability; -inf exactly when the restriction, top-k or top-p removes the target
+ * (or target is no id of [0, V)).  forced[pos + 1] >= 0: the schedule writes that token, the row is not a draw: logprob 0,
+ * valid 0.  valid (optional) is 1 for every other row.  cfg_logits (optional, row r at cfg_logits + r * cfg_stride) receives the
+ * guided logits of the rows that are draws with a target in [0, V): the bits ld_llm_logits_to_probs writes to its cfg_logits. */
+int ld_llm_token_logprobs(const float* cond, int64_t cond_stride, const float* uncond, int64_t uncond_stride, int64_t n,
+                          int64_t V, int32_t guided, float scale, float temperature, const int32_t* pos, int64_t pos_stride,
+                          int32_t pos_bias, const int32_t* allowed, int64_t allowed_stride, const int32_t* forced,
+                          int64_t n_pos, int32_t top_k, float top_p, const int64_t* target, float* logprob, int32_t* valid,
+                          float* cfg_logits, int64_t cfg_stride, void* stream);
+
+/* C[M][N] = A[M][K] . W[N][K]^T, fp32 operands and fp32 accumulation (v_mfma_f32_32x32x2_f32: each element a k-ordered fmaf
+ * chain), row strides lda / ldw / ldc in elements: the head of transformer.py:112-118 on every row of a teacher-forced pass (the
+ * decode's two rows go through ld_gemv).  Any M, N; K, lda, ldw multiples of 4 and A, W 16-byte aligned (LD_ERR_INVALID
+ * otherwise).  Nothing outside [M] x [N] of C is written. */
+int ld_llm_head_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int64_t M, int64_t N,
+                    int64_t K, void* stream);
 
 /* ---- normalisation kernels (ld_norm.hip) ---- */
 

@@ -25,6 +25,11 @@ def parse_args(argv=None):
     parser.add_argument("--num_samples", type=int, default=1,
                         help="Candidates of the prompt (1-4), seeds --seed .. --seed + N - 1, their tokens from ONE batched AR decode; "
                              "N > 1 writes <save_file_name>_<i>.mp4 / _<i>.npy, each what --seed (seed + i) alone produces.")
+    parser.add_argument("--keep", type=int, default=None,
+                        help="Best-of-N: with --num_samples N >= K, rank the N candidates by the total log-probability of their "
+                             "tokens under the distribution they were sampled from and run the diffusion stage for the K most "
+                             "likely only.  All N .npy are written, videos for the kept ones (named by candidate index), and "
+                             "<save_file_name>_scores.json lists {index, seed, logprob, kept} for every candidate.")
     parser.add_argument("--extend_video", type=str, default=None,
                         help="Continue this clip instead of generating from scratch: a uint8 [F, H, W, 3] .npy (the format "
                              "save_video_tensor falls back to) or an mp4 when imageio can read it.")
@@ -48,6 +53,11 @@ def parse_args(argv=None):
         parser.error("--num_samples applies to generation from a prompt, not to --extend_video")
     if args.num_samples > 1 and not all(args.seed + i for i in range(args.num_samples)):
         parser.error("--num_samples needs non-zero seeds (--seed .. --seed + N - 1)")
+    if args.keep is not None:
+        if args.num_samples < 2:
+            parser.error("--keep ranks the candidates of --num_samples N (N >= 2)")
+        if not 1 <= args.keep <= args.num_samples:
+            parser.error(f"--keep must be between 1 and --num_samples ({args.num_samples})")
     return args
 
 
@@ -120,7 +130,9 @@ def sample_names(args) -> list:
 
 
 def llm_infer_samples(args):
-    """--num_samples N > 1: llm_infer for seeds seed .. seed + N - 1 from one batched decode -> tokens [N, n_visual] (cuda)."""
+    """--num_samples N > 1: llm_infer for seeds seed .. seed + N - 1 from one batched decode -> tokens [N, n_visual] (cuda).
+    -> (tokens, kept): kept = the candidate indices --keep K selects, in rank order (<save_file_name>_scores.json is written next to
+    the .npy files), or None without --keep: every candidate."""
     llm_model_cfg = build_llm()
     first = first_frame_tokens(args) if args.first_frame else None
     llm = ArModelInferWrapper(args.llm_ckpt, llm_model_cfg, max_samples=args.num_samples)
@@ -129,19 +141,29 @@ def llm_infer_samples(args):
                     sample_cfg=ARSampleCfg(temperature=1.0, cfg=args.cfg, motion_score=args.motion_score,
                                            num_frames=llm_model_cfg.segment_length, use_gt_first_frame=first is not None),
                     first_frame_tokens=first)
-    tokens = llm(task, seeds=[s for s, _ in names]).result
+    task = llm(task, seeds=[s for s, _ in names], return_logprobs=args.keep is not None)
+    tokens = task.result
     for row, (_, stem) in zip(tokens, names):
         path = Path(f"{stem}.npy")
         path.parent.mkdir(parents=True, exist_ok=True)
         np.save(path, row.numpy())
     del llm
     torch.cuda.empty_cache()
-    return tokens.cuda()
+    if args.keep is None:
+        return tokens.cuda(), None
+    from landiff_amd.pipeline import rank_candidates, write_scores_json
+    scores = task.logprobs.double().sum(1).tolist()
+    kept = rank_candidates(scores)[:args.keep]
+    write_scores_json(f"{args.save_file_name}_scores.json", [s for s, _ in names], scores, kept)
+    return tokens.cuda(), kept
 
 
-def infer_diffusion_samples(args, tokens):
+def infer_diffusion_samples(args, tokens, kept=None):
+    """kept (--keep): the candidate indices to run, in rank order; None: every candidate."""
     model = CogModelInferWrapper(ckpt_path=args.diffusion_ckpt)
-    for row, (seed, stem) in zip(tokens, sample_names(args)):
+    names = sample_names(args)
+    for i in (range(len(names)) if kept is None else kept):
+        row, (seed, stem) = tokens[i], names[i]
         task = model(VideoTask(save_file_name=f"{stem}.mp4", prompt=args.prompt, seed=seed, fps=8, semantic_token=row))
         save_video_tensor(task.result, task.save_file_name, fps=task.fps)
         print(f"save video to {task.save_file_name}")
@@ -234,7 +256,7 @@ def main():
         extend_diffusion(args)
         return
     if args.num_samples > 1:
-        infer_diffusion_samples(args, llm_infer_samples(args))
+        infer_diffusion_samples(args, *llm_infer_samples(args))
         return
     infer_diffusion(args, llm_infer(args))
 

@@ -49,6 +49,9 @@ class CodeTask:
     #   gt_tokens          -- teacher_forcing: the whole clip, fed back instead of the sampled ids (lm_model.py:506-507).
     first_frame_tokens: None | torch.Tensor = None
     gt_tokens: None | torch.Tensor = None
+    # forward(..., seeds=..., return_logprobs=True): fp32 [len(seeds), sampled positions], the log-probability of every sampled id
+    # under the distribution it was drawn from (LLMRunner.sample_many(return_logprobs=True)); their row sums rank the candidates
+    logprobs: None | torch.Tensor = None
 
 
 def teacher_sequence(cfg: LLMConfig, S: int, num_frames: int, gt_tokens: torch.Tensor, skip: int = 0) -> torch.Tensor:
@@ -87,9 +90,12 @@ class ArModelInferWrapper(torch.nn.Module):
         self.runner = LLMRunner(sd, model_cfg, self.device_, max_text=model_cfg.max_cond_tokens, max_samples=max_samples)
 
     @torch.no_grad()
-    def forward(self, code_task: CodeTask, seeds=None) -> CodeTask:
+    def forward(self, code_task: CodeTask, seeds=None, return_logprobs: bool = False) -> CodeTask:
         """seeds (optional, non-zero ints, at most the wrapper's max_samples): that many samples of the prompt from one batched
-        decode (LLMRunner.sample_many) -- .result is then LongTensor [len(seeds), n_visual], row i what seed seeds[i] alone gives."""
+        decode (LLMRunner.sample_many) -- .result is then LongTensor [len(seeds), n_visual], row i what seed seeds[i] alone gives.
+        return_logprobs (with seeds): .logprobs receives the sampled ids' log-probabilities; .result is unchanged by it."""
+        if return_logprobs and seeds is None:
+            raise ValueError("return_logprobs scores the candidates of a batched decode: give seeds")
         sc, c = code_task.sample_cfg, self.config
         first = None
         if sc.use_gt_first_frame:
@@ -117,7 +123,10 @@ class ArModelInferWrapper(torch.nn.Module):
                 raise ValueError("teacher_forcing decodes one token stream: no seeds")
             tokens = self.runner.sample_many(text, seeds, motion_score=sc.motion_score, num_frames=sc.num_frames,
                                              guidance_scale=sc.cfg, temperature=sc.temperature, top_k=sc.top_k, top_p=sc.top_p,
-                                             first_frame_tokens=first)
+                                             first_frame_tokens=first, return_logprobs=return_logprobs)
+            if return_logprobs:
+                tokens, logprobs = tokens
+                code_task.logprobs = logprobs.cpu()
             code_task.result = tokens.cpu()
             return code_task
         tokens = self.runner.sample(text, motion_score=sc.motion_score,

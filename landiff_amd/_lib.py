@@ -44,7 +44,7 @@ class LlmLayer(Structure):
 
 
 _lib = None
-ABI_VERSION = 14         # LD_ABI_VERSION of include/landiff_hip.h that SIGNATURES below were written against
+ABI_VERSION = 15         # LD_ABI_VERSION of include/landiff_hip.h that SIGNATURES below were written against
 
 I64 = c_int64
 I32 = c_int32
@@ -94,6 +94,9 @@ SIGNATURES: dict[str, list] = {
     "ld_llm_sample_advance": [P, P, P, I64, I32, c_float, c_float, P, P, I64, I32, c_float, P, P, P, P, P, P, P, P, I64, I64, P],
     "ld_llm_sample_advance_pairs": [P, P, P, I64, I32, c_float, c_float, P, P, I64, I32, c_float, P, P, P, P, I64, P, P, P, P, I64, I64,
                                     P],
+    "ld_llm_token_logprobs": [P, I64, P, I64, I64, I64, I32, c_float, c_float, P, I64, I32, P, I64, P, I64, I32, c_float, P, P, P, P,
+                              I64, P],
+    "ld_llm_head_f32": [P, I64, P, I64, P, I64, I64, I64, I64, P],
     "ld_layernorm": [P, I64, I32, P, P, P, I64, I32, I64, I64, c_float, P, I64, I64, I64, I64, I64, I64, I64, P],
     "ld_qkv_split": [P, P, P, P, I64, I64, I64, I64, I32, P, P, P, P, c_float, P, P, P],
     "ld_groupnorm_stats_blocks": [I64],

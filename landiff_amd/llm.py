@@ -206,7 +206,9 @@ class LLMRunner:
         return feats
 
     # ---- transformer ---------------------------------------------------------------------------
-    def _prefill(self, feats: torch.Tensor):
+    def _prefill_blocks(self, feats: torch.Tensor):
+        """Every block over all m positions of feats [2, m, hidden] from position 0 (KV rows [0, m) of the first pair's cache are
+        written) -> the residual stream, bf16 [2 * m, hidden]."""
         c = self.cfg
         B, m, d = feats.shape
         M = B * m
@@ -228,6 +230,12 @@ class LLMRunner:
             ops.gemm(xn, w["w3"], out=h3)
             ops.gemm(xn, w["w1"], out=gate, act="gelu_tanh", mul=h3)
             ops.gemm(gate, w["w2"], out=x, resid=x)
+        return x
+
+    def _prefill(self, feats: torch.Tensor):
+        c = self.cfg
+        B, m, d = feats.shape
+        x = self._prefill_blocks(feats)
         last = x.view(B, m, d)[:, -1]                       # rows (b, m-1), stride m*d
         ops.layernorm_bf16_to_f32(last, self.ln_w, self.ln_b, self.lnf, c.ln_eps)
         ops.gemv(self.lnf, self.head, self.logits)
@@ -373,8 +381,13 @@ class LLMRunner:
                temperature: float = 1.0, seed: int | None = None, generator=None, use_graph: bool = False,
                teacher_fed=None, logits_log=None, top_k: int | None = None, top_p: float | None = None,
                first_frame_tokens: torch.Tensor | None = None, on_segment=None, segment_tokens: int | None = None,
-               mode: str | None = None, prefix_tokens: torch.Tensor | None = None) -> torch.Tensor:
+               mode: str | None = None, prefix_tokens: torch.Tensor | None = None, return_logprobs: bool = False):
         """Returns the clamped visual token ids, int64 [n_visual] on the device (lm_model.py:509-516).
+        return_logprobs: -> (ids, logprobs): fp32 [n_visual], the log-probability of every SAMPLED id.  With first_frame_tokens /
+        prefix_tokens the given ids are not draws and have none: logprobs then covers ids[-logprobs.numel():] only, it is SHORTER
+        than ids under the guided, restricted, filtered distribution it
+        was drawn from -- one ld_llm_token_logprobs launch per step on the step's own logits; the ids are those of the call
+        without the flag.  "chain" form only: refused with use_graph, another mode or teacher_fed.
         top_k / top_p filter the unrestricted positions inside the sampling kernel (lm_model.py:441-447).
         first_frame_tokens (int64 [iframe_len], e.g. from TokenizerEncoder.encode_to_index): use_gt_first_frame of the
         reference (lm_model.py:332-352) -- the given I-frame tokens, END_OF_IFrame and the first START_OF_PFrame join the
@@ -391,6 +404,9 @@ class LLMRunner:
         # an unsupported shape falls back to "chain"
         mode = self.decode_mode if mode is None else mode
         assert mode in ("chain", "chained", "fused"), mode
+        if return_logprobs and (use_graph or mode != "chain" or teacher_fed is not None):
+            raise ValueError("sample: return_logprobs needs the per-operation 'chain' form without graph capture or teacher feeding "
+                             f"(use_graph={use_graph}, mode={mode!r}, teacher_fed {'given' if teacher_fed is not None else 'None'})")
         if mode != "chain" and not _lib.has_variants():
             raise _lib.LandiffHipError(f"decode mode {mode!r} needs the variants build of the library (LD_BUILD_VARIANTS=1 "
                                        f"landiff_amd/csrc/build.sh, then LANDIFF_HIP_LIB={_lib.VARIANTS_LIB_PATH}); the shipped library "
@@ -420,6 +436,11 @@ class LLMRunner:
         self._prefill(feats)
         self.pos.fill_(S_last)
         self._sample_and_advance(guided, guidance_scale, temperature, generator)
+        lp_steps = None
+        if return_logprobs:
+            lp_steps = torch.empty(full_len - (S_last + 1), 1, device=dev, dtype=torch.float32)      # one row per generated position
+            self._step_logprobs(self.logits[0:1], self.logits[1:2], self.sampled.view(1), self.pos, lp_steps[0], guided,
+                                guidance_scale, temperature, top_k, top_p)
         try:                               # from here on the host-side position is live: the finally below always retires it
             self._pos_host = S_last + 1
             if self._mode == "fused":
@@ -449,6 +470,9 @@ class LLMRunner:
                     self._decode_forward()
                     self._sample_and_advance(guided, guidance_scale, temperature, generator)
                     self._pos_host += 1
+                    if lp_steps is not None:
+                        self._step_logprobs(self.logits[0:1], self.logits[1:2], self.sampled.view(1), self.pos, lp_steps[it + 1],
+                                            guided, guidance_scale, temperature, top_k, top_p)
                 note_position(S_last + 2 + it)
                 if logits_log is not None:
                     logits_log.append(self.cfg_logits.clone())
@@ -464,13 +488,73 @@ class LLMRunner:
             out = torch.cat([first_frame_tokens.reshape(-1).to(dev, torch.int64), out])
         if n_prefix:
             out = torch.cat([prefix_tokens.reshape(-1).to(dev, torch.int64), out])
-        return out.clamp(0, c.visual_vocab - 1)
+        out = out.clamp(0, c.visual_vocab - 1)
+        if lp_steps is not None:
+            return out, self._gather_logprobs(lp_steps, S_last, full_len, forced)[0]
+        return out
+
+    def _step_logprobs(self, cond, uncond, sampled, pos, out, guided, scale, temperature, top_k, top_p):
+        """The log-probabilities of the tokens the sampling launch just drew, from the logits it read (the next forward has not
+        been queued yet).  That launch has advanced the position words: bias -1 names the position it sampled at."""
+        ops.llm_token_logprobs(cond, uncond, sampled, out, guided, scale, temperature, pos=pos, pos_stride=1 if pos.numel() > 1 else 0,
+                               pos_bias=-1, allowed=self.allowed, forced=self.forced, top_k=top_k, top_p=top_p)
+
+    def _gather_logprobs(self, lp_steps, S_last, full_len, forced):
+        """lp_steps [generated positions, P] -> [P, sampled positions]: the rows of the positions the schedule leaves free."""
+        free = torch.tensor([q not in forced for q in range(S_last + 1, full_len)], dtype=torch.bool, device=self.dev)
+        return lp_steps[free].t().contiguous()
+
+    @torch.no_grad()
+    def score(self, text_emb: torch.Tensor, tokens, *, motion_score: float = 0.1, num_frames: int = 13, guidance_scale: float = 7.5,
+              temperature: float = 1.0, top_k: int | None = None, top_p: float | None = None):
+        """Teacher forcing in one pass: the log-probability of every id of `tokens` (int [n_visual], what sample() returns for
+        this text length and num_frames) under the distribution sample() with these keywords draws that position from, given the
+        ids before it -> (logprobs fp32 [n_visual] on the device, their sum as a float).  -inf where the filters remove an id.
+        The ids are laid into the free slots of the forced-token schedule; one prefill-form pass (bf16 GEMMs) runs over all
+        full_len - 1 positions of the (cond, uncond) pair, then the final LayerNorm, the fp32 head (ld_llm_head_f32) and ONE
+        ld_llm_token_logprobs launch over the rows that predict a generated position.  Overwrites the runner's KV cache and
+        schedule tables, as a sample() does.  Decode steps compute the same logits through GEMVs, which round differently: the
+        online log-probabilities of sample(return_logprobs=True) agree with score() of its ids to bf16 noise, not bit for bit."""
+        c, dev = self.cfg, self.dev
+        S = text_emb.shape[-2] + 3                          # position of the first START_OF_IFrame (prefix_features)
+        full_len, forced, _, n_visual = forced_token_schedule(c, S, num_frames)
+        if full_len > self.Lmax:
+            raise ValueError(f"LLM score of {num_frames} frames after {text_emb.shape[-2]} text tokens needs {full_len} positions; this runner "
+                             f"was built for {self.Lmax} (max_text / max_frames of LLMRunner)")
+        tok = torch.as_tensor(tokens).reshape(-1)
+        if tok.is_floating_point() or tok.dtype == torch.bool:
+            raise TypeError(f"score: tokens must be integer ids, got {tok.dtype}")
+        if tok.numel() != n_visual:
+            raise ValueError(f"score: {tok.numel()} ids, {num_frames} frames hold {n_visual}")
+        if n_visual and (int(tok.min()) < 0 or int(tok.max()) >= c.visual_vocab):
+            raise ValueError(f"score: ids outside [0, {c.visual_vocab}) (min {int(tok.min())}, max {int(tok.max())})")
+        guided = guidance_scale > 0 and guidance_scale != 1
+        feats, _, _, _, _, _ = self._decode_plan(text_emb, motion_score, num_frames, None, None)
+        # ids of positions S + 1 .. full_len - 1: the schedule's forced tokens with the given ids in the free slots
+        tmpl = torch.tensor([forced.get(q, -1) for q in range(S + 1, full_len)], dtype=torch.int64)
+        slots = (tmpl < 0).to(dev)
+        ids = tmpl.to(dev)
+        ids[slots] = tok.to(dev, torch.int64)
+        feats = torch.cat([feats, self.emb[ids[:-1]].to(BF)[None].expand(2, -1, -1)], 1)      # positions 0 .. full_len - 2
+        m, nr = full_len - 1, full_len - 1 - S              # rows S .. m - 1 predict positions S + 1 .. full_len - 1
+        xv = self._prefill_blocks(feats).view(2, m, c.hidden)
+        lnf = torch.empty(2, nr, c.hidden, device=dev, dtype=torch.float32)
+        for b in range(2):
+            ops.layernorm_bf16_to_f32(xv[b, S:], self.ln_w, self.ln_b, lnf[b], c.ln_eps)
+        logits = torch.empty(2 * nr, c.vocab, device=dev, dtype=torch.float32)
+        ops.llm_head_f32(lnf.view(2 * nr, c.hidden), self.head, logits)
+        lp = torch.empty(nr, device=dev, dtype=torch.float32)
+        ops.llm_token_logprobs(logits[:nr], logits[nr:], ids, lp, guided, guidance_scale, temperature, pos_bias=S,
+                               allowed=self.allowed, forced=self.forced, top_k=top_k, top_p=top_p)
+        out = lp[slots]
+        return out, float(out.double().sum().item())
 
     @torch.no_grad()
     def sample_many(self, text_emb: torch.Tensor, seeds, *, motion_score: float = 0.1, num_frames: int = 13, guidance_scale: float = 7.5,
                     temperature: float = 1.0, use_graph: bool = False, teacher_fed=None, logits_log=None, top_k: int | None = None,
                     top_p: float | None = None, first_frame_tokens: torch.Tensor | None = None, on_segment=None,
-                    segment_tokens: int | None = None, mode: str | None = None, prefix_tokens: torch.Tensor | None = None) -> torch.Tensor:
+                    segment_tokens: int | None = None, mode: str | None = None, prefix_tokens: torch.Tensor | None = None,
+                    return_logprobs: bool = False):
         """len(seeds) samples of ONE prompt from one weight stream: int64 [P, n_visual], row p exactly the ids
         sample(..., seed=seeds[p]) returns.  The samples share the text, the motion score and any first_frame_tokens /
         prefix_tokens, hence the prefill (run once for the (cond, uncond) pair, its KV rows and first logits copied to the other
@@ -478,7 +562,9 @@ class LLMRunner:
         and drawing only its own noise row per step, its own token, KV rows and output row.  A step is one
         ld_llm_decode_forward_pairs (every weight matrix streamed once for all 2P rows) and one ld_llm_sample_advance_pairs.
         The per-operation "chain" form only, no graph capture, no teacher feeding.  Keywords as sample(); logits_log receives
-        [P, vocab] per step; on_segment(s) fires when segment s of EVERY sample is queued (self.m_out_tokens[p])."""
+        [P, vocab] per step; on_segment(s) fires when segment s of EVERY sample is queued (self.m_out_tokens[p]).
+        return_logprobs: -> (ids, logprobs fp32 [P, sampled positions]), row p what sample(seed=seeds[p], return_logprobs=True)
+        returns: one more launch per step (ld_llm_token_logprobs over the P pairs), the ids unchanged."""
         c, dev = self.cfg, self.dev
         seeds = [int(s) for s in seeds]
         P = len(seeds)
@@ -495,10 +581,11 @@ class LLMRunner:
         if not all(seeds):
             raise ValueError("sample_many needs a non-zero seed per sample (sample() draws a zero seed from the shared default generator)")
         if self.max_samples == 1:
-            return self.sample(text_emb, motion_score=motion_score, num_frames=num_frames, guidance_scale=guidance_scale,
-                               temperature=temperature, seed=seeds[0], logits_log=logits_log, top_k=top_k, top_p=top_p,
-                               first_frame_tokens=first_frame_tokens, on_segment=on_segment, segment_tokens=segment_tokens,
-                               mode="chain", prefix_tokens=prefix_tokens)[None]
+            r = self.sample(text_emb, motion_score=motion_score, num_frames=num_frames, guidance_scale=guidance_scale,
+                            temperature=temperature, seed=seeds[0], logits_log=logits_log, top_k=top_k, top_p=top_p,
+                            first_frame_tokens=first_frame_tokens, on_segment=on_segment, segment_tokens=segment_tokens,
+                            mode="chain", prefix_tokens=prefix_tokens, return_logprobs=return_logprobs)
+            return (r[0][None], r[1][None]) if return_logprobs else r[None]
         self._mode = "chain"
         guided = guidance_scale > 0 and guidance_scale != 1
         feats, S_last, full_len, forced, n_visual, n_prefix = self._decode_plan(text_emb, motion_score, num_frames, first_frame_tokens,
@@ -510,7 +597,15 @@ class LLMRunner:
             gens.append(g)
         B = 2 * P
         out_tokens, out_count = self.m_out_tokens[:P], self.m_out_count[:P]
-        sample_and_advance = lambda: self._sample_and_advance_many(gens, guided, guidance_scale, temperature, top_k, top_p, logits_log)
+        lp_steps = None
+        if return_logprobs:
+            lp_steps = torch.empty(full_len - (S_last + 1), P, device=dev, dtype=torch.float32)      # one row per generated position
+            pairs = self.m_logits[:B].view(P, 2 * c.vocab)                                       # row p = (cond, uncond) of sample p
+        def sample_and_advance(k=0):
+            self._sample_and_advance_many(gens, guided, guidance_scale, temperature, top_k, top_p, logits_log)
+            if lp_steps is not None:
+                self._step_logprobs(pairs[:, :c.vocab], pairs[:, c.vocab:], self.m_sampled[:P], self.m_pos[:P], lp_steps[k], guided,
+                                    guidance_scale, temperature, top_k, top_p)
 
         emitted = 0
         def note_position(q):              # the token of position q has just been queued (for every sample)
@@ -536,7 +631,7 @@ class LLMRunner:
         t_enq = time.perf_counter()
         for it in range(steps):
             self._decode_forward_many(P, S_last + 1 + it)
-            sample_and_advance()
+            sample_and_advance(it + 1)
             note_position(S_last + 2 + it)
         self.host_enqueue_s = time.perf_counter() - t_enq
         counts = out_count.tolist()
@@ -545,7 +640,10 @@ class LLMRunner:
         head = [t.reshape(1, -1).to(dev, torch.int64).expand(P, -1) for t in (prefix_tokens, first_frame_tokens) if t is not None]
         if head:
             out = torch.cat(head + [out], 1)
-        return out.clamp(0, c.visual_vocab - 1)
+        out = out.clamp(0, c.visual_vocab - 1)
+        if lp_steps is not None:
+            return out, self._gather_logprobs(lp_steps, S_last, full_len, forced)
+        return out
 
     def _raise_on_wait_timeout(self):
         """The 'fused' and 'chained' forms spin-wait on other workgroups without a cooperative launch; a wait that gives up sets a

@@ -436,6 +436,82 @@ def llm_decode_advance(sampled, forced, pos, token, out_tokens, out_count):
                                             _ptr(out_count), _stream()), "ld_llm_decode_advance")
 
 
+LLM_SAMPLE_MAXV = 4096            # LD_SAMPLE_MAXV
+
+
+def _f32_rows(t, name, V=None):
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name} must be float32, got {t.dtype}")
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{name} must be [rows, cols] with contiguous rows, got shape {tuple(t.shape)} strides {t.stride()}")
+    if V is not None and t.shape[1] != V:
+        raise ValueError(f"{name} has {t.shape[1]} columns, expected {V}")
+
+
+def llm_token_logprobs(cond, uncond, target, logprob, guided, scale, temperature, *, pos=None, pos_stride=0, pos_bias=0,
+                       allowed=None, forced=None, top_k=None, top_p=None, valid=None, cfg_logits=None):
+    """logprob[r] = log-probability of target[r] under the sampler's distribution of logits row r (ld_llm_token_logprobs).
+    cond / uncond: fp32 [n, V] views with any row stride (uncond None: unguided); pos: an int32 device word (row r reads
+    pos[r * pos_stride]) to which pos_bias is added, or None: row r is position pos_bias + r; allowed [n_pos, w] / forced [n_pos]:
+    the schedule tables; target int64 [n], logprob fp32 [n], valid int32 [n] (optional); cfg_logits fp32 [n, V] (optional): the
+    guided logits of the rows that are draws."""
+    for t in (cond, uncond, target, logprob, pos, allowed, forced, valid, cfg_logits):
+        _ptr(t)                                      # CPU tensors are refused before any shape is looked at
+    _f32_rows(cond, "cond")
+    n, V = cond.shape
+    if V > LLM_SAMPLE_MAXV:
+        raise ValueError(f"llm_token_logprobs: V = {V} exceeds LD_SAMPLE_MAXV = {LLM_SAMPLE_MAXV}")
+    if guided and uncond is None:
+        raise ValueError("llm_token_logprobs: guided needs the unconditional rows")
+    if uncond is not None:
+        _f32_rows(uncond, "uncond", V)
+        if uncond.shape[0] != n:
+            raise ValueError(f"uncond has {uncond.shape[0]} rows, cond {n}")
+    if target.dtype != torch.int64 or target.shape != (n,) or not target.is_contiguous():
+        raise ValueError(f"target must be contiguous int64 [{n}], got {target.dtype} {tuple(target.shape)}")
+    if logprob.dtype != torch.float32 or logprob.shape != (n,) or not logprob.is_contiguous():
+        raise ValueError(f"logprob must be contiguous float32 [{n}], got {logprob.dtype} {tuple(logprob.shape)}")
+    if valid is not None and (valid.dtype != torch.int32 or valid.shape != (n,) or not valid.is_contiguous()):
+        raise ValueError(f"valid must be contiguous int32 [{n}], got {valid.dtype} {tuple(valid.shape)}")
+    if pos is not None and (pos.dtype != torch.int32 or pos.numel() < 1 + (n - 1) * pos_stride or not pos.is_contiguous()):
+        raise ValueError(f"pos must be contiguous int32 with {1 + (n - 1) * pos_stride} words, got {pos.dtype} {tuple(pos.shape)}")
+    if cfg_logits is not None:
+        _f32_rows(cfg_logits, "cfg_logits", V)
+        if cfg_logits.shape[0] != n:
+            raise ValueError(f"cfg_logits has {cfg_logits.shape[0]} rows, cond {n}")
+    n_pos = 0
+    if allowed is not None:
+        if allowed.dtype != torch.int32 or allowed.dim() != 2 or allowed.stride(1) != 1:
+            raise ValueError(f"allowed must be int32 [n_pos, 1 + ids], got {allowed.dtype} {tuple(allowed.shape)}")
+        n_pos = allowed.shape[0]
+    if forced is not None:
+        if forced.dtype != torch.int32 or forced.dim() != 1 or not forced.is_contiguous():
+            raise ValueError(f"forced must be contiguous int32 [n_pos], got {forced.dtype} {tuple(forced.shape)}")
+        if allowed is not None and forced.shape[0] != n_pos:
+            raise ValueError(f"forced has {forced.shape[0]} rows, allowed {n_pos}")
+        n_pos = forced.shape[0]
+    check(_lib.load().ld_llm_token_logprobs(_ptr(cond), cond.stride(0), _ptr(uncond), uncond.stride(0) if uncond is not None else 0,
+                                            n, V, int(guided), float(scale), float(temperature), _ptr(pos), int(pos_stride),
+                                            int(pos_bias), _ptr(allowed), allowed.stride(0) if allowed is not None else 0,
+                                            _ptr(forced), n_pos, int(top_k) if top_k is not None else 0,
+                                            float(top_p) if top_p is not None else -1.0, _ptr(target), _ptr(logprob), _ptr(valid),
+                                            _ptr(cfg_logits), cfg_logits.stride(0) if cfg_logits is not None else 0, _stream()), "ld_llm_token_logprobs")
+    return logprob
+
+
+def llm_head_f32(a, w, out):
+    """out[M, N] = a[M, K] @ w[N, K]^T, all fp32 with fp32 accumulation (ld_llm_head_f32); a / w / out may have row strides."""
+    for t in (a, w, out):
+        _ptr(t)
+    _f32_rows(a, "a"); _f32_rows(w, "w", a.shape[1]); _f32_rows(out, "out", w.shape[0])
+    if out.shape[0] != a.shape[0]:
+        raise ValueError(f"out has {out.shape[0]} rows, a {a.shape[0]}")
+    M, K = a.shape
+    check(_lib.load().ld_llm_head_f32(_ptr(a), a.stride(0), _ptr(w), w.stride(0), _ptr(out), out.stride(0), M, w.shape[0], K,
+                                      _stream()), "ld_llm_head_f32")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # normalisation
 # ------------------------------------------------------------------------------------------------

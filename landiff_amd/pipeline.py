@@ -65,6 +65,7 @@ class LanDiffPipeline:
         # the tokenizer's encoder half (optional; nothing else uses it)
         self.theia = theia
         self.timings = {}
+        self.last_candidates = None       # generate_samples(keep=k): every candidate's ids and scores
 
     def _t(self, name, t0):
         torch.cuda.current_stream(self.dev).synchronize()      # (the stage's own stream: an overlapped AR decode keeps running)
@@ -113,18 +114,45 @@ class LanDiffPipeline:
         return self.decode(z, want_float=want_float)
 
     @torch.no_grad()
-    def generate_samples(self, inp: PromptInputs, seeds, want_float: bool = False) -> list:
+    def generate_samples(self, inp: PromptInputs, seeds, keep: int | None = None, want_float: bool = False) -> list:
         """Several candidates of one prompt: result i is identical to `self(replace(inp, seed=seeds[i]))`.  The AR decode of all
         seeds is one LLMRunner.sample_many (the LLM's weights streamed once per step for all of them; needs
-        LanDiffPipeline(..., max_samples >= len(seeds)) and non-zero seeds); detokenize, DiT and VAE then run per sample."""
+        LanDiffPipeline(..., max_samples >= len(seeds)) and non-zero seeds); detokenize, DiT and VAE then run per sample.
+        keep=k (1 <= k <= len(seeds)): best-of-N.  The decode also returns every candidate's total log-probability under the
+        distribution it was sampled from (sample_many(return_logprobs=True)), the candidates are ranked by it (rank_candidates)
+        and detokenize, DiT and VAE run for the k most likely only -> [(seed, score, frames)] in rank order, frames what the
+        keep=None call returns for that seed.  self.last_candidates keeps every candidate: {"seeds", "tokens" [N, n_visual],
+        "scores" [N], "order"}.  Whether likelihood rank tracks visual quality is not measured."""
         from dataclasses import replace
+        seeds = [int(s) for s in seeds]
+        if keep is not None and not 1 <= int(keep) <= len(seeds):
+            raise ValueError(f"generate_samples: keep={keep} outside [1, {len(seeds)}] (the number of seeds)")
+        kw = dict(motion_score=inp.motion_score, num_frames=self.cfg.llm.segment_length, guidance_scale=inp.cfg, temperature=1.0)
         t0 = time.perf_counter()
-        tokens = self.llm.sample_many(inp.llm_text_emb, seeds, motion_score=inp.motion_score, num_frames=self.cfg.llm.segment_length,
-                                      guidance_scale=inp.cfg, temperature=1.0)
+        if keep is None:
+            tokens = self.llm.sample_many(inp.llm_text_emb, seeds, **kw)
+            self._t("llm", t0)
+            return [self.decode(self.generate_latent(tokens[i], replace(inp, seed=s)), want_float=want_float)
+                    for i, s in enumerate(seeds)]
+        tokens, logprobs = self.llm.sample_many(inp.llm_text_emb, seeds, return_logprobs=True, **kw)
+        scores = logprobs.double().sum(1).tolist()
         self._t("llm", t0)
-        return [self.decode(self.generate_latent(tokens[i], replace(inp, seed=int(s))), want_float=want_float)
-                for i, s in enumerate(seeds)]
+        order = rank_candidates(scores)
+        self.last_candidates = {"seeds": seeds, "tokens": tokens.clone(), "scores": scores, "order": order}
+        return [(seeds[i], scores[i], self.decode(self.generate_latent(tokens[i], replace(inp, seed=seeds[i])), want_float=want_float))
+                for i in order[:int(keep)]]
 
+    @torch.no_grad()
+    def score_tokens(self, inp: PromptInputs, tokens: torch.Tensor):
+        """How well the prompt explains a token sequence: LLMRunner.score of `tokens` (one segment's ids, as generate_tokens
+        returns them) under the distribution generate_tokens samples from for this prompt -> (logprobs [n_visual], total)."""
+        return self.llm.score(inp.llm_text_emb, tokens, motion_score=inp.motion_score, num_frames=self.cfg.llm.segment_length,
+                              guidance_scale=inp.cfg, temperature=1.0)
+
+    @torch.no_grad()
+    def score_clip(self, inp: PromptInputs, frames: torch.Tensor):
+        """score_tokens of a real clip's ids (tokenize_frames: needs the Theia extractor, and fails as that method does)."""
+        return self.score_tokens(inp, self.tokenize_frames(frames))
 
     # ---- several prompts on one GPU: prompt-level software pipeline ---------------------------------------
     @torch.no_grad()
@@ -419,6 +447,27 @@ class LanDiffPipeline:
         if self.theia.encoder is None:
             raise ValueError("tokenize_frames: the Theia extractor has no tokenizer encoder attached")
         return self.theia.tokenize_video(select_frames(frames.to(self.dev), self.cfg.tok.temporal))
+
+
+def rank_candidates(scores) -> list:
+    """Indices of `scores` (total log-probabilities) from most to least likely.  Ties go to the lower index; a score that is
+    not finite (-inf: a filter removed one of the ids; NaN) ranks after every finite one, again by index."""
+    import math
+    vals = [float(v) for v in scores]
+    return sorted(range(len(vals)), key=lambda i: (0, -vals[i], i) if math.isfinite(vals[i]) else (1, 0.0, i))
+
+
+def write_scores_json(path: str, seeds, scores, kept) -> list:
+    """<name>_scores.json of infer_video --keep: [{index, seed, logprob, kept}] for every candidate, in candidate order (a score
+    that is not finite is written as null: JSON has no infinity)."""
+    import json
+    import math
+    kept = set(int(i) for i in kept)
+    rows = [{"index": i, "seed": int(s), "logprob": float(v) if math.isfinite(float(v)) else None, "kept": i in kept}
+            for i, (s, v) in enumerate(zip(seeds, scores))]
+    with open(path, "w") as f:
+        json.dump(rows, f, indent=1)
+    return rows
 
 
 def stream_plan(cfg: PipelineConfig, n_chunks: int, prefix_frames: int):
