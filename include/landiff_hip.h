@@ -30,7 +30,9 @@ extern "C" {
  * 9: ld_attn_fwd_bf16_exact was added.  10: ld_attn_last_fallbacks was added.  11: ld_vae_enc_place_input,
  * ld_vae_enc_downsample and ld_vae_posterior were added.  12: ld_vit_patch_rows, ld_vit_embed and ld_vit_tail were added,
  * ld_qkv_split gained mode 2.  13: ld_gemm_route was added.  14: ld_gemv_pairs, ld_llm_decode_forward_pairs and
- * ld_llm_sample_advance_pairs were added.  15: ld_llm_token_logprobs and ld_llm_head_f32 were added. */
+ * ld_llm_sample_advance_pairs were added.  15: ld_llm_token_logprobs and ld_llm_head_f32 were added;
+ * ld_gemv_wide, ld_llm_decode_forward_wide and ld_llm_sample_advance_wide joined later (additions do not change the number: no
+ * existing signature moved). */
 #define LD_ABI_VERSION 15
 
 int ld_version(void);
@@ -283,6 +285,21 @@ int ld_gemv_pairs(const void* x, int64_t ldx, int32_t x_f32, const void* W, cons
                   int64_t B, int64_t N, int64_t K, int32_t in_act, int32_t act, const float* norm_w, float norm_eps,
                   void* stream);
 
+/* The second engine of the batched decode: out[b][n] = epi(sum_k xn[b][k] * W[n][k]) for B = 2P rows, 1 <= P <= LD_LLM_MAX_WIDE,
+ * as a weight-streaming skinny GEMM on v_mfma_f32_32x32x16_bf16 (32 weight rows x the B activation rows as the 32 columns; every
+ * weight byte read once).  Arguments of ld_gemv_pairs; bf16 x / W / out only, with the forms the decode uses: fused RMSNorm of x
+ * (norm_w), the gated form act(W x) * (W2 x), bias, residual add (out == resid allowed).  Rounding points are ld_gemv's (bf16
+ * normalised activations, fp32 accumulation and epilogue, one rounding to bf16 per Linear output); the ORDER of the fp32 sum is
+ * another, so the result is not ld_gemv's bit for bit.  What it guarantees instead: row b's bits depend on row b alone -- not on
+ * B, on b, or on the other rows (the order of summation is a function of K only).
+ * LD_ERR_INVALID: odd B, null pointers, misaligned x / W; LD_ERR_UNSUPPORTED: B > 32, K % 16 != 0, fp32 x / weights / output,
+ * in_act -- nothing is launched. */
+#define LD_LLM_MAX_WIDE 16
+int ld_gemv_wide(const void* x, int64_t ldx, int32_t x_f32, const void* W, const void* W2, int32_t w_f32,
+                 const void* bias, const void* resid, int64_t ldr, void* out, int64_t ldo, int32_t out_f32,
+                 int64_t B, int64_t N, int64_t K, int32_t in_act, int32_t act, const float* norm_w, float norm_eps,
+                 void* stream);
+
 /* RMSNorm (transformer_blocks.py:22-40): bf16 rows [rows][D], fp32 weight, fp32 math, bf16 out. */
 int ld_rmsnorm_bf16(const void* x, const float* w, void* out, int64_t rows, int64_t D, float eps, void* stream);
 
@@ -346,6 +363,17 @@ int ld_llm_decode_forward_pairs(const ld_llm_layer* layers, int64_t n_layers, co
                                 const float* cos_t, const float* sin_t, const float* lnf_w, const float* lnf_b, float* lnf_out,
                                 const float* head_w, float* logits, int64_t B, int64_t hidden, int64_t heads, int64_t mlp,
                                 int64_t vocab, int64_t Lmax, int64_t nsplit, float rms_eps, float ln_eps, void* stream);
+
+/* ld_llm_decode_forward_pairs on the second engine, B = 2P rows, P <= LD_LLM_MAX_WIDE: every block GEMV is ld_gemv_wide, the head
+ * is ld_llm_head_f32; embedding of token[P], key-split attention (nsplit of the two-row runner) and final LayerNorm as in the
+ * _pairs form.  Pair p's logits depend on pair p's token and cache rows alone (not on P or p); they agree with
+ * ld_llm_decode_forward's to bf16 rounding noise, not bit for bit.  LD_ERR_INVALID: odd B, null pointers, head_dim != 128;
+ * LD_ERR_UNSUPPORTED: P > LD_LLM_MAX_WIDE, mlp % 16 != 0 -- checked before anything is launched. */
+int ld_llm_decode_forward_wide(const ld_llm_layer* layers, int64_t n_layers, const float* emb_table, const int64_t* token,
+                               const int32_t* pos, int32_t pos_value, void* x, void* qkv, void* att, void* gate, float* attn_ws,
+                               const float* cos_t, const float* sin_t, const float* lnf_w, const float* lnf_b, float* lnf_out,
+                               const float* head_w, float* logits, int64_t B, int64_t hidden, int64_t heads, int64_t mlp,
+                               int64_t vocab, int64_t Lmax, int64_t nsplit, float rms_eps, float ln_eps, void* stream);
 
 /* ---- Entry points of the VARIANTS build only (landiff_amd/variants/liblandiff_hip_variants.so, built by
  * `LD_BUILD_VARIANTS=1 landiff_amd/csrc/build.sh` with -DLD_VARIANTS): two other forms of the decode step that were built, are
@@ -425,6 +453,14 @@ int ld_llm_sample_advance_pairs(const float* logits, float* probs, float* cfg_lo
                                 int32_t top_k, float top_p, const float* noise, const int32_t* forced, int64_t* token,
                                 int64_t* out_tokens, int64_t out_stride, int32_t* out_count, int64_t* sampled,
                                 const float* emb_table, void* x, int64_t P, int64_t D, void* stream);
+
+/* ld_llm_sample_advance_pairs for the second engine: the same kernel and arguments, 1 <= P <= LD_LLM_MAX_WIDE
+ * (LD_ERR_UNSUPPORTED beyond). */
+int ld_llm_sample_advance_wide(const float* logits, float* probs, float* cfg_logits, int64_t V, int32_t guided, float scale,
+                               float temperature, int32_t* pos, const int32_t* allowed, int64_t allowed_stride,
+                               int32_t top_k, float top_p, const float* noise, const int32_t* forced, int64_t* token,
+                               int64_t* out_tokens, int64_t out_stride, int32_t* out_count, int64_t* sampled,
+                               const float* emb_table, void* x, int64_t P, int64_t D, void* stream);
 
 /* After torch.multinomial: forced-token override (forced[*pos + 1] >= 0), record sampled visual tokens, ++*pos
  * (the elif chain of lm_model.py:455-508). */

@@ -23,8 +23,12 @@ def parse_args(argv=None):
     parser.add_argument("--motion_score", type=float, default=0.1, help="Motion score for the video generation.")
     parser.add_argument("--seed", type=int, default=42, help="Random seed for video generation.")
     parser.add_argument("--num_samples", type=int, default=1,
-                        help="Candidates of the prompt (1-4), seeds --seed .. --seed + N - 1, their tokens from ONE batched AR decode; "
+                        help="Candidates of the prompt (1-4; 1-16 with --decode_engine mfma), seeds --seed .. --seed + N - 1, their tokens from ONE batched AR decode; "
                              "N > 1 writes <save_file_name>_<i>.mp4 / _<i>.npy, each what --seed (seed + i) alone produces.")
+    parser.add_argument("--decode_engine", choices=("gemv", "mfma"), default="gemv",
+                        help="Engine of the batched AR decode (--num_samples N > 1).  gemv: register GEMV, candidate i bit-identical "
+                             "to --seed (seed + i) alone, N <= 4.  mfma: MFMA skinny GEMM, N <= 16; candidate i depends on its own seed "
+                             "alone and equals the single run up to near-ties of the draw.")
     parser.add_argument("--keep", type=int, default=None,
                         help="Best-of-N: with --num_samples N >= K, rank the N candidates by the total log-probability of their "
                              "tokens under the distribution they were sampled from and run the diffusion stage for the K most "
@@ -47,8 +51,9 @@ def parse_args(argv=None):
                         help="Image-guided generation (use_gt_first_frame): a uint8 [H, W, 3] .npy or an image imageio can "
                              "read, tokenized by the Theia extractor; its I-frame tokens start the AR decode.")
     args = parser.parse_args(argv)
-    if not 1 <= args.num_samples <= 4:
-        parser.error("--num_samples must be between 1 and 4")
+    max_n = 16 if args.decode_engine == "mfma" else 4
+    if not 1 <= args.num_samples <= max_n:
+        parser.error(f"--num_samples must be between 1 and {max_n}" + ("" if max_n == 16 else " (1 and 16 with --decode_engine mfma)"))
     if args.num_samples > 1 and args.extend_video:
         parser.error("--num_samples applies to generation from a prompt, not to --extend_video")
     if args.num_samples > 1 and not all(args.seed + i for i in range(args.num_samples)):
@@ -135,13 +140,15 @@ def llm_infer_samples(args):
     the .npy files), or None without --keep: every candidate."""
     llm_model_cfg = build_llm()
     first = first_frame_tokens(args) if args.first_frame else None
-    llm = ArModelInferWrapper(args.llm_ckpt, llm_model_cfg, max_samples=args.num_samples)
+    wide = args.decode_engine == "mfma"
+    llm = ArModelInferWrapper(args.llm_ckpt, llm_model_cfg, max_samples=1 if wide else args.num_samples,
+                              wide_samples=args.num_samples if wide else 0)
     names = sample_names(args)
     task = CodeTask(save_file_name=f"{args.save_file_name}.npy", prompt=args.prompt, seed=args.seed,
                     sample_cfg=ARSampleCfg(temperature=1.0, cfg=args.cfg, motion_score=args.motion_score,
                                            num_frames=llm_model_cfg.segment_length, use_gt_first_frame=first is not None),
                     first_frame_tokens=first)
-    task = llm(task, seeds=[s for s, _ in names], return_logprobs=args.keep is not None)
+    task = llm(task, seeds=[s for s, _ in names], return_logprobs=args.keep is not None, engine=args.decode_engine)
     tokens = task.result
     for row, (_, stem) in zip(tokens, names):
         path = Path(f"{stem}.npy")

@@ -73,7 +73,8 @@ class ArModelInferWrapper(torch.nn.Module):
     text_encoder: optional callable prompts -> list of [n_i, text_dim] states replacing the FLAN-T5-XXL run (pre-computed
     embeddings, as `load_weights=False` does in the reference's text encoder, text_encoder.py:126-131)."""
 
-    def __init__(self, ckpt_path: str, model_cfg: LLMConfig, device="cuda", text_encoder=None, max_samples: int = 1):
+    def __init__(self, ckpt_path: str, model_cfg: LLMConfig, device="cuda", text_encoder=None, max_samples: int = 1,
+                 wide_samples: int = 0):
         super().__init__()
         assert Path(ckpt_path).exists(), f"ckpt_path: {ckpt_path} does not exist"
         assert Path(ckpt_path).suffix == ".safetensors", f"ckpt_path: {ckpt_path} is not a safetensors file"
@@ -87,13 +88,16 @@ class ArModelInferWrapper(torch.nn.Module):
         assert not missing, f"load_state_dict(strict=True): missing keys {missing[:5]}{'...' if len(missing) > 5 else ''}"
         bad = [k for k in want if tuple(sd[k].shape) != want[k]]
         assert not bad, f"checkpoint / model_cfg shape mismatch at {bad[:3]}: {[tuple(sd[k].shape) for k in bad[:3]]} vs {[want[k] for k in bad[:3]]}"
-        self.runner = LLMRunner(sd, model_cfg, self.device_, max_text=model_cfg.max_cond_tokens, max_samples=max_samples)
+        self.runner = LLMRunner(sd, model_cfg, self.device_, max_text=model_cfg.max_cond_tokens, max_samples=max_samples,
+                                wide_samples=wide_samples)
 
     @torch.no_grad()
-    def forward(self, code_task: CodeTask, seeds=None, return_logprobs: bool = False) -> CodeTask:
+    def forward(self, code_task: CodeTask, seeds=None, return_logprobs: bool = False, engine: str = "gemv") -> CodeTask:
         """seeds (optional, non-zero ints, at most the wrapper's max_samples): that many samples of the prompt from one batched
         decode (LLMRunner.sample_many) -- .result is then LongTensor [len(seeds), n_visual], row i what seed seeds[i] alone gives.
-        return_logprobs (with seeds): .logprobs receives the sampled ids' log-probabilities; .result is unchanged by it."""
+        return_logprobs (with seeds): .logprobs receives the sampled ids' log-probabilities; .result is unchanged by it.
+        engine (with seeds): "gemv", or "mfma" for up to the wrapper's wide_samples (<= 16) seeds on the MFMA decode engine
+        (LLMRunner.sample_many(engine="mfma"): row i then depends on seeds[i] alone, and equals the single decode up to near-ties)."""
         if return_logprobs and seeds is None:
             raise ValueError("return_logprobs scores the candidates of a batched decode: give seeds")
         sc, c = code_task.sample_cfg, self.config
@@ -123,7 +127,7 @@ class ArModelInferWrapper(torch.nn.Module):
                 raise ValueError("teacher_forcing decodes one token stream: no seeds")
             tokens = self.runner.sample_many(text, seeds, motion_score=sc.motion_score, num_frames=sc.num_frames,
                                              guidance_scale=sc.cfg, temperature=sc.temperature, top_k=sc.top_k, top_p=sc.top_p,
-                                             first_frame_tokens=first, return_logprobs=return_logprobs)
+                                             first_frame_tokens=first, return_logprobs=return_logprobs, engine=engine)
             if return_logprobs:
                 tokens, logprobs = tokens
                 code_task.logprobs = logprobs.cpu()

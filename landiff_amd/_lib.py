@@ -71,6 +71,7 @@ SIGNATURES: dict[str, list] = {
     "ld_attn_queue_poke": [I32, c_uint32, P],
     "ld_gemv": [P, I64, I32, P, P, I32, P, P, I64, P, I64, I32, I64, I64, I64, I32, I32, P, c_float, P],
     "ld_gemv_pairs": [P, I64, I32, P, P, I32, P, P, I64, P, I64, I32, I64, I64, I64, I32, I32, P, c_float, P],
+    "ld_gemv_wide": [P, I64, I32, P, P, I32, P, P, I64, P, I64, I32, I64, I64, I64, I32, I32, P, c_float, P],
     "ld_rmsnorm_bf16": [P, P, P, I64, I64, c_float, P],
     "ld_layernorm_bf16_to_f32": [P, I64, P, P, P, I64, I64, c_float, P],
     "ld_llm_rope_append": [P, P, P, P, P, P, P, I64, I64, I64, I64, P],
@@ -89,11 +90,15 @@ SIGNATURES: dict[str, list] = {
                               c_float, c_float, P],
     "ld_llm_decode_forward_pairs": [P, I64, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64,
                                     c_float, c_float, P],
+    "ld_llm_decode_forward_wide": [P, I64, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64,
+                                   c_float, c_float, P],
     "ld_llm_logits_to_probs": [P, P, P, I64, I32, c_float, c_float, P, P, I64, I32, c_float, P],
     "ld_llm_decode_advance": [P, P, P, P, P, P, P],
     "ld_llm_sample_advance": [P, P, P, I64, I32, c_float, c_float, P, P, I64, I32, c_float, P, P, P, P, P, P, P, P, I64, I64, P],
     "ld_llm_sample_advance_pairs": [P, P, P, I64, I32, c_float, c_float, P, P, I64, I32, c_float, P, P, P, P, I64, P, P, P, P, I64, I64,
                                     P],
+    "ld_llm_sample_advance_wide": [P, P, P, I64, I32, c_float, c_float, P, P, I64, I32, c_float, P, P, P, P, I64, P, P, P, P, I64, I64,
+                                   P],
     "ld_llm_token_logprobs": [P, I64, P, I64, I64, I64, I32, c_float, c_float, P, I64, I32, P, I64, P, I64, I32, c_float, P, P, P, P,
                               I64, P],
     "ld_llm_head_f32": [P, I64, P, I64, P, I64, I64, I64, I64, P],

@@ -34,7 +34,8 @@ build_lib() {   # $1 = object dir, $2 = output, $3 = extra flags, $4.. = sources
       # loop) the prefill's rotated q / k came out one bf16 step off in ~1e-5 .. 1e-3 of the even elements, and the decode sampled
       # other tokens (tools/llm_race_probe2.py, profiles/r05_llm_packed_f32_under_coresidency.txt).  Scalar v_mul / v_sub / v_add: clean.
       # ld_llm_score.hip restates the sampling kernel's distribution: its guided logits must be the same bits, hence the same flags.
-      case $s in ld_llm.hip|ld_llm_fused.hip|ld_llm_score.hip) extra="-ffp-contract=off -fno-slp-vectorize";; esac
+      # ld_llm_wide.hip restates ld_gemv_kernel's RMSNorm staging and epilogue: the same rounding points need the same unfused mul / add.
+      case $s in ld_llm.hip|ld_llm_fused.hip|ld_llm_score.hip|ld_llm_wide.hip) extra="-ffp-contract=off -fno-slp-vectorize";; esac
       hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wno-unused-result $extra $flags -c "$s" -o "$o" &
       pids+=($!)
     fi

@@ -1239,6 +1239,58 @@ LD_API int ld_llm_decode_forward_pairs(const ld_llm_layer* layers, int64_t n_lay
                        nullptr, 0.f, stream);
 }
 
+// ld_llm_decode_forward_pairs on the second engine: every block GEMV is ld_gemv_wide (ld_llm_wide.hip: the 2P rows are the columns of
+// an MFMA, every weight matrix streamed once for up to 16 samples), the head is ld_llm_head_f32 (a sequential fp32 dot per element,
+// whatever M is); the embedding of token[P], the key-split attention over (B * heads, split) and the final LayerNorm are the launches
+// of the _pairs form.  What pair p gets depends on its own rows alone: not on P, not on the pair's index.
+LD_API int ld_llm_decode_forward_wide(const ld_llm_layer* layers, int64_t n_layers, const float* emb_table, const int64_t* token,
+                                      const int32_t* pos, int32_t pos_value, void* x, void* qkv, void* att, void* gate, float* attn_ws,
+                                      const float* cos_t, const float* sin_t, const float* lnf_w, const float* lnf_b,
+                                      float* lnf_out, const float* head_w, float* logits, int64_t B, int64_t hidden,
+                                      int64_t heads, int64_t mlp, int64_t vocab, int64_t Lmax, int64_t nsplit, float rms_eps,
+                                      float ln_eps, void* stream) {
+  LD_REQUIRE(layers && n_layers > 0 && (emb_table == nullptr || token) && pos && x && qkv && att && gate && attn_ws && cos_t && sin_t &&
+             lnf_w && lnf_b && lnf_out && head_w && logits, "ld_llm_decode_forward_wide: null pointer");
+  LD_REQUIRE(B >= 2 && B % 2 == 0, "ld_llm_decode_forward_wide: %ld rows are not (cond, uncond) pairs", (long)B);
+  if (B > 2 * LD_LLM_MAX_WIDE)
+    return ld_set_error(LD_ERR_UNSUPPORTED, "ld_llm_decode_forward_wide: %ld samples, at most %d", (long)(B / 2), LD_LLM_MAX_WIDE);
+  LD_REQUIRE(hidden == heads * 128, "ld_llm_decode_forward_wide: head_dim must be 128 (hidden=%ld heads=%ld)", (long)hidden, (long)heads);
+  LD_REQUIRE(mlp >= 16 && vocab >= 1, "ld_llm_decode_forward_wide: mlp=%ld vocab=%ld", (long)mlp, (long)vocab);
+  if (mlp % 16 != 0) return ld_set_error(LD_ERR_UNSUPPORTED, "ld_llm_decode_forward_wide: mlp=%ld is not a multiple of 16", (long)mlp);
+  LD_REQUIRE(nsplit > 1 && (Lmax + nsplit - 1) / nsplit <= 16 * KV_MAXIT,
+             "ld_llm_decode_forward_wide: the decode path is the key-split attention (nsplit > 1, <= 256 keys per split)");
+  LD_REQUIRE(pos_value < Lmax, "ld_llm_decode_forward_wide: pos_value %d outside [0, Lmax)", (int)pos_value);
+  for (int64_t i = 0; i < n_layers; ++i) {
+    const ld_llm_layer& w = layers[i];
+    LD_REQUIRE(w.wqkv && w.wo && w.w1 && w.w3 && w.w2 && w.n0 && w.n1 && w.k_cache && w.v_cache,
+               "ld_llm_decode_forward_wide: layer %ld has a null pointer", (long)i);
+  }
+  int rc = 0;
+  if (emb_table) {
+    hipLaunchKernelGGL(ld_embed_pairs_kernel, dim3((B * hidden + 255) / 256), dim3(256), 0, (hipStream_t)stream, emb_table,
+                       (const long*)token, (bf16_t*)x, (int)B, (int)hidden);
+    rc = ld_check_launch("ld_llm_decode_forward_wide(embed)");
+  }
+  for (int64_t i = 0; i < n_layers && rc == 0; ++i) {
+    const ld_llm_layer& w = layers[i];
+    rc = ld_gemv_wide(x, hidden, 0, w.wqkv, nullptr, 0, nullptr, nullptr, 0, qkv, 3 * hidden, 0, B, 3 * hidden, hidden, 0, 0,
+                      w.n0, rms_eps, stream);
+    if (rc) break;
+    rc = kv_attn_impl(nullptr, w.k_cache, w.v_cache, pos, pos_value, att, B, 1, heads, Lmax, attn_ws, nsplit, qkv, cos_t, sin_t, stream);
+    if (rc) break;
+    rc = ld_gemv_wide(att, hidden, 0, w.wo, nullptr, 0, nullptr, x, hidden, x, hidden, 0, B, hidden, hidden, 0, 0, nullptr, 0.f, stream);
+    if (rc) break;
+    rc = ld_gemv_wide(x, hidden, 0, w.w1, w.w3, 0, nullptr, nullptr, 0, gate, mlp, 0, B, mlp, hidden, 0, LD_ACT_GELU_TANH,
+                      w.n1, rms_eps, stream);
+    if (rc) break;
+    rc = ld_gemv_wide(gate, mlp, 0, w.w2, nullptr, 0, nullptr, x, hidden, x, hidden, 0, B, hidden, mlp, 0, 0, nullptr, 0.f, stream);
+  }
+  if (rc) return rc;
+  rc = ld_layernorm_bf16_to_f32(x, hidden, lnf_w, lnf_b, lnf_out, B, hidden, ln_eps, stream);
+  if (rc) return rc;
+  return ld_llm_head_f32(lnf_out, hidden, head_w, hidden, logits, vocab, B, vocab, hidden, stream);
+}
+
 #ifdef LD_VARIANTS   // the dependent-launch form of a decode step: measured slower, only in the variants build
 namespace {
 // the register GEMV in its dependent-launch form (B = 2): variant choice of launch_gemv_b, <= 128 registers, <= 512 workgroups
@@ -1358,6 +1410,24 @@ LD_API int ld_llm_sample_advance_pairs(const float* logits, float* probs, float*
                      (int)V, guided, scale, temperature, (const int*)pos, (const int*)allowed, (int)allowed_stride,
                      (int)top_k, top_p, sa);
   return ld_check_launch("ld_llm_sample_advance_pairs");
+}
+
+// ld_llm_sample_advance_pairs with the cap of the second engine (LD_LLM_MAX_WIDE samples): the same kernel, P workgroups.
+LD_API int ld_llm_sample_advance_wide(const float* logits, float* probs, float* cfg_logits, int64_t V, int32_t guided, float scale,
+                                      float temperature, int32_t* pos, const int32_t* allowed, int64_t allowed_stride,
+                                      int32_t top_k, float top_p, const float* noise, const int32_t* forced, int64_t* token,
+                                      int64_t* out_tokens, int64_t out_stride, int32_t* out_count, int64_t* sampled,
+                                      const float* emb_table, void* x, int64_t P, int64_t D, void* stream) {
+  LD_REQUIRE(logits && V > 0 && V <= LD_SAMPLE_MAXV, "ld_llm_sample_advance_wide: bad args (V=%ld, max %d)", (long)V, LD_SAMPLE_MAXV);
+  LD_REQUIRE(pos && noise && forced && token && out_tokens && out_count && emb_table && x, "ld_llm_sample_advance_wide: null pointer");
+  LD_REQUIRE(P >= 1 && D >= 1 && out_stride >= 0, "ld_llm_sample_advance_wide: P=%ld D=%ld out_stride=%ld", (long)P, (long)D, (long)out_stride);
+  if (P > LD_LLM_MAX_WIDE) return ld_set_error(LD_ERR_UNSUPPORTED, "ld_llm_sample_advance_wide: %ld samples, at most %d", (long)P, LD_LLM_MAX_WIDE);
+  SampleArgs sa{noise, (const int*)forced, (int*)pos, (long*)token, (long*)out_tokens, (int*)out_count, (long*)sampled,
+                emb_table, (bf16_t*)x, 2, (int)D, (long)out_stride};
+  hipLaunchKernelGGL(ld_logits_to_probs_kernel<true>, dim3((unsigned)P), dim3(1024), 0, (hipStream_t)stream, logits, probs, cfg_logits,
+                     (int)V, guided, scale, temperature, (const int*)pos, (const int*)allowed, (int)allowed_stride,
+                     (int)top_k, top_p, sa);
+  return ld_check_launch("ld_llm_sample_advance_wide");
 }
 
 LD_API int ld_llm_decode_advance(const int64_t* sampled, const int32_t* forced, int32_t* pos, int64_t* token,

@@ -68,11 +68,19 @@ def forced_token_schedule(cfg: LLMConfig, S: int, num_frames: int):
 class LLMRunner:
     B = 2   # (cond, uncond)
 
-    def __init__(self, sd: dict, cfg: LLMConfig, device, max_text: int = 512, max_frames: int = 13, max_samples: int = 1):
+    def __init__(self, sd: dict, cfg: LLMConfig, device, max_text: int = 512, max_frames: int = 13, max_samples: int = 1,
+                 wide_samples: int = 0):
         """max_samples > 1: sample_many() decodes up to that many samples of one prompt side by side (KV cache and step buffers
-        for 2 * max_samples rows; sample() keeps working on the first pair of them).  1: nothing extra is allocated."""
+        for 2 * max_samples rows; sample() keeps working on the first pair of them).  1: nothing extra is allocated.
+        wide_samples (0..16, independent of max_samples): sample_many(engine="mfma") decodes up to that many samples on the MFMA
+        engine (ld_gemv_wide): KV cache and step buffers for 2 * wide_samples rows, rows 0-1 being the cache sample() and the
+        prefill use.  At full size (24 layers, hidden 2048, the default max_text / max_frames) a row's K and V cost ~0.36 GB:
+        ~11.5 GB at wide_samples=16.  The two limits share one allocation of 2 * max(max_samples, wide_samples) rows."""
         assert 1 <= max_samples <= ops.LLM_MAX_PAIRS, f"max_samples {max_samples} outside [1, {ops.LLM_MAX_PAIRS}]"
-        self.cfg, self.dev, self.max_samples = cfg, device, max_samples
+        assert 0 <= wide_samples <= ops.LLM_MAX_WIDE, f"wide_samples {wide_samples} outside [0, {ops.LLM_MAX_WIDE}]"
+        self.cfg, self.dev, self.max_samples, self.wide_samples = cfg, device, max_samples, wide_samples
+        n_rows = max(max_samples, wide_samples)            # samples the m_* buffers and the KV cache hold
+        multi = max_samples > 1 or wide_samples >= 1       # sample_many has buffers of its own
         c = cfg
         g = lambda k, dt=BF: sd[k].detach().to(device=device, dtype=dt).contiguous()
         self.blocks = []
@@ -99,13 +107,13 @@ class LLMRunner:
         self.cos, self.sin = cis.real.contiguous().to(device), cis.imag.contiguous().to(device)
         # state in HBM
         B, H, D = self.B, c.heads, c.head_dim
-        if max_samples == 1:
+        if not multi:
             self.kc = [torch.zeros(B, self.Lmax, H, D, device=device, dtype=BF) for _ in range(c.num_layers)]
             self.vc = [torch.zeros(B, self.Lmax, H, D, device=device, dtype=BF) for _ in range(c.num_layers)]
         else:
             # rows (2p, 2p+1) = sample p; the first pair is the cache sample() and the prefill use (same address, same layout)
-            self.kc_all = [torch.zeros(B * max_samples, self.Lmax, H, D, device=device, dtype=BF) for _ in range(c.num_layers)]
-            self.vc_all = [torch.zeros(B * max_samples, self.Lmax, H, D, device=device, dtype=BF) for _ in range(c.num_layers)]
+            self.kc_all = [torch.zeros(B * n_rows, self.Lmax, H, D, device=device, dtype=BF) for _ in range(c.num_layers)]
+            self.vc_all = [torch.zeros(B * n_rows, self.Lmax, H, D, device=device, dtype=BF) for _ in range(c.num_layers)]
             self.kc, self.vc = [t[:B] for t in self.kc_all], [t[:B] for t in self.vc_all]
         self.pos = torch.zeros(1, device=device, dtype=torch.int32)
         self.pos0 = torch.zeros(1, device=device, dtype=torch.int32)
@@ -135,8 +143,8 @@ class LLMRunner:
         self.top_k, self.top_p = None, None
         # partial results [B*H][nsplit][130] + B*H arrival counters (zero between launches: the last split to arrive merges)
         self.attn_ws = torch.zeros(B * H * (self.nsplit * 130 + 1), device=device, dtype=torch.float32)
-        if max_samples > 1:
-            Pm, Bm = max_samples, B * max_samples
+        if multi:
+            Pm, Bm = n_rows, B * n_rows
             self.m_x, self.m_qkv, self.m_att, self.m_gate = e(Bm, c.hidden), e(Bm, 3 * c.hidden), e(Bm, c.hidden), e(Bm, c.mlp)
             self.m_lnf, self.m_logits = e(Bm, c.hidden, dt=torch.float32), e(Bm, c.vocab, dt=torch.float32)
             self.m_cfg_logits, self.m_noise = e(Pm, c.vocab, dt=torch.float32), e(Pm, c.vocab, dt=torch.float32)
@@ -305,26 +313,30 @@ class LLMRunner:
         torch.multinomial(self.probs, num_samples=1, generator=generator, out=self.sampled)
         ops.llm_decode_advance(self.sampled, self.forced, self.pos, self.token, self.out_tokens, self.out_count)
 
-    def _decode_forward_many(self, P: int, pos_value: int):
+    def _decode_forward_many(self, P: int, pos_value: int, wide: bool = False, embed: bool = False):
         """_decode_forward for P samples (rows (2p, 2p+1) of the m_* buffers): the embedding rows of their tokens, left in m_x by
-        the sampling launch, at position pos_value -> logits [2P, V]; one native call, every weight matrix streamed once."""
+        the sampling launch, at position pos_value -> logits [2P, V]; one native call, every weight matrix streamed once.
+        wide: the MFMA engine (ld_llm_decode_forward_wide).  embed: m_token was written by the host (teacher feeding): the step
+        embeds it from the table instead of trusting m_x."""
         c, B = self.cfg, 2 * P
         if self._layer_table is None:
             self._layer_table = ops.llm_layer_table(self.blocks, self.kc, self.vc)      # (kc[i] is the head of kc_all[i]: same address)
-        ops.llm_decode_forward_pairs(self._layer_table, None, self.m_token[:P], self.m_pos[:P], self.m_x[:B], self.m_qkv[:B], self.m_att[:B],
-                                     self.m_gate[:B], self.m_attn_ws, self.cos, self.sin, self.ln_w, self.ln_b, self.m_lnf[:B], self.head,
-                                     self.m_logits[:B], c.heads, self.Lmax, self.nsplit, c.rms_eps, c.ln_eps, pos_value=pos_value)
+        forward = ops.llm_decode_forward_wide if wide else ops.llm_decode_forward_pairs
+        forward(self._layer_table, self.emb if embed else None, self.m_token[:P], self.m_pos[:P], self.m_x[:B], self.m_qkv[:B], self.m_att[:B],
+                self.m_gate[:B], self.m_attn_ws, self.cos, self.sin, self.ln_w, self.ln_b, self.m_lnf[:B], self.head,
+                self.m_logits[:B], c.heads, self.Lmax, self.nsplit, c.rms_eps, c.ln_eps, pos_value=pos_value)
 
-    def _sample_and_advance_many(self, gens, guided, scale, temperature, top_k=None, top_p=None, logits_log=None):
+    def _sample_and_advance_many(self, gens, guided, scale, temperature, top_k=None, top_p=None, logits_log=None, wide=False):
         """_sample_and_advance for len(gens) samples: generator p draws the [vocab] Exp(1) row sample() draws from it at this
         step (and nothing else), then one launch samples, records and advances every sample and embeds its next token."""
         P = len(gens)
         noise, cfg_logits = self.m_noise[:P], self.m_cfg_logits[:P]
         for p in range(P):
             noise[p].exponential_(1.0, generator=gens[p])
-        ops.llm_sample_advance_pairs(self.m_logits[:2 * P], None, cfg_logits, guided, scale, temperature, self.m_pos[:P], self.allowed, noise,
-                                     self.forced, self.m_token[:P], self.m_out_tokens[:P], self.m_out_count[:P], self.m_sampled[:P],
-                                     self.emb, self.m_x[:2 * P], top_k=top_k, top_p=top_p)
+        advance = ops.llm_sample_advance_wide if wide else ops.llm_sample_advance_pairs
+        advance(self.m_logits[:2 * P], None, cfg_logits, guided, scale, temperature, self.m_pos[:P], self.allowed, noise,
+                self.forced, self.m_token[:P], self.m_out_tokens[:P], self.m_out_count[:P], self.m_sampled[:P],
+                self.emb, self.m_x[:2 * P], top_k=top_k, top_p=top_p)
         if logits_log is not None:
             logits_log.append(cfg_logits.clone())
 
@@ -554,7 +566,7 @@ class LLMRunner:
                     temperature: float = 1.0, use_graph: bool = False, teacher_fed=None, logits_log=None, top_k: int | None = None,
                     top_p: float | None = None, first_frame_tokens: torch.Tensor | None = None, on_segment=None,
                     segment_tokens: int | None = None, mode: str | None = None, prefix_tokens: torch.Tensor | None = None,
-                    return_logprobs: bool = False):
+                    return_logprobs: bool = False, engine: str = "gemv"):
         """len(seeds) samples of ONE prompt from one weight stream: int64 [P, n_visual], row p exactly the ids
         sample(..., seed=seeds[p]) returns.  The samples share the text, the motion score and any first_frame_tokens /
         prefix_tokens, hence the prefill (run once for the (cond, uncond) pair, its KV rows and first logits copied to the other
@@ -564,23 +576,48 @@ class LLMRunner:
         The per-operation "chain" form only, no graph capture, no teacher feeding.  Keywords as sample(); logits_log receives
         [P, vocab] per step; on_segment(s) fires when segment s of EVERY sample is queued (self.m_out_tokens[p]).
         return_logprobs: -> (ids, logprobs fp32 [P, sampled positions]), row p what sample(seed=seeds[p], return_logprobs=True)
-        returns: one more launch per step (ld_llm_token_logprobs over the P pairs), the ids unchanged."""
+        returns: one more launch per step (ld_llm_token_logprobs over the P pairs), the ids unchanged.
+        engine="mfma" (opt-in; "gemv" is everything above, launch for launch): up to wide_samples (<= 16) samples per weight
+        stream on the MFMA engine -- a step is one ld_llm_decode_forward_wide (block GEMVs: ld_gemv_wide; head: ld_llm_head_f32)
+        and one ld_llm_sample_advance_wide.  An MFMA sums K in another order than the register GEMV, so row p is NOT bit for
+        bit sample(seed=seeds[p]).  Its contract: (1) batch invariance, bit for bit -- what seed s gets depends on s and the
+        prompt alone, not on P, its row or the other seeds; (2) the GEMV path's rounding points; (3) the ids equal those of
+        sample(seed=s) up to the first step at which a rounding difference of the logits flips a near-tie of the draw
+        (tests/flip_audit.py).  teacher_fed (this engine only): int64 [steps] (every sample) or [P, steps]: the host writes the
+        fed token of each step into every sample's token word and the step re-embeds it from the table."""
         c, dev = self.cfg, self.dev
         seeds = [int(s) for s in seeds]
         P = len(seeds)
+        if engine not in ("gemv", "mfma"):
+            raise ValueError(f"sample_many: unknown engine {engine!r} ('gemv': register GEMV, bit-identical to sample(); 'mfma': "
+                             "ld_gemv_wide, up to 16 samples)")
+        wide = engine == "mfma"
         mode = "chain" if mode is None else mode
         if mode != "chain":
             raise ValueError(f"sample_many: decode mode {mode!r} is not supported (the batched decode is the per-operation 'chain' form)")
         if use_graph:
             raise ValueError("sample_many: graph capture is not supported")
-        if teacher_fed is not None:
+        if teacher_fed is not None and not wide:
             raise ValueError("sample_many: teacher_fed is not supported (teacher forcing has one token stream)")
-        if not 1 <= P <= self.max_samples:
+        if wide and not 1 <= P <= self.wide_samples:
+            raise ValueError(f"sample_many(engine='mfma'): {P} seeds, this runner was built with wide_samples={self.wide_samples} "
+                             f"(LLMRunner(..., wide_samples=N), N <= {ops.LLM_MAX_WIDE})")
+        if not wide and not 1 <= P <= self.max_samples:
             raise ValueError(f"sample_many: {P} seeds, this runner was built with max_samples={self.max_samples} "
                              f"(LLMRunner(..., max_samples=N), N <= {ops.LLM_MAX_PAIRS})")
         if not all(seeds):
             raise ValueError("sample_many needs a non-zero seed per sample (sample() draws a zero seed from the shared default generator)")
-        if self.max_samples == 1:
+        if return_logprobs and teacher_fed is not None:
+            raise ValueError("sample_many: return_logprobs scores draws; a teacher-fed decode has none")
+        fed = None
+        if teacher_fed is not None:
+            fed = torch.as_tensor(teacher_fed).to(dev, torch.int64)
+            if fed.dim() == 1:
+                fed = fed[None].expand(P, -1)
+            if fed.dim() != 2 or fed.shape[0] != P:
+                raise ValueError(f"sample_many: teacher_fed must be int64 [steps] or [{P}, steps], got {tuple(fed.shape)}")
+            fed = fed.t().contiguous()                      # [steps, P]: one row per step
+        if not wide and self.max_samples == 1:
             r = self.sample(text_emb, motion_score=motion_score, num_frames=num_frames, guidance_scale=guidance_scale,
                             temperature=temperature, seed=seeds[0], logits_log=logits_log, top_k=top_k, top_p=top_p,
                             first_frame_tokens=first_frame_tokens, on_segment=on_segment, segment_tokens=segment_tokens,
@@ -602,7 +639,7 @@ class LLMRunner:
             lp_steps = torch.empty(full_len - (S_last + 1), P, device=dev, dtype=torch.float32)      # one row per generated position
             pairs = self.m_logits[:B].view(P, 2 * c.vocab)                                       # row p = (cond, uncond) of sample p
         def sample_and_advance(k=0):
-            self._sample_and_advance_many(gens, guided, guidance_scale, temperature, top_k, top_p, logits_log)
+            self._sample_and_advance_many(gens, guided, guidance_scale, temperature, top_k, top_p, logits_log, wide)
             if lp_steps is not None:
                 self._step_logprobs(pairs[:, :c.vocab], pairs[:, c.vocab:], self.m_sampled[:P], self.m_pos[:P], lp_steps[k], guided,
                                     guidance_scale, temperature, top_k, top_p)
@@ -629,8 +666,12 @@ class LLMRunner:
         note_position(S_last + 1)
         steps = full_len - (S_last + 1) - 1
         t_enq = time.perf_counter()
+        if fed is not None and fed.shape[0] < steps:
+            raise ValueError(f"sample_many: teacher_fed holds {fed.shape[0]} steps, the decode runs {steps}")
         for it in range(steps):
-            self._decode_forward_many(P, S_last + 1 + it)
+            if fed is not None:
+                self.m_token[:P].copy_(fed[it])
+            self._decode_forward_many(P, S_last + 1 + it, wide, embed=fed is not None)
             sample_and_advance(it + 1)
             note_position(S_last + 2 + it)
         self.host_enqueue_s = time.perf_counter() - t_enq

@@ -259,6 +259,20 @@ def gemv_pairs(x, w, out, *, w2=None, bias=None, resid=None, in_act=None, act=No
     return out
 
 
+def gemv_wide(x, w, out, *, w2=None, bias=None, resid=None, in_act=None, act=None, norm_w=None, norm_eps=0.0):
+    """gemv for B = 2 P rows, P <= LLM_MAX_WIDE, on the MFMA engine (ld_gemv_wide): bf16 only; a row's bits depend on that row
+    alone (not on B or its index); same rounding points as gemv, another order of the fp32 sum."""
+    B, K = x.shape
+    N = w.shape[0]
+    assert w.shape[1] == K and out.shape == (B, N) and x.stride(1) == 1 and out.stride(1) == 1 and w.is_contiguous()
+    check(_lib.load().ld_gemv_wide(_ptr(x), x.stride(0), int(x.dtype == torch.float32), _ptr(w), _ptr(w2),
+                                   int(w.dtype == torch.float32), _ptr(bias), _ptr(resid),
+                                   resid.stride(0) if resid is not None else 0, _ptr(out), out.stride(0),
+                                   int(out.dtype == torch.float32), B, N, K, ACT[in_act], ACT[act], _ptr(norm_w), float(norm_eps),
+                                   _stream()), "ld_gemv_wide")
+    return out
+
+
 def rmsnorm(x, w, out, eps):
     rows, D = x.shape
     _bf16(x, "x")
@@ -341,6 +355,25 @@ def llm_decode_forward_pairs(table, emb, token, pos, x, qkv, att, gate, attn_ws,
                                                   _ptr(lnf_w), _ptr(lnf_b), _ptr(lnf_out), _ptr(head), _ptr(logits), B, hidden,
                                                   heads, gate.shape[1], logits.shape[1], Lmax, nsplit, float(rms_eps),
                                                   float(ln_eps), _stream()), "ld_llm_decode_forward_pairs")
+
+
+LLM_MAX_WIDE = 16                  # LD_LLM_MAX_WIDE
+
+
+def llm_decode_forward_wide(table, emb, token, pos, x, qkv, att, gate, attn_ws, cos_t, sin_t, lnf_w, lnf_b, lnf_out, head, logits,
+                            heads, Lmax, nsplit, rms_eps, ln_eps, pos_value=-1):
+    """llm_decode_forward_pairs on the MFMA engine, P <= LLM_MAX_WIDE samples (ld_llm_decode_forward_wide): the block GEMVs are
+    ld_gemv_wide, the head ld_llm_head_f32; pair p's logits depend on pair p alone."""
+    B, hidden = x.shape
+    for t in (x, qkv, att, gate, lnf_out, logits, head):
+        assert t.is_contiguous()
+    need = B * heads * (nsplit * 130 + 1)
+    assert attn_ws.dtype == torch.float32 and attn_ws.numel() >= need, f"attn_ws: {attn_ws.numel()} words, needs {need}"
+    check(_lib.load().ld_llm_decode_forward_wide(ctypes.addressof(table), len(table), _ptr(emb), _ptr(token), _ptr(pos), int(pos_value),
+                                                 _ptr(x), _ptr(qkv), _ptr(att), _ptr(gate), _ptr(attn_ws), _ptr(cos_t), _ptr(sin_t),
+                                                 _ptr(lnf_w), _ptr(lnf_b), _ptr(lnf_out), _ptr(head), _ptr(logits), B, hidden,
+                                                 heads, gate.shape[1], logits.shape[1], Lmax, nsplit, float(rms_eps),
+                                                 float(ln_eps), _stream()), "ld_llm_decode_forward_wide")
 
 
 LLM_FUSED_CTL_WORDS = 512          # LD_LLM_FUSED_CTL_WORDS
@@ -429,6 +462,25 @@ def llm_sample_advance_pairs(logits, probs, cfg_logits, guided, scale, temperatu
                                                   float(top_p) if top_p is not None else -1.0, _ptr(noise), _ptr(forced),
                                                   _ptr(token), _ptr(out_tokens), out_tokens.stride(0), _ptr(out_count), _ptr(sampled),
                                                   _ptr(emb), _ptr(x), P, D, _stream()), "ld_llm_sample_advance_pairs")
+
+
+def llm_sample_advance_wide(logits, probs, cfg_logits, guided, scale, temperature, pos, allowed, noise, forced, token, out_tokens,
+                            out_count, sampled, emb, x, top_k=None, top_p=None):
+    """llm_sample_advance_pairs with the MFMA engine's cap, P <= LLM_MAX_WIDE (ld_llm_sample_advance_wide): the same kernel."""
+    V = logits.shape[-1]
+    P = noise.shape[0]
+    D = x.shape[1]
+    assert logits.shape[0] == 2 * P and x.shape[0] == 2 * P and out_tokens.shape[0] == P and out_tokens.stride(1) == 1
+    assert pos.numel() == P and token.numel() == P and out_count.numel() == P and (sampled is None or sampled.numel() == P)
+    for t in (logits, noise, x, probs, cfg_logits):
+        assert t is None or t.is_contiguous()
+    check(_lib.load().ld_llm_sample_advance_wide(_ptr(logits), _ptr(probs), _ptr(cfg_logits), V, int(guided), float(scale),
+                                                 float(temperature), _ptr(pos), _ptr(allowed),
+                                                 allowed.stride(0) if allowed is not None else 0,
+                                                 int(top_k) if top_k is not None else 0,
+                                                 float(top_p) if top_p is not None else -1.0, _ptr(noise), _ptr(forced),
+                                                 _ptr(token), _ptr(out_tokens), out_tokens.stride(0), _ptr(out_count), _ptr(sampled),
+                                                 _ptr(emb), _ptr(x), P, D, _stream()), "ld_llm_sample_advance_wide")
 
 
 def llm_decode_advance(sampled, forced, pos, token, out_tokens, out_count):

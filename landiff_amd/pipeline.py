@@ -41,7 +41,7 @@ class PromptInputs:
 
 class LanDiffPipeline:
     def __init__(self, cfg: PipelineConfig, states: dict, device="cuda:0", max_llm_frames: int | None = None,
-                 fp8_gemm: bool = False, theia=None, max_samples: int = 1):
+                 fp8_gemm: bool = False, theia=None, max_samples: int = 1, wide_samples: int = 0):
         if not torch.cuda.is_available():
             raise _lib.LandiffHipError("LanDiffPipeline needs an MI355X GPU: there is no CPU fallback")
         _lib.load()
@@ -49,9 +49,10 @@ class LanDiffPipeline:
         self.dev = torch.device(device)
         torch.cuda.set_device(self.dev)
         # max_llm_frames > segment_length sizes the KV cache / position tables for multi-segment (streaming) decodes
-        # max_samples > 1: generate_samples decodes that many samples of a prompt side by side (LLMRunner.sample_many)
+        # max_samples > 1: generate_samples decodes that many samples of a prompt side by side (LLMRunner.sample_many);
+        # wide_samples (0..16): as many with generate_samples(engine="mfma") (the MFMA decode engine, ~0.36 GB of KV cache per row)
         self.llm = LLMRunner(states["llm"], cfg.llm, self.dev, max_frames=max_llm_frames or cfg.llm.segment_length,
-                             max_samples=max_samples) if "llm" in states else None
+                             max_samples=max_samples, wide_samples=wide_samples) if "llm" in states else None
         self.detok = Detokenizer(states["tok"], states["ups"], cfg.tok, cfg.ups, self.dev)
         # fp8_gemm: BASELINE configs[4] (e4m3 operands for the DiT's four large linears); never the headline configuration
         self.dit = ControlDiTRunner(states["dit_main"], states["dit_control"], cfg.dit, self.dev, fp8_gemm=fp8_gemm)
@@ -114,7 +115,8 @@ class LanDiffPipeline:
         return self.decode(z, want_float=want_float)
 
     @torch.no_grad()
-    def generate_samples(self, inp: PromptInputs, seeds, keep: int | None = None, want_float: bool = False) -> list:
+    def generate_samples(self, inp: PromptInputs, seeds, keep: int | None = None, want_float: bool = False,
+                         engine: str = "gemv") -> list:
         """Several candidates of one prompt: result i is identical to `self(replace(inp, seed=seeds[i]))`.  The AR decode of all
         seeds is one LLMRunner.sample_many (the LLM's weights streamed once per step for all of them; needs
         LanDiffPipeline(..., max_samples >= len(seeds)) and non-zero seeds); detokenize, DiT and VAE then run per sample.
@@ -122,12 +124,17 @@ class LanDiffPipeline:
         distribution it was sampled from (sample_many(return_logprobs=True)), the candidates are ranked by it (rank_candidates)
         and detokenize, DiT and VAE run for the k most likely only -> [(seed, score, frames)] in rank order, frames what the
         keep=None call returns for that seed.  self.last_candidates keeps every candidate: {"seeds", "tokens" [N, n_visual],
-        "scores" [N], "order"}.  Whether likelihood rank tracks visual quality is not measured."""
+        "scores" [N], "order"}.  Whether likelihood rank tracks visual quality is not measured.
+        engine="mfma": the decode runs on the MFMA engine (sample_many(engine="mfma"); needs LanDiffPipeline(..., wide_samples >=
+        len(seeds)), up to 16 seeds).  Result i is then identical to the ONE-seed call generate_samples(inp, [seeds[i]],
+        engine="mfma") -- whatever the other seeds are -- and equals `self(replace(inp, seed=seeds[i]))` only up to the first
+        near-tie of the draw that the engines' different summation orders decide differently."""
         from dataclasses import replace
         seeds = [int(s) for s in seeds]
         if keep is not None and not 1 <= int(keep) <= len(seeds):
             raise ValueError(f"generate_samples: keep={keep} outside [1, {len(seeds)}] (the number of seeds)")
-        kw = dict(motion_score=inp.motion_score, num_frames=self.cfg.llm.segment_length, guidance_scale=inp.cfg, temperature=1.0)
+        kw = dict(motion_score=inp.motion_score, num_frames=self.cfg.llm.segment_length, guidance_scale=inp.cfg, temperature=1.0,
+                  engine=engine)
         t0 = time.perf_counter()
         if keep is None:
             tokens = self.llm.sample_many(inp.llm_text_emb, seeds, **kw)
