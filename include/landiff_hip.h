@@ -258,7 +258,7 @@ int ld_feature_denorm(const void* x, const float* mean, const float* stdv, void*
 int ld_vq_nearest(const void* x, int64_t ldx, const float* codebook, int64_t* idx, int64_t rows, int64_t V,
                   int64_t dim, void* stream);
 
-/* ---- HBM-bound small-batch kernels (ld_llm.hip) ---- */
+/* ---- HBM-bound small-batch kernels (ld_llm_gemv.hip, ld_llm_attn.hip, ld_llm_sample.hip, ld_llm.hip) ---- */
 
 /* y[b][n] = epi(sum_k in_act(x[b][k]) * W[n][k]), 1 <= B <= 4, weights streamed once (one wave per row).
  * bf16 weights: result rounds to bf16 (Linear output), then act, then `* bf16(W2 x)` (gated MLP,

@@ -50,6 +50,12 @@ I64 = c_int64
 I32 = c_int32
 P = c_void_p
 
+# argument lists that several entry points share (the engines of one operation)
+_GEMV = [P, I64, I32, P, P, I32, P, P, I64, P, I64, I32, I64, I64, I64, I32, I32, P, c_float, P]
+_DECODE_FORWARD = [P, I64, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, c_float, c_float, P]
+_SAMPLE_ADVANCE_MANY = [P, P, P, I64, I32, c_float, c_float, P, P, I64, I32, c_float, P, P, P, P, I64, P, P, P, P, I64, I64, P]
+_ATTN_FWD = [P, P, P, P, I64, I64, I64, I64, I64, I64, I64, c_float, P, P, P, P, P]
+
 # name -> argtypes; every symbol declared in include/landiff_hip.h must be listed here
 SIGNATURES: dict[str, list] = {
     "ld_version": [],
@@ -63,15 +69,15 @@ SIGNATURES: dict[str, list] = {
     "ld_gemm_route": [I64, I64, I64, I64, POINTER(Epilogue), POINTER(I32)],
     "ld_calib_mfma_bf16": [P, I64, P, I64, I64, POINTER(c_double), P],
     "ld_calib_stream_read": [P, I64, P, P],
-    "ld_attn_fwd_bf16": [P, P, P, P, I64, I64, I64, I64, I64, I64, I64, c_float, P, P, P, P, P],
-    "ld_attn_fwd_bf16_exact": [P, P, P, P, I64, I64, I64, I64, I64, I64, I64, c_float, P, P, P, P, P],
+    "ld_attn_fwd_bf16": _ATTN_FWD,
+    "ld_attn_fwd_bf16_exact": _ATTN_FWD,
     "ld_attn_last_kernel": [],
     "ld_attn_last_fallbacks": [P, P],
     "ld_reset": [P],
     "ld_attn_queue_poke": [I32, c_uint32, P],
-    "ld_gemv": [P, I64, I32, P, P, I32, P, P, I64, P, I64, I32, I64, I64, I64, I32, I32, P, c_float, P],
-    "ld_gemv_pairs": [P, I64, I32, P, P, I32, P, P, I64, P, I64, I32, I64, I64, I64, I32, I32, P, c_float, P],
-    "ld_gemv_wide": [P, I64, I32, P, P, I32, P, P, I64, P, I64, I32, I64, I64, I64, I32, I32, P, c_float, P],
+    "ld_gemv": _GEMV,
+    "ld_gemv_pairs": _GEMV,
+    "ld_gemv_wide": _GEMV,
     "ld_rmsnorm_bf16": [P, P, P, I64, I64, c_float, P],
     "ld_layernorm_bf16_to_f32": [P, I64, P, P, P, I64, I64, c_float, P],
     "ld_llm_rope_append": [P, P, P, P, P, P, P, I64, I64, I64, I64, P],
@@ -86,19 +92,14 @@ SIGNATURES: dict[str, list] = {
     "ld_feature_norm_cl": [P, I32, P, P, P, I64, I64, I64, P],
     "ld_feature_denorm": [P, P, P, P, I64, I64, P],
     "ld_vq_nearest": [P, I64, P, P, I64, I64, I64, P],
-    "ld_llm_decode_forward": [P, I64, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64,
-                              c_float, c_float, P],
-    "ld_llm_decode_forward_pairs": [P, I64, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64,
-                                    c_float, c_float, P],
-    "ld_llm_decode_forward_wide": [P, I64, P, P, P, I32, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64,
-                                   c_float, c_float, P],
+    "ld_llm_decode_forward": _DECODE_FORWARD,
+    "ld_llm_decode_forward_pairs": _DECODE_FORWARD,
+    "ld_llm_decode_forward_wide": _DECODE_FORWARD,
     "ld_llm_logits_to_probs": [P, P, P, I64, I32, c_float, c_float, P, P, I64, I32, c_float, P],
     "ld_llm_decode_advance": [P, P, P, P, P, P, P],
     "ld_llm_sample_advance": [P, P, P, I64, I32, c_float, c_float, P, P, I64, I32, c_float, P, P, P, P, P, P, P, P, I64, I64, P],
-    "ld_llm_sample_advance_pairs": [P, P, P, I64, I32, c_float, c_float, P, P, I64, I32, c_float, P, P, P, P, I64, P, P, P, P, I64, I64,
-                                    P],
-    "ld_llm_sample_advance_wide": [P, P, P, I64, I32, c_float, c_float, P, P, I64, I32, c_float, P, P, P, P, I64, P, P, P, P, I64, I64,
-                                   P],
+    "ld_llm_sample_advance_pairs": _SAMPLE_ADVANCE_MANY,
+    "ld_llm_sample_advance_wide": _SAMPLE_ADVANCE_MANY,
     "ld_llm_token_logprobs": [P, I64, P, I64, I64, I64, I32, c_float, c_float, P, I64, I32, P, I64, P, I64, I32, c_float, P, P, P, P,
                               I64, P],
     "ld_llm_head_f32": [P, I64, P, I64, P, I64, I64, I64, I64, P],

@@ -7,7 +7,7 @@
 set -e
 cd "$(dirname "$0")"
 VARIANT_ONLY="ld_attn_pipe.hip ld_attn_q128.hip ld_llm_fused.hip ld_gemm_variants.hip"
-HDRS="ld_common.h ld_gemm.h ld_attn.h ld_attn_q64_body.h ld_llm_dev.h ../../include/landiff_hip.h build.sh"      # (build.sh: a change of flags rebuilds everything)
+HDRS="ld_common.h ld_gemm.h ld_attn.h ld_attn_q64_body.h ld_llm.h ld_llm_dev.h ld_llm_sample_dev.h ../../include/landiff_hip.h build.sh"      # (build.sh: a change of flags rebuilds everything)
 
 build_lib() {   # $1 = object dir, $2 = output, $3 = extra flags, $4.. = sources
   local objdir=$1 out=$2 flags=$3; shift 3
@@ -33,9 +33,10 @@ build_lib() {   # $1 = object dir, $2 = output, $3 = extra flags, $4.. = sources
       # of the SIMD do: with the DiT's 64-row attention kernel co-resident (AR decode under the DiT loop: generate_many, the streaming
       # loop) the prefill's rotated q / k came out one bf16 step off in ~1e-5 .. 1e-3 of the even elements, and the decode sampled
       # other tokens (tools/llm_race_probe2.py, profiles/r05_llm_packed_f32_under_coresidency.txt).  Scalar v_mul / v_sub / v_add: clean.
-      # ld_llm_score.hip restates the sampling kernel's distribution: its guided logits must be the same bits, hence the same flags.
+      # ld_llm_score.hip shares the sampling kernel's distribution (ld_llm_sample_dev.h): the same bits need the same flags.
       # ld_llm_wide.hip restates ld_gemv_kernel's RMSNorm staging and epilogue: the same rounding points need the same unfused mul / add.
-      case $s in ld_llm.hip|ld_llm_fused.hip|ld_llm_score.hip|ld_llm_wide.hip) extra="-ffp-contract=off -fno-slp-vectorize";; esac
+      # The pattern covers the whole family, so that a new file of it cannot miss the flags.
+      case $s in ld_llm*.hip) extra="-ffp-contract=off -fno-slp-vectorize";; esac
       hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wno-unused-result $extra $flags -c "$s" -o "$o" &
       pids+=($!)
     fi

@@ -1,4 +1,4 @@
-// Device helpers shared by the decode-step kernels (ld_llm.hip: one launch per operation; ld_llm_fused.hip: one persistent
+// Device helpers shared by the decode-step kernels (ld_llm_gemv.hip, ld_llm_attn.hip: one launch per operation; ld_llm_fused.hip: one persistent
 // launch for all blocks of a step).  Both forms must produce the same bits, so the arithmetic they share lives here.
 #pragma once
 #include "ld_common.h"
@@ -64,7 +64,7 @@ __host__ __device__ inline int kv_eff_splits(int L, int nsplit_max, KvSplitRule 
   while ((L + ns - 1) / ns > 16 * KV_MAXIT && ns < nsplit_max) ns = 2 * ns < nsplit_max ? 2 * ns : nsplit_max;
   return ns;
 }
-KvSplitRule ld_kv_split_rule();      // ld_llm.hip (environment knob, read once)
+KvSplitRule ld_kv_split_rule();      // ld_llm_attn.hip (environment knob, read once)
 
 // rows k_begin .. k_begin + n of (b, h) in caches laid out [B][Lmax][H][128]; row0 = b * Lmax + k_begin
 __device__ __forceinline__ void kv_rows_request(KvRows& r, const bf16_t* kc, const bf16_t* vc, long row0, int H, int h, int n,

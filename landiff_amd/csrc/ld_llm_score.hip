@@ -1,26 +1,9 @@
 // Scoring of AR token sequences: the log-probability of given tokens under the distribution the sampler draws from
 // (ld_llm_token_logprobs), and the all-positions fp32 head of the teacher-forced pass (ld_llm_head_f32).
-// Siblings of the sampling kernels of ld_llm.hip: nothing here is called by them and nothing of theirs is edited.
 #include "ld_common.h"
-#include "../../include/landiff_hip.h"
+#include "ld_llm_sample_dev.h"
 
 namespace {
-
-// LD_SAMPLE_MAXV comes from the public header; ld_llm.hip (not edited here) carries its own, token-identical #define, which the
-// preprocessor accepts only while the two agree: a different value there is a macro-redefinition diagnostic in that file.
-static_assert(LD_SAMPLE_MAXV == 4096, "the sampling kernels of ld_llm.hip size their LDS rows for 4096 ids");
-
-// ld_llm.hip's block_sum_1024, restated: the same order of additions gives the same total for the same terms (the softmax
-// denominator and the top-p mass must be the sampler's bits, or a target on the edge of the nucleus is judged differently)
-__device__ __forceinline__ float score_block_sum(float v, float* red, int tid, int nthreads) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((tid & 63) == 0) red[tid >> 6] = v;
-  __syncthreads();
-  float tot = 0.f;
-  for (int w = 0; w < (nthreads >> 6); ++w) tot += red[w];
-  return tot;
-}
 
 struct ScoreArgs {
   const float* cond; long cond_stride;       // conditional logits, row r at cond + r * cond_stride
@@ -33,9 +16,9 @@ struct ScoreArgs {
   float* cfg_out; long cfg_stride;           // optional: the guided logits of the rows that are draws
 };
 
-// One workgroup per row.  The distribution is ld_logits_to_probs_kernel's, operation for operation (CFG, / temperature, restriction,
-// top-k, softmax, top-p); only the result is taken in the log domain: (l_t - max) - log(sum exp(l - max)) [- log(kept)], which stays
-// finite where the sampler's fp32 probability exp(l_t - max) / sum has long underflowed to 0.
+// One workgroup per row.  The distribution is the sampler's (ld_llm_sample_dev.h); only the result is taken in the log domain:
+// (l_t - max) - log(sum exp(l - max)) [- log(kept)], which stays finite where the sampler's fp32 probability
+// exp(l_t - max) / sum has long underflowed to 0.
 __global__ __launch_bounds__(1024) void ld_token_logprobs_kernel(ScoreArgs a) {
   __shared__ float red[32];
   __shared__ float sv[LD_SAMPLE_MAXV];     // filtered logit per vocabulary id, later its probability
@@ -59,83 +42,20 @@ __global__ __launch_bounds__(1024) void ld_token_logprobs_kernel(ScoreArgs a) {
     if (tid == 0) { a.logprob[r] = -INFINITY; if (a.valid) a.valid[r] = 1; }
     return;
   }
-  const float* lc = a.cond + r * a.cond_stride;
-  const float* lu = a.uncond + r * a.uncond_stride;
-  const int* al = nullptr;
-  int nal = 0;
-  if (a.allowed) {
-    al = a.allowed + (long)(pos + 1) * a.allowed_stride;    // table indexed by the position being generated
-    nal = al[0];
-  }
-  for (int i = tid; i < V; i += nt) {
-    float l = lc[i];
-    if (a.guided) { const float u = lu[i]; l = u + a.scale * (l - u); }
-    if (a.cfg_out) a.cfg_out[r * a.cfg_stride + i] = l;
-    l = l / a.temperature;
-    if (nal > 0) {
-      bool ok = false;
-      for (int k = 0; k < nal; ++k) ok |= (al[1 + k] == i);
-      if (!ok) l = -INFINITY;
-    }
-    sv[i] = l;
-  }
-  if (tid == 0) removed_s = 0;
-  __syncthreads();
-  // top-k (unrestricted positions only): everything below the k-th largest logit -> -inf; ties at the threshold stay
-  if (a.top_k > 0 && a.top_k < V && nal == 0) {
-    for (int i = tid; i < V; i += nt) {
-      const float v = sv[i];
-      int gt = 0, ge = 0;
-      for (int j = 0; j < V; ++j) { const float o = sv[j]; gt += (o > v); ge += (o >= v); }
-      if (gt < a.top_k && a.top_k <= ge) thr_s = v;           // every writer holds the same value
-    }
-    __syncthreads();
-    const float thr = thr_s;
-    for (int i = tid; i < V; i += nt) if (sv[i] < thr) sv[i] = -INFINITY;
-    __syncthreads();
-  }
-  float mx = -3.0e38f;
-  for (int i = tid; i < V; i += nt) mx = fmaxf(mx, sv[i]);
-  mx = wave_max(mx);
-  if ((tid & 63) == 0) red[tid >> 6] = mx;
-  __syncthreads();
-  float m2 = red[0];
-  for (int w = 1; w < (nt >> 6); ++w) m2 = fmaxf(m2, red[w]);
+  if (tid == 0) removed_s = 0;                              // (published by the barrier that ends dist_fill)
+  const int nal = dist_fill(sv, a.cond + r * a.cond_stride, a.uncond + r * a.uncond_stride, a.guided, a.scale, a.temperature,
+                            a.cfg_out ? a.cfg_out + r * a.cfg_stride : nullptr,
+                            a.allowed ? a.allowed + (long)(pos + 1) * a.allowed_stride : nullptr, V, tid, nt);
+  dist_top_k(sv, &thr_s, a.top_k, nal, V, tid, nt);
+  const float m2 = dist_max(sv, red, V, tid, nt);
   const float lt = sv[t] - m2;                                // the target's shifted logit (-inf: removed), before sv is overwritten
   __syncthreads();
-  float s = 0.f;
-  for (int i = tid; i < V; i += nt) { const float e = expf(sv[i] - m2); sv[i] = e; s += e; }
-  const float tot = score_block_sum(s, red, tid, nt);
+  const float tot = dist_exp_sum(sv, red, m2, V, tid, nt);
   float lp = lt - logf(tot);
-  // top-p (unrestricted positions only): drop sorted position j >= 1 when cumsum[j-1] >= top_p, renormalise
-  if (a.top_p >= 0.f && nal == 0) {
-    for (int i = tid; i < V; i += nt) sv[i] = sv[i] / tot;
-    __syncthreads();
-    int rk[(LD_SAMPLE_MAXV + 1023) / 1024];
-    int c = 0;
-    for (int i = tid; i < V; i += nt, ++c) {
-      const float v = sv[i];
-      int q = 0;
-      for (int j = 0; j < V; ++j) { const float o = sv[j]; q += (o > v) || (o == v && j < i); }   // stable descending rank
-      rk[c] = q;
-      ss[q] = v;
-    }
-    __syncthreads();
-    if (tid == 0) {                                            // sequential fp32 cumsum (torch.cumsum's CPU order)
-      float acc = 0.f;
-      for (int j = 0; j < V; ++j) { acc += ss[j]; ss[j] = acc; }
-    }
-    __syncthreads();
-    float ks = 0.f;
-    c = 0;
-    for (int i = tid; i < V; i += nt, ++c) {
-      const int q = rk[c];
-      float p = sv[i];
-      if (q >= 1 && ss[q - 1] >= a.top_p) { p = 0.f; if (i == t) removed_s = 1; }
-      ks += p;
-    }
-    const float kept = score_block_sum(ks, red, tid, nt);      // (its barriers publish removed_s)
-    lp = removed_s ? -INFINITY : lp - logf(kept);
+  if (dist_top_p_applies(a.top_p, nal)) {
+    dist_divide(sv, tot, V, tid, nt);
+    const float kept = dist_top_p(sv, ss, red, a.top_p, V, tid, nt, [&](int i) { if (i == t) removed_s = 1; });
+    lp = removed_s ? -INFINITY : lp - logf(kept);              // (the barriers of the last block sum publish removed_s)
   }
   if (tid == 0) {
     a.logprob[r] = lt == -INFINITY ? -INFINITY : lp;

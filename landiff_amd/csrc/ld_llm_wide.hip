@@ -1,7 +1,7 @@
 // Weight-streaming skinny GEMM on v_mfma_f32_32x32x16_bf16: the second engine of the batched AR decode (ld_gemv_wide).
 //
 // out[b][n] = epi( sum_k xn[b][k] * W[n][k] ) for B <= 32 activation rows (up to 16 (cond, uncond) pairs of one prompt, Semantic1DLM.sample
-// once per seed, lm_model.py:417-508, over the cached blocks of transformer_blocks.py:128-236).  The register GEMV of ld_llm.hip
+// once per seed, lm_model.py:417-508, over the cached blocks of transformer_blocks.py:128-236).  The register GEMV of ld_llm_gemv.hip
 // (ld_gemv_pairs) keeps all B activation rows in registers and stops at B = 8; here 32 weight rows are the MFMA's 32-row operand and
 // the B activation rows are its 32 columns (columns >= B are zero operands), so every weight byte is read from HBM once for all rows.
 //

@@ -321,10 +321,10 @@ class LLMRunner:
         c, B = self.cfg, 2 * P
         if self._layer_table is None:
             self._layer_table = ops.llm_layer_table(self.blocks, self.kc, self.vc)      # (kc[i] is the head of kc_all[i]: same address)
-        forward = ops.llm_decode_forward_wide if wide else ops.llm_decode_forward_pairs
-        forward(self._layer_table, self.emb if embed else None, self.m_token[:P], self.m_pos[:P], self.m_x[:B], self.m_qkv[:B], self.m_att[:B],
-                self.m_gate[:B], self.m_attn_ws, self.cos, self.sin, self.ln_w, self.ln_b, self.m_lnf[:B], self.head,
-                self.m_logits[:B], c.heads, self.Lmax, self.nsplit, c.rms_eps, c.ln_eps, pos_value=pos_value)
+        ops._llm_decode_forward("ld_llm_decode_forward_wide" if wide else "ld_llm_decode_forward_pairs", self._layer_table,
+                                self.emb if embed else None, self.m_token[:P], self.m_pos[:P], self.m_x[:B], self.m_qkv[:B], self.m_att[:B],
+                                self.m_gate[:B], self.m_attn_ws, self.cos, self.sin, self.ln_w, self.ln_b, self.m_lnf[:B], self.head,
+                                self.m_logits[:B], c.heads, self.Lmax, self.nsplit, c.rms_eps, c.ln_eps, pos_value)
 
     def _sample_and_advance_many(self, gens, guided, scale, temperature, top_k=None, top_p=None, logits_log=None, wide=False):
         """_sample_and_advance for len(gens) samples: generator p draws the [vocab] Exp(1) row sample() draws from it at this
@@ -333,10 +333,10 @@ class LLMRunner:
         noise, cfg_logits = self.m_noise[:P], self.m_cfg_logits[:P]
         for p in range(P):
             noise[p].exponential_(1.0, generator=gens[p])
-        advance = ops.llm_sample_advance_wide if wide else ops.llm_sample_advance_pairs
-        advance(self.m_logits[:2 * P], None, cfg_logits, guided, scale, temperature, self.m_pos[:P], self.allowed, noise,
-                self.forced, self.m_token[:P], self.m_out_tokens[:P], self.m_out_count[:P], self.m_sampled[:P],
-                self.emb, self.m_x[:2 * P], top_k=top_k, top_p=top_p)
+        ops._llm_sample_advance_many("ld_llm_sample_advance_wide" if wide else "ld_llm_sample_advance_pairs", self.m_logits[:2 * P], None,
+                                     cfg_logits, guided, scale, temperature, self.m_pos[:P], self.allowed, noise, self.forced,
+                                     self.m_token[:P], self.m_out_tokens[:P], self.m_out_count[:P], self.m_sampled[:P], self.emb,
+                                     self.m_x[:2 * P], top_k=top_k, top_p=top_p)
         if logits_log is not None:
             logits_log.append(cfg_logits.clone())
 
@@ -387,6 +387,31 @@ class LLMRunner:
         self.forced.copy_(ft); self.allowed.copy_(al)
         return feats, S_last, full_len, forced, n_visual, n_prefix
 
+    def _segment_notifier(self, on_segment, segment_tokens, forced, first_frame_tokens, prefix_tokens):
+        """-> note(pos), called when the token of position pos has just been queued (for every sample): on_segment(s) fires after
+        the last of every `segment_tokens` positions the schedule leaves free."""
+        assert on_segment is None or (segment_tokens and first_frame_tokens is None and prefix_tokens is None)
+        emitted = 0
+        def note(pos):
+            nonlocal emitted
+            if on_segment is None or pos in forced:
+                return
+            emitted += 1
+            if emitted % segment_tokens == 0:
+                on_segment(emitted // segment_tokens - 1)
+        return note
+
+    def _assemble_ids(self, out, prefix_tokens, first_frame_tokens, lp_steps, S_last, full_len, forced):
+        """out int64 [P, n]: the sampled ids -> the given prefix_tokens / first_frame_tokens in front of every row, clamped
+        (lm_model.py:509-516); with lp_steps: (ids, logprobs [P, sampled positions])."""
+        head = [t.reshape(1, -1).to(self.dev, torch.int64).expand(out.shape[0], -1) for t in (prefix_tokens, first_frame_tokens) if t is not None]
+        if head:
+            out = torch.cat(head + [out], 1)
+        out = out.clamp(0, self.cfg.visual_vocab - 1)
+        if lp_steps is None:
+            return out
+        return out, self._gather_logprobs(lp_steps, S_last, full_len, forced)
+
     # ---- decode loop -----------------------------------------------------------------------------
     @torch.no_grad()
     def sample(self, text_emb: torch.Tensor, *, motion_score: float = 0.1, num_frames: int = 13, guidance_scale: float = 7.5,
@@ -429,22 +454,14 @@ class LLMRunner:
         guided = guidance_scale > 0 and guidance_scale != 1
         # unguided (ARSampleCfg's dataclass default cfg=0.0, lm_model.py:311-319): the conditional row is independent of the
         # second row, so the resident two-row buffers are kept and the sampling kernel reads row 0 only.
-        feats, S_last, full_len, forced, n_visual, n_prefix = self._decode_plan(text_emb, motion_score, num_frames, first_frame_tokens,
+        feats, S_last, full_len, forced, n_visual, _ = self._decode_plan(text_emb, motion_score, num_frames, first_frame_tokens,
                                                                                 prefix_tokens)
         self._x_from_tail = self.fused_tail and teacher_fed is None          # (a teacher-fed token is written by the host: re-embed it)
         self.out_count.zero_()
         if generator is None and seed:
             generator = torch.Generator(device=dev)
             generator.manual_seed(seed)                     # lm_model.py:398-402
-        emitted = 0
-        def note_position(pos):            # the token of position pos has just been queued
-            nonlocal emitted
-            if on_segment is None or pos in forced:
-                return
-            emitted += 1
-            if emitted % segment_tokens == 0:
-                on_segment(emitted // segment_tokens - 1)
-        assert on_segment is None or (segment_tokens and first_frame_tokens is None and prefix_tokens is None)
+        note_position = self._segment_notifier(on_segment, segment_tokens, forced, first_frame_tokens, prefix_tokens)
         self._prefill(feats)
         self.pos.fill_(S_last)
         self._sample_and_advance(guided, guidance_scale, temperature, generator)
@@ -495,15 +512,8 @@ class LLMRunner:
         self.host_enqueue_s = time.perf_counter() - t_enq      # host time to enqueue the loop (< wall time when the GPU is the bound)
         self._raise_on_wait_timeout()
         assert int(self.out_count.item()) == n_visual, (int(self.out_count.item()), n_visual)
-        out = self.out_tokens[:n_visual]
-        if first_frame_tokens is not None:
-            out = torch.cat([first_frame_tokens.reshape(-1).to(dev, torch.int64), out])
-        if n_prefix:
-            out = torch.cat([prefix_tokens.reshape(-1).to(dev, torch.int64), out])
-        out = out.clamp(0, c.visual_vocab - 1)
-        if lp_steps is not None:
-            return out, self._gather_logprobs(lp_steps, S_last, full_len, forced)[0]
-        return out
+        res = self._assemble_ids(self.out_tokens[None, :n_visual], prefix_tokens, first_frame_tokens, lp_steps, S_last, full_len, forced)
+        return (res[0][0], res[1][0]) if lp_steps is not None else res[0]
 
     def _step_logprobs(self, cond, uncond, sampled, pos, out, guided, scale, temperature, top_k, top_p):
         """The log-probabilities of the tokens the sampling launch just drew, from the logits it read (the next forward has not
@@ -625,7 +635,7 @@ class LLMRunner:
             return (r[0][None], r[1][None]) if return_logprobs else r[None]
         self._mode = "chain"
         guided = guidance_scale > 0 and guidance_scale != 1
-        feats, S_last, full_len, forced, n_visual, n_prefix = self._decode_plan(text_emb, motion_score, num_frames, first_frame_tokens,
+        feats, S_last, full_len, forced, n_visual, _ = self._decode_plan(text_emb, motion_score, num_frames, first_frame_tokens,
                                                                                 prefix_tokens)
         gens = []
         for s in seeds:
@@ -644,15 +654,7 @@ class LLMRunner:
                 self._step_logprobs(pairs[:, :c.vocab], pairs[:, c.vocab:], self.m_sampled[:P], self.m_pos[:P], lp_steps[k], guided,
                                     guidance_scale, temperature, top_k, top_p)
 
-        emitted = 0
-        def note_position(q):              # the token of position q has just been queued (for every sample)
-            nonlocal emitted
-            if on_segment is None or q in forced:
-                return
-            emitted += 1
-            if emitted % segment_tokens == 0:
-                on_segment(emitted // segment_tokens - 1)
-        assert on_segment is None or (segment_tokens and first_frame_tokens is None and prefix_tokens is None)
+        note_position = self._segment_notifier(on_segment, segment_tokens, forced, first_frame_tokens, prefix_tokens)
         out_count.zero_()
         self.m_attn_ws.zero_()             # (its counter words sit where another P's partial results were)
         self._prefill(feats)
@@ -677,14 +679,7 @@ class LLMRunner:
         self.host_enqueue_s = time.perf_counter() - t_enq
         counts = out_count.tolist()
         assert counts == [n_visual] * P, (counts, n_visual)
-        out = out_tokens[:, :n_visual]
-        head = [t.reshape(1, -1).to(dev, torch.int64).expand(P, -1) for t in (prefix_tokens, first_frame_tokens) if t is not None]
-        if head:
-            out = torch.cat(head + [out], 1)
-        out = out.clamp(0, c.visual_vocab - 1)
-        if lp_steps is not None:
-            return out, self._gather_logprobs(lp_steps, S_last, full_len, forced)
-        return out
+        return self._assemble_ids(out_tokens[:, :n_visual], prefix_tokens, first_frame_tokens, lp_steps, S_last, full_len, forced)
 
     def _raise_on_wait_timeout(self):
         """The 'fused' and 'chained' forms spin-wait on other workgroups without a cooperative launch; a wait that gives up sets a

@@ -231,46 +231,33 @@ def attn_queue_poke(value: int, set_index: int = -1) -> None:
 # ------------------------------------------------------------------------------------------------
 # small-batch / LLM kernels
 # ------------------------------------------------------------------------------------------------
-def gemv(x, w, out, *, w2=None, bias=None, resid=None, in_act=None, act=None, norm_w=None, norm_eps=0.0):
-    """out[B,N] = epi(x[B,K] @ w[N,K]^T) for B <= 4 (weight streaming)."""
+def _gemv(symbol, x, w, out, w2, bias, resid, in_act, act, norm_w, norm_eps):
     B, K = x.shape
     N = w.shape[0]
     assert w.shape[1] == K and out.shape == (B, N) and x.stride(1) == 1 and out.stride(1) == 1 and w.is_contiguous()
-    w_f32 = w.dtype == torch.float32
-    lib = _lib.load()
-    check(lib.ld_gemv(_ptr(x), x.stride(0), int(x.dtype == torch.float32), _ptr(w), _ptr(w2), int(w_f32), _ptr(bias),
-                      _ptr(resid), resid.stride(0) if resid is not None else 0, _ptr(out), out.stride(0),
-                      int(out.dtype == torch.float32), B, N, K, ACT[in_act], ACT[act], _ptr(norm_w), float(norm_eps),
-                      _stream()), "ld_gemv")
+    check(getattr(_lib.load(), symbol)(_ptr(x), x.stride(0), int(x.dtype == torch.float32), _ptr(w), _ptr(w2),
+                                       int(w.dtype == torch.float32), _ptr(bias), _ptr(resid),
+                                       resid.stride(0) if resid is not None else 0, _ptr(out), out.stride(0),
+                                       int(out.dtype == torch.float32), B, N, K, ACT[in_act], ACT[act], _ptr(norm_w), float(norm_eps),
+                                       _stream()), symbol)
     return out
+
+
+def gemv(x, w, out, *, w2=None, bias=None, resid=None, in_act=None, act=None, norm_w=None, norm_eps=0.0):
+    """out[B,N] = epi(x[B,K] @ w[N,K]^T) for B <= 4 (weight streaming)."""
+    return _gemv("ld_gemv", x, w, out, w2, bias, resid, in_act, act, norm_w, norm_eps)
 
 
 def gemv_pairs(x, w, out, *, w2=None, bias=None, resid=None, in_act=None, act=None, norm_w=None, norm_eps=0.0):
     """gemv for B = 2 P rows (P <= LLM_MAX_PAIRS samples side by side): rows (2p, 2p+1) get the bits of gemv on those two rows;
     the bf16 register forms stream the weights once for all pairs (ld_gemv_pairs)."""
-    B, K = x.shape
-    N = w.shape[0]
-    assert w.shape[1] == K and out.shape == (B, N) and x.stride(1) == 1 and out.stride(1) == 1 and w.is_contiguous()
-    check(_lib.load().ld_gemv_pairs(_ptr(x), x.stride(0), int(x.dtype == torch.float32), _ptr(w), _ptr(w2),
-                                    int(w.dtype == torch.float32), _ptr(bias), _ptr(resid),
-                                    resid.stride(0) if resid is not None else 0, _ptr(out), out.stride(0),
-                                    int(out.dtype == torch.float32), B, N, K, ACT[in_act], ACT[act], _ptr(norm_w), float(norm_eps),
-                                    _stream()), "ld_gemv_pairs")
-    return out
+    return _gemv("ld_gemv_pairs", x, w, out, w2, bias, resid, in_act, act, norm_w, norm_eps)
 
 
 def gemv_wide(x, w, out, *, w2=None, bias=None, resid=None, in_act=None, act=None, norm_w=None, norm_eps=0.0):
     """gemv for B = 2 P rows, P <= LLM_MAX_WIDE, on the MFMA engine (ld_gemv_wide): bf16 only; a row's bits depend on that row
     alone (not on B or its index); same rounding points as gemv, another order of the fp32 sum."""
-    B, K = x.shape
-    N = w.shape[0]
-    assert w.shape[1] == K and out.shape == (B, N) and x.stride(1) == 1 and out.stride(1) == 1 and w.is_contiguous()
-    check(_lib.load().ld_gemv_wide(_ptr(x), x.stride(0), int(x.dtype == torch.float32), _ptr(w), _ptr(w2),
-                                   int(w.dtype == torch.float32), _ptr(bias), _ptr(resid),
-                                   resid.stride(0) if resid is not None else 0, _ptr(out), out.stride(0),
-                                   int(out.dtype == torch.float32), B, N, K, ACT[in_act], ACT[act], _ptr(norm_w), float(norm_eps),
-                                   _stream()), "ld_gemv_wide")
-    return out
+    return _gemv("ld_gemv_wide", x, w, out, w2, bias, resid, in_act, act, norm_w, norm_eps)
 
 
 def rmsnorm(x, w, out, eps):
@@ -325,55 +312,45 @@ def llm_layer_table(blocks, k_caches, v_caches):
     return arr
 
 
-def llm_decode_forward(table, emb, token, pos, x, qkv, att, gate, attn_ws, cos_t, sin_t, lnf_w, lnf_b, lnf_out, head, logits,
-                       heads, Lmax, nsplit, rms_eps, ln_eps, pos_value=-1):
-    """One decode step (embedding -> all blocks -> final LN -> fp32 head), every launch queued from native code."""
+LLM_MAX_PAIRS = 4                  # LD_LLM_MAX_PAIRS
+LLM_MAX_WIDE = 16                  # LD_LLM_MAX_WIDE
+
+
+def _llm_decode_forward(symbol, table, emb, token, pos, x, qkv, att, gate, attn_ws, cos_t, sin_t, lnf_w, lnf_b, lnf_out, head, logits,
+                        heads, Lmax, nsplit, rms_eps, ln_eps, pos_value):
     B, hidden = x.shape
     for t in (x, qkv, att, gate, lnf_out, logits, head):
         assert t.is_contiguous()
-    check(_lib.load().ld_llm_decode_forward(ctypes.addressof(table), len(table), _ptr(emb), _ptr(token), _ptr(pos), int(pos_value), _ptr(x),
-                                            _ptr(qkv), _ptr(att), _ptr(gate), _ptr(attn_ws), _ptr(cos_t), _ptr(sin_t),
-                                            _ptr(lnf_w), _ptr(lnf_b), _ptr(lnf_out), _ptr(head), _ptr(logits), B, hidden,
-                                            heads, gate.shape[1], logits.shape[1], Lmax, nsplit, float(rms_eps),
-                                            float(ln_eps), _stream()), "ld_llm_decode_forward")
+    need = B * heads * (nsplit * 130 + 1)
+    assert attn_ws.dtype == torch.float32 and attn_ws.numel() >= need, f"attn_ws: {attn_ws.numel()} words, needs {need}"
+    check(getattr(_lib.load(), symbol)(ctypes.addressof(table), len(table), _ptr(emb), _ptr(token), _ptr(pos), int(pos_value), _ptr(x),
+                                       _ptr(qkv), _ptr(att), _ptr(gate), _ptr(attn_ws), _ptr(cos_t), _ptr(sin_t), _ptr(lnf_w),
+                                       _ptr(lnf_b), _ptr(lnf_out), _ptr(head), _ptr(logits), B, hidden, heads, gate.shape[1],
+                                       logits.shape[1], Lmax, nsplit, float(rms_eps), float(ln_eps), _stream()), symbol)
 
 
-LLM_MAX_PAIRS = 4                  # LD_LLM_MAX_PAIRS
+def llm_decode_forward(table, emb, token, pos, x, qkv, att, gate, attn_ws, cos_t, sin_t, lnf_w, lnf_b, lnf_out, head, logits,
+                       heads, Lmax, nsplit, rms_eps, ln_eps, pos_value=-1):
+    """One decode step (embedding -> all blocks -> final LN -> fp32 head), every launch queued from native code."""
+    _llm_decode_forward("ld_llm_decode_forward", table, emb, token, pos, x, qkv, att, gate, attn_ws, cos_t, sin_t, lnf_w, lnf_b, lnf_out, head, logits,
+                        heads, Lmax, nsplit, rms_eps, ln_eps, pos_value)
 
 
 def llm_decode_forward_pairs(table, emb, token, pos, x, qkv, att, gate, attn_ws, cos_t, sin_t, lnf_w, lnf_b, lnf_out, head, logits,
                              heads, Lmax, nsplit, rms_eps, ln_eps, pos_value=-1):
     """llm_decode_forward for P samples of one prompt: B = 2 P rows, pair p = rows (2p, 2p+1); token [P]; nsplit: the value a
     two-row runner with this Lmax uses (ld_llm_decode_forward_pairs)."""
-    B, hidden = x.shape
-    for t in (x, qkv, att, gate, lnf_out, logits, head):
-        assert t.is_contiguous()
-    need = B * heads * (nsplit * 130 + 1)
-    assert attn_ws.dtype == torch.float32 and attn_ws.numel() >= need, f"attn_ws: {attn_ws.numel()} words, needs {need}"
-    check(_lib.load().ld_llm_decode_forward_pairs(ctypes.addressof(table), len(table), _ptr(emb), _ptr(token), _ptr(pos), int(pos_value),
-                                                  _ptr(x), _ptr(qkv), _ptr(att), _ptr(gate), _ptr(attn_ws), _ptr(cos_t), _ptr(sin_t),
-                                                  _ptr(lnf_w), _ptr(lnf_b), _ptr(lnf_out), _ptr(head), _ptr(logits), B, hidden,
-                                                  heads, gate.shape[1], logits.shape[1], Lmax, nsplit, float(rms_eps),
-                                                  float(ln_eps), _stream()), "ld_llm_decode_forward_pairs")
-
-
-LLM_MAX_WIDE = 16                  # LD_LLM_MAX_WIDE
+    _llm_decode_forward("ld_llm_decode_forward_pairs", table, emb, token, pos, x, qkv, att, gate, attn_ws, cos_t, sin_t, lnf_w, lnf_b,
+                        lnf_out, head, logits, heads, Lmax, nsplit, rms_eps, ln_eps, pos_value)
 
 
 def llm_decode_forward_wide(table, emb, token, pos, x, qkv, att, gate, attn_ws, cos_t, sin_t, lnf_w, lnf_b, lnf_out, head, logits,
                             heads, Lmax, nsplit, rms_eps, ln_eps, pos_value=-1):
     """llm_decode_forward_pairs on the MFMA engine, P <= LLM_MAX_WIDE samples (ld_llm_decode_forward_wide): the block GEMVs are
     ld_gemv_wide, the head ld_llm_head_f32; pair p's logits depend on pair p alone."""
-    B, hidden = x.shape
-    for t in (x, qkv, att, gate, lnf_out, logits, head):
-        assert t.is_contiguous()
-    need = B * heads * (nsplit * 130 + 1)
-    assert attn_ws.dtype == torch.float32 and attn_ws.numel() >= need, f"attn_ws: {attn_ws.numel()} words, needs {need}"
-    check(_lib.load().ld_llm_decode_forward_wide(ctypes.addressof(table), len(table), _ptr(emb), _ptr(token), _ptr(pos), int(pos_value),
-                                                 _ptr(x), _ptr(qkv), _ptr(att), _ptr(gate), _ptr(attn_ws), _ptr(cos_t), _ptr(sin_t),
-                                                 _ptr(lnf_w), _ptr(lnf_b), _ptr(lnf_out), _ptr(head), _ptr(logits), B, hidden,
-                                                 heads, gate.shape[1], logits.shape[1], Lmax, nsplit, float(rms_eps),
-                                                 float(ln_eps), _stream()), "ld_llm_decode_forward_wide")
+    _llm_decode_forward("ld_llm_decode_forward_wide", table, emb, token, pos, x, qkv, att, gate, attn_ws, cos_t, sin_t, lnf_w, lnf_b,
+                        lnf_out, head, logits, heads, Lmax, nsplit, rms_eps, ln_eps, pos_value)
+
 
 
 LLM_FUSED_CTL_WORDS = 512          # LD_LLM_FUSED_CTL_WORDS
@@ -444,10 +421,8 @@ def llm_sample_advance(logits, probs, cfg_logits, guided, scale, temperature, po
                                             _ptr(x), B, D, _stream()), "ld_llm_sample_advance")
 
 
-def llm_sample_advance_pairs(logits, probs, cfg_logits, guided, scale, temperature, pos, allowed, noise, forced, token, out_tokens,
-                             out_count, sampled, emb, x, top_k=None, top_p=None):
-    """llm_sample_advance for P samples in one launch: logits [2P, V], noise / probs / cfg_logits [P, V], pos / token / out_count /
-    sampled [P], out_tokens [P, n], x [2P, D]; forced / allowed are the shared schedule (ld_llm_sample_advance_pairs)."""
+def _llm_sample_advance_many(symbol, logits, probs, cfg_logits, guided, scale, temperature, pos, allowed, noise, forced, token,
+                             out_tokens, out_count, sampled, emb, x, top_k=None, top_p=None):
     V = logits.shape[-1]
     P = noise.shape[0]
     D = x.shape[1]
@@ -455,32 +430,27 @@ def llm_sample_advance_pairs(logits, probs, cfg_logits, guided, scale, temperatu
     assert pos.numel() == P and token.numel() == P and out_count.numel() == P and (sampled is None or sampled.numel() == P)
     for t in (logits, noise, x, probs, cfg_logits):
         assert t is None or t.is_contiguous()
-    check(_lib.load().ld_llm_sample_advance_pairs(_ptr(logits), _ptr(probs), _ptr(cfg_logits), V, int(guided), float(scale),
-                                                  float(temperature), _ptr(pos), _ptr(allowed),
-                                                  allowed.stride(0) if allowed is not None else 0,
-                                                  int(top_k) if top_k is not None else 0,
-                                                  float(top_p) if top_p is not None else -1.0, _ptr(noise), _ptr(forced),
-                                                  _ptr(token), _ptr(out_tokens), out_tokens.stride(0), _ptr(out_count), _ptr(sampled),
-                                                  _ptr(emb), _ptr(x), P, D, _stream()), "ld_llm_sample_advance_pairs")
+    check(getattr(_lib.load(), symbol)(_ptr(logits), _ptr(probs), _ptr(cfg_logits), V, int(guided), float(scale), float(temperature),
+                                       _ptr(pos), _ptr(allowed), allowed.stride(0) if allowed is not None else 0,
+                                       int(top_k) if top_k is not None else 0, float(top_p) if top_p is not None else -1.0,
+                                       _ptr(noise), _ptr(forced), _ptr(token), _ptr(out_tokens), out_tokens.stride(0), _ptr(out_count),
+                                       _ptr(sampled), _ptr(emb), _ptr(x), P, D, _stream()), symbol)
+
+
+def llm_sample_advance_pairs(logits, probs, cfg_logits, guided, scale, temperature, pos, allowed, noise, forced, token, out_tokens,
+                             out_count, sampled, emb, x, top_k=None, top_p=None):
+    """llm_sample_advance for P samples in one launch: logits [2P, V], noise / probs / cfg_logits [P, V], pos / token / out_count /
+    sampled [P], out_tokens [P, n], x [2P, D]; forced / allowed are the shared schedule (ld_llm_sample_advance_pairs)."""
+    _llm_sample_advance_many("ld_llm_sample_advance_pairs", logits, probs, cfg_logits, guided, scale, temperature, pos, allowed, noise,
+                             forced, token, out_tokens, out_count, sampled, emb, x, top_k, top_p)
 
 
 def llm_sample_advance_wide(logits, probs, cfg_logits, guided, scale, temperature, pos, allowed, noise, forced, token, out_tokens,
                             out_count, sampled, emb, x, top_k=None, top_p=None):
     """llm_sample_advance_pairs with the MFMA engine's cap, P <= LLM_MAX_WIDE (ld_llm_sample_advance_wide): the same kernel."""
-    V = logits.shape[-1]
-    P = noise.shape[0]
-    D = x.shape[1]
-    assert logits.shape[0] == 2 * P and x.shape[0] == 2 * P and out_tokens.shape[0] == P and out_tokens.stride(1) == 1
-    assert pos.numel() == P and token.numel() == P and out_count.numel() == P and (sampled is None or sampled.numel() == P)
-    for t in (logits, noise, x, probs, cfg_logits):
-        assert t is None or t.is_contiguous()
-    check(_lib.load().ld_llm_sample_advance_wide(_ptr(logits), _ptr(probs), _ptr(cfg_logits), V, int(guided), float(scale),
-                                                 float(temperature), _ptr(pos), _ptr(allowed),
-                                                 allowed.stride(0) if allowed is not None else 0,
-                                                 int(top_k) if top_k is not None else 0,
-                                                 float(top_p) if top_p is not None else -1.0, _ptr(noise), _ptr(forced),
-                                                 _ptr(token), _ptr(out_tokens), out_tokens.stride(0), _ptr(out_count), _ptr(sampled),
-                                                 _ptr(emb), _ptr(x), P, D, _stream()), "ld_llm_sample_advance_wide")
+    _llm_sample_advance_many("ld_llm_sample_advance_wide", logits, probs, cfg_logits, guided, scale, temperature, pos, allowed, noise,
+                             forced, token, out_tokens, out_count, sampled, emb, x, top_k, top_p)
+
 
 
 def llm_decode_advance(sampled, forced, pos, token, out_tokens, out_count):

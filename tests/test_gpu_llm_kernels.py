@@ -1,4 +1,5 @@
-"""The kernels of landiff_amd/csrc/ld_llm.hip that the AR model's prefill runs, and the small ones around every step, each against a
+"""The kernels of landiff_amd/csrc/ld_llm_attn.hip, ld_llm_sample.hip and ld_llm.hip that the AR model's prefill runs, and the small
+ones around every step, each against a
 plain torch reference of its own -- the model-level tests reach them only through the last row's CFG logits after 2 to 24 blocks
 (err < max(2 x bf16-oracle floor, 2e-2)), a bound that a missing bf16 rounding, a key too many, a position off by one for j > 0, a
 wrong head stride at H != 16 or a one-pass variance all stay inside.
@@ -10,7 +11,7 @@ wrong head stride at H != 16 or a one-pass variance all stay inside.
   * ld_layernorm_bf16_to_f32, the register kernel and the three-pass kernel, against fp64 F.layer_norm;
   * ld_llm_embed bit for bit; ld_llm_logits_to_probs at a restricted position (lm_model.py:417-454).
 
-ld_llm.hip is built with -ffp-contract=off -fno-slp-vectorize, so its plain fp32 arithmetic can be restated in torch bit for bit.
+The ld_llm*.hip files are built with -ffp-contract=off -fno-slp-vectorize, so their plain fp32 arithmetic can be restated in torch bit for bit.
 Output and cache buffers start as NaN (or a known bit pattern) and bf16 tensors are compared as int16, so that a stray write shows."""
 import functools
 import os

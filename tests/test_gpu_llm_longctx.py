@@ -121,7 +121,7 @@ def test_decode_is_unaffected_by_attention_launches_sharing_the_gpu(cuda):
     quiet GPU -- logits off by up to 2 of 30 from the prefill on.  tools/llm_race_probe2.py traced it to ld_llm_rope_append: the
     compiler's SLP vectoriser had packed RoPE's two dot products into v_pk_mul_f32 / v_pk_add_f32 with op_sel / neg modifiers, and
     those came out one fp32 rounding different while the 64-row attention kernel's MFMA waves shared the SIMD (never alone, never
-    beside the GEMM or the plain attention kernel).  ld_llm.hip is built with -fno-slp-vectorize since (csrc/build.sh).  Here: the
+    beside the GEMM or the plain attention kernel).  The ld_llm*.hip files are built with -fno-slp-vectorize since (csrc/build.sh).  Here: the
     full-width decoder cut to 4 blocks, one frame's decode on a side stream from a helper thread, quiet and under back-to-back
     attention launches of the DiT shape -- the CFG logits of every step and the ids must be identical, and so must the attention
     output."""

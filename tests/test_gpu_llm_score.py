@@ -163,6 +163,45 @@ def test_token_logprobs_consistent_with_sampling_kernel(cuda):
     assert checked >= 20 and removed >= 5, (checked, removed)
 
 
+@pytest.mark.parametrize("case", ["plain", "top_k_tie", "top_p", "restricted"])
+def test_token_logprobs_support_equals_sampling_kernel(cuda, case):
+    """The scorer and the sampler state one distribution (csrc/ld_llm_sample_dev.h), so their supports are the same set, id for id:
+    over EVERY id of a row as the target, logprob is finite exactly where ld_llm_logits_to_probs gives a non-zero probability and
+    -inf where a filter or the restriction gave 0.  V = 70 is no multiple of 64 (the last wave is partly idle in both block
+    reductions); four rows of guided logits small enough that no kept probability underflows.  plain: neither filter, all 70 ids;
+    top_k_tie: top-k = 5 with the 5th and 6th largest guided logits equal, 6 ids; top_p: 0.9; restricted: 3 allowed ids."""
+    from landiff_amd import ops
+    V, rows, scale, temperature, position = 70, 4, 7.5, 0.9, 3
+    g = torch.Generator().manual_seed(70)
+    cond, uncond = 0.5 * torch.randn(rows, V, generator=g), 0.5 * torch.randn(rows, V, generator=g)
+    if case == "top_k_tie":
+        order = (uncond + scale * (cond - uncond)).argsort(1, descending=True)
+        for r in range(rows):                                             # equal operands: the guided logits tie bit for bit
+            cond[r, order[r, 5]], uncond[r, order[r, 5]] = cond[r, order[r, 4]], uncond[r, order[r, 4]]
+    allowed = torch.zeros(position + 2, 4, dtype=torch.int32)
+    if case == "restricted":
+        allowed[position + 1] = torch.tensor([3, 69, 0, 41], dtype=torch.int32)
+    kw = dict(top_k=5 if case == "top_k_tie" else None, top_p=0.9 if case == "top_p" else None)
+    cond, uncond, allowed = cond.to(cuda), uncond.to(cuda), allowed.to(cuda)
+    pos = torch.tensor([position], device=cuda, dtype=torch.int32)
+    targets = torch.arange(V, device=cuda)
+    for r in range(rows):
+        probs = torch.full((1, V), NAN, device=cuda)
+        ops.llm_logits_to_probs(torch.stack([cond[r], uncond[r]]), probs, None, True, scale, temperature, pos, allowed, **kw)
+        lp = torch.full((V,), NAN, device=cuda)
+        ops.llm_token_logprobs(cond[r:r + 1].expand(V, V), uncond[r:r + 1].expand(V, V), targets, lp, True, scale, temperature,
+                               pos=pos, pos_stride=0, allowed=allowed, **kw)
+        kept = probs[0] > 0
+        print(f"{case} row {r}: sampler support {int(kept.sum())} ids, scorer finite {int(torch.isfinite(lp).sum())}")
+        assert not torch.isnan(probs).any() and not torch.isnan(lp).any()
+        assert torch.equal(torch.isfinite(lp), kept), (case, r, kept.nonzero().flatten().tolist(), torch.isfinite(lp).nonzero().flatten().tolist())
+        assert bool((lp[~kept] == -math.inf).all())
+        n = int(kept.sum())
+        assert n == {"plain": V, "top_k_tie": 6, "restricted": 3}.get(case, n) and 0 < n < (V if case == "top_p" else V + 1), (case, r, n)
+        if case == "restricted":
+            assert kept.nonzero().flatten().tolist() == [0, 41, 69]
+
+
 # ---- ld_llm_head_f32 -------------------------------------------------------------------------------------------------
 _HEAD = {}
 

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Register / occupancy table of one kernel file: tools/kernel_resources.sh ld_llm.hip [filter] [extra hipcc flags]
+# Register / occupancy table of one kernel file: tools/kernel_resources.sh ld_llm_gemv.hip [filter] [extra hipcc flags]
 f=$1; filt=${2:-.}; shift; shift
 cd "$(dirname "$0")/../landiff_amd/csrc"
 hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC "$@" -Rpass-analysis=kernel-resource-usage -c $f -o /tmp/ra_$$.o 2>&1 \
