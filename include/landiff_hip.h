@@ -31,8 +31,8 @@ extern "C" {
  * ld_vae_enc_downsample and ld_vae_posterior were added.  12: ld_vit_patch_rows, ld_vit_embed and ld_vit_tail were added,
  * ld_qkv_split gained mode 2.  13: ld_gemm_route was added.  14: ld_gemv_pairs, ld_llm_decode_forward_pairs and
  * ld_llm_sample_advance_pairs were added.  15: ld_llm_token_logprobs and ld_llm_head_f32 were added;
- * ld_gemv_wide, ld_llm_decode_forward_wide and ld_llm_sample_advance_wide joined later (additions do not change the number: no
- * existing signature moved). */
+ * ld_gemv_wide, ld_llm_decode_forward_wide and ld_llm_sample_advance_wide joined later, and so did ld_absdiff_sums,
+ * ld_residual_sub and ld_residual_add (additions do not change the number: no existing signature moved). */
 #define LD_ABI_VERSION 15
 
 int ld_version(void);
@@ -575,6 +575,24 @@ int ld_to_uint8(const void* x, int64_t ldx, uint8_t* out, float* video, int64_t 
  * (dif_infer.py:251 `1/scale_factor * latent` on the bf16 samples). */
 int ld_latent_to_cl(const float* x, void* out, int64_t T, int64_t C, int64_t H, int64_t W, int64_t Cpad, float mul,
                     int32_t src_tchw, void* stream);
+
+/* ---- DiT step cache (ld_dit_cache.hip; landiff_amd/dit_cache.py).  No reference op site: the reference evaluates every
+ * sampler step.  n >= 1 elements of bf16, any n; pointers that are 16-byte aligned take the 16-byte path.  The sums are fp32,
+ * reproducible bit for bit (fixed grid = f(n), fixed-order two-stage reduction through `workspace`, no atomics);
+ * workspace: LD_DIT_CACHE_WS_FLOATS floats of device memory, free for reuse once the call's launches have run. ---- */
+#define LD_DIT_CACHE_WS_FLOATS 4096
+
+/* out[0] = Sum|cur - prev|, out[1] = Sum|prev| (device memory); update_prev != 0: the same pass writes prev <- cur (the sums
+ * are those against the OLD prev). */
+int ld_absdiff_sums(const void* cur, void* prev, int64_t n, float* out, float* workspace, int32_t update_prev, void* stream);
+
+/* out = bf16(float(a) - float(b)).  old (optional, may be the buffer `out` overwrites): out2[0] = Sum|out - old|,
+ * out2[1] = Sum|old| with `out` as rounded; out2 and workspace are needed only with old. */
+int ld_residual_sub(const void* a, const void* b, void* out, int64_t n, const void* old, float* out2, float* workspace,
+                    void* stream);
+
+/* out = bf16(float(a) + float(r)); out == a is allowed. */
+int ld_residual_add(const void* a, const void* r, void* out, int64_t n, void* stream);
 
 /* ---- 3D-VAE encoder (ld_vae_enc.hip; ContextParallelEncoder3D, cp_enc_dec.py:785-911, + DiagonalGaussianRegularizer,
  * regularizers.py:10-28,96-114).  Its convolutions, GroupNorms and residual adds are ld_conv_cl_bf16[_gn] / ld_groupnorm_*. ---- */

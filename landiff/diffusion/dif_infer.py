@@ -13,6 +13,7 @@ from landiff.utils import set_seed_for_single_process, stable_hash
 from landiff_amd.config import DiffusionInferConfig, load_diffusion_config
 from landiff_amd.detokenizer import Detokenizer
 from landiff_amd.dit import ControlDiTRunner
+from landiff_amd.dit_cache import as_config
 from landiff_amd.sampler import DiffusionSampler
 from landiff_amd.text import encode_t5_v11
 from landiff_amd.vae import VAEDecoder
@@ -61,7 +62,7 @@ class CogWrapper(torch.nn.Module):
     used only when forward() gets no seed (then hashed with the prompt, :190-194)."""
 
     def __init__(self, cfg: DiffusionInferConfig, ckpt_path: str, device, seed: int = 1234, text_encoder=None,
-                 feature_extractor=None, theia_ckpt: str | None = None):
+                 feature_extractor=None, theia_ckpt: str | None = None, dit_cache=None):
         super().__init__()
         if feature_extractor is not None and theia_ckpt is not None:
             raise ValueError("give the Theia extractor as one of feature_extractor and theia_ckpt")
@@ -75,8 +76,11 @@ class CogWrapper(torch.nn.Module):
         st = load_diffusion_states(resolve_ckpt_path(ckpt_path), None, base_dit_ckpt=cfg.base_dit_ckpt, vae_ckpt=cfg.vae_ckpt,
                                    tokenizer_ckpt=cfg.tokenizer_ckpt or None)
         self.detok = Detokenizer(st["tok"], st["ups"], cfg.tok, cfg.ups, device)
-        self.dit = ControlDiTRunner(st["dit_main"], st["dit_control"], cfg.dit, device)
         self.sampler = DiffusionSampler(cfg.sampler)
+        # dit_cache (not in the reference): None, a threshold or a landiff_amd.dit_cache.StepCacheConfig -- the DiT step cache
+        self.dit_cache = as_config(dit_cache)
+        self.dit = ControlDiTRunner(st["dit_main"], st["dit_control"], cfg.dit, device, step_cache=self.dit_cache,
+                                    plan_timesteps=[sp.timestep for sp in self.sampler.plan] if self.dit_cache is not None else None)
         self.vae = VAEDecoder(st["vae"], cfg.vae, device)
         self._encoder = None            # tokenizer encoder half: built on the first video-conditioned call
         self._vae_encoder = None        # 3D-VAE encoder: built on the first encode_first_stage call
@@ -190,16 +194,22 @@ class CogModelInferWrapper(torch.nn.Module):
     [3, 4T-3, H, W] in [0,1] on CPU (dif_infer.py:274-302).
     text_encoder: optional callable prompts -> [1, text_length, 4096] T5 states (pre-computed embeddings) replacing the
     T5-v1.1-XXL run; feature_extractor: the Theia backbone for VideoTask.mp4 (see CogWrapper._semantic_from_video), or
-    theia_ckpt: a Theia model.safetensors (or its directory) that the HIP extractor is built from (landiff_amd.theia)."""
+    theia_ckpt: a Theia model.safetensors (or its directory) that the HIP extractor is built from (landiff_amd.theia).
+    dit_cache: None, a threshold or a landiff_amd.dit_cache.StepCacheConfig -- the opt-in DiT step cache (not in the reference)."""
 
     def __init__(self, ckpt_path: str, infer_cfg_path: str = DEFAULT_INFER_CFG, model_cfg_path: str = DEFAULT_MODEL_CFG,
-                 device="cuda", text_encoder=None, feature_extractor=None, theia_ckpt: str | None = None):
+                 device="cuda", text_encoder=None, feature_extractor=None, theia_ckpt: str | None = None, dit_cache=None):
         super().__init__()
         self.infer_cfg_path, self.model_cfg_path, self.ckpt_path = infer_cfg_path, model_cfg_path, ckpt_path
         cfg = load_diffusion_config(_cfg_path(model_cfg_path), _cfg_path(infer_cfg_path))
         dev = torch.device(device if device != "cuda" else f"cuda:{torch.cuda.current_device()}")
         self.init_infer_model = CogWrapper(cfg, ckpt_path, dev, text_encoder=text_encoder, feature_extractor=feature_extractor,
-                                           theia_ckpt=theia_ckpt)
+                                           theia_ckpt=theia_ckpt, dit_cache=dit_cache)
+
+    def dit_cache_report(self):
+        """dit_cache: the step cache's report of the last forward() (ControlDiTRunner.cache_report), else None."""
+        m = self.init_infer_model
+        return [dict(r) for r in m.dit.cache_report] if m.dit_cache is not None else None
 
     @torch.no_grad()
     def forward(self, x: VideoTask) -> VideoTask:

@@ -50,7 +50,20 @@ def parse_args(argv=None):
     parser.add_argument("--first_frame", type=str, default=None,
                         help="Image-guided generation (use_gt_first_frame): a uint8 [H, W, 3] .npy or an image imageio can "
                              "read, tokenized by the Theia extractor; its I-frame tokens start the AR decode.")
+    parser.add_argument("--dit_cache", type=str, default=None, metavar="THRESH",
+                        help="DiT step cache (off by default): a sampler step whose first-block input moved by less than THRESH "
+                             "(accumulated relative L1, a float >= 0) since the last computed step reuses that step's residual across "
+                             "the transformer stack instead of running it.  0 computes every step.  What each step did is written "
+                             "to <save_file_name>_dit_cache.json.  The quality at a given threshold is not measured.")
     args = parser.parse_args(argv)
+    if args.dit_cache is not None:
+        import math
+        try:
+            args.dit_cache = float(args.dit_cache)
+        except ValueError:
+            parser.error(f"--dit_cache takes a float >= 0, got {args.dit_cache!r}")
+        if math.isnan(args.dit_cache) or args.dit_cache < 0:
+            parser.error(f"--dit_cache takes a float >= 0, got {args.dit_cache!r}")
     max_n = 16 if args.decode_engine == "mfma" else 4
     if not 1 <= args.num_samples <= max_n:
         parser.error(f"--num_samples must be between 1 and {max_n}" + ("" if max_n == 16 else " (1 and 16 with --decode_engine mfma)"))
@@ -165,22 +178,41 @@ def llm_infer_samples(args):
     return tokens.cuda(), kept
 
 
+def _diffusion_model(args):
+    """CogModelInferWrapper of the run; --dit_cache is handed on only when given (without it the call is the reference's)."""
+    if getattr(args, "dit_cache", None) is None:
+        return CogModelInferWrapper(ckpt_path=args.diffusion_ckpt)
+    return CogModelInferWrapper(ckpt_path=args.diffusion_ckpt, dit_cache=args.dit_cache)
+
+
+def _write_dit_cache_report(args, stem, report):
+    """--dit_cache: <stem>_dit_cache.json, what the step cache did in the run that produced <stem>.mp4."""
+    if getattr(args, "dit_cache", None) is None:
+        return
+    from landiff_amd.dit_cache import write_report_json
+    path = Path(f"{stem}_dit_cache.json")
+    path.parent.mkdir(parents=True, exist_ok=True)
+    write_report_json(str(path), report)
+
+
 def infer_diffusion_samples(args, tokens, kept=None):
     """kept (--keep): the candidate indices to run, in rank order; None: every candidate."""
-    model = CogModelInferWrapper(ckpt_path=args.diffusion_ckpt)
+    model = _diffusion_model(args)
     names = sample_names(args)
     for i in (range(len(names)) if kept is None else kept):
         row, (seed, stem) = tokens[i], names[i]
         task = model(VideoTask(save_file_name=f"{stem}.mp4", prompt=args.prompt, seed=seed, fps=8, semantic_token=row))
+        _write_dit_cache_report(args, stem, model.dit_cache_report() if args.dit_cache is not None else None)
         save_video_tensor(task.result, task.save_file_name, fps=task.fps)
         print(f"save video to {task.save_file_name}")
 
 
 def infer_diffusion(args, semantic_token):
-    model = CogModelInferWrapper(ckpt_path=args.diffusion_ckpt)
+    model = _diffusion_model(args)
     task = VideoTask(save_file_name=f"{args.save_file_name}.mp4", prompt=args.prompt, seed=args.seed, fps=8,
                      semantic_token=semantic_token)
     task = model(task)
+    _write_dit_cache_report(args, args.save_file_name, model.dit_cache_report() if args.dit_cache is not None else None)
     save_video_tensor(task.result, task.save_file_name, fps=task.fps)
     print(f"save video to {task.save_file_name}")
 
@@ -220,7 +252,7 @@ def build_continuation(args):
     c = cfg.llm
     # the clip is chunk 0 of the stream: its multi-segment AR decode needs n_seg segments of KV cache
     _, _, n_seg = stream_plan(cfg, args.extend_chunks + 1, args.extend_prefix_frames)
-    pipe = LanDiffPipeline(cfg, st, dev, max_llm_frames=n_seg * c.segment_length)
+    pipe = LanDiffPipeline(cfg, st, dev, max_llm_frames=n_seg * c.segment_length, dit_cache=getattr(args, "dit_cache", None))
     text = encode_flan_t5([args.prompt], dev, max_length=c.max_cond_tokens, model_path=c.text_encoder_path)[0]
     ctx = encode_t5_v11([args.prompt], resolve_ckpt_path(dcfg.t5_dir), cfg.dit.text_len, dev)
     inp = PromptInputs(text, ctx, seed=args.seed, cfg=args.cfg, motion_score=args.motion_score)
@@ -243,6 +275,7 @@ def extend_diffusion(args):
         clip_tokens = "from_frames" if args.theia_ckpt else None
     new = pipe.extend_video(inp, args.extend_chunks, frames=clip, clip_tokens=clip_tokens,
                             prefix_frames=args.extend_prefix_frames)
+    _write_dit_cache_report(args, args.save_file_name, pipe.dit_cache_reports)        # one list per appended chunk
     frames = torch.cat([clip, new.cpu()], dim=0)
     path = f"{args.save_file_name}.mp4"
     save_video_tensor(frames, path, fps=8)

@@ -16,6 +16,7 @@ import torch
 
 from . import ops
 from .config import DiTConfig
+from .dit_cache import StepCacheConfig, StepCachePolicy
 
 BF = torch.bfloat16
 
@@ -79,7 +80,7 @@ class ControlDiTRunner:
     B = 2
 
     def __init__(self, main_sd: dict, control_sd: dict, cfg: DiTConfig, device, fp8_gemm: bool = False,
-                 attn_exact: "bool | str | None" = None):
+                 attn_exact: "bool | str | None" = None, step_cache: "StepCacheConfig | None" = None, plan_timesteps=None):
         """fp8_gemm: BASELINE configs[4] -- the qkv / dense / 4h / 4h->h linears run on e4m3 operands; attention, norms,
         residual stream and every other layer stay bf16.  True / "row": weights quantised once per output channel,
         activations per row by a pass in front of each GEMM.  "mx": MXFP8 (one power-of-two scale per 32 K elements, applied
@@ -161,6 +162,11 @@ class ControlDiTRunner:
             self._attn_blocks = B * c.heads * ((self.Npad + 255) // 256)
         self.attn_events = None                 # bench.py: list of (start, end, solo) HIP events around every attention launch
         self.gemm_events = None                 # bench.py: list of (start, end, flops) around the large linears (qkv, dense, 4h, 4h->h, zero)
+        # step_cache (landiff_amd/dit_cache.py; None = off: nothing below is allocated and step() is the code path it always was):
+        # skip the transformer stack of a sampler step whose first-block input barely moved, see _step_cached()
+        self._sc = None
+        if step_cache is not None:
+            self._init_step_cache(step_cache, plan_timesteps)
 
     def _use(self, i: int):
         """Select the workspace set the layer methods read through self.ln / self.q / ... (set 1 exists only when the two chains overlap)."""
@@ -178,6 +184,7 @@ class ControlDiTRunner:
             for b in range(self.B):   # text_proj + position rows (zero in the shipped table, added all the same)
                 ops.gemm(ctx[b], br.text_w, out=dst[b], bias=br.text_b, add2=br.pos[: c.text_len])
         self.sem = semantic_feature.to(self.dev, BF).contiguous()
+        self.reset_step_cache()
 
     # ---- pieces ----------------------------------------------------------------------------
     def _time_emb(self, br: _Branch, timestep: float):
@@ -383,10 +390,123 @@ class ControlDiTRunner:
             if i < c.layers_control:
                 main_s.wait_event(self._ctrl_done[i])
             self._layer(self.main, i, self.h, self.h, self.ctrl_out[i] if i < c.layers_control else None)
+        if self._sc is not None:
+            self._sc_keep_residual()
         return self._final(self.h, x, c_out, c_skip, cfg_scale, out)
+
+    # ---- step cache ------------------------------------------------------------------------
+    def _init_step_cache(self, step_cache: StepCacheConfig, plan_timesteps):
+        if plan_timesteps is None:
+            raise ValueError("ControlDiTRunner(step_cache=...) needs plan_timesteps (the timesteps of schedule.build_plan, in sampler order): "
+                             "a step is identified by the position of its timestep")
+        ts = [float(t) for t in plan_timesteps]
+        if len(set(ts)) != len(ts) or len(ts) < 1:
+            raise ValueError("plan_timesteps must be distinct")
+        if step_cache.plan is not None and len(step_cache.plan) != len(ts):
+            raise ValueError(f"StepCacheConfig.plan has {len(step_cache.plan)} entries for {len(ts)} timesteps")
+        self._sc = StepCachePolicy(step_cache)
+        self._sc_index = {t: i for i, t in enumerate(ts)}
+        e = lambda *s, dt=BF: torch.empty(*s, device=self.dev, dtype=dt)
+        M, d, S = self.M, self.cfg.hidden, len(ts)
+        self.sc_prev_mod = e(M, d)                  # main layer 0's modulated LN1 output of the previous step
+        self.sc_h0 = e(M, d)                        # this step's embedded stream (what main layer 0 reads)
+        self.sc_residual = e(M, d)                  # the last computed step's (stack output - h0)
+        self._sc_sums = e(2, dt=torch.float32)      # indicator sums; the output-side pair of step s in row s of _sc_out
+        self._sc_out = torch.zeros(S, 2, device=self.dev, dtype=torch.float32)
+        self._sc_ws = e(ops.DIT_CACHE_WS_FLOATS, dt=torch.float32)
+        self._sc_host = torch.zeros(2, dtype=torch.float32).pin_memory()
+        self._sc_out_host = torch.zeros(S, 2, dtype=torch.float32).pin_memory()
+        self._sc_ev, self._sc_out_ev = torch.cuda.Event(), torch.cuda.Event()
+        self._sc_report, self._sc_pending = [], []
+        self.reset_step_cache()
+
+    def reset_step_cache(self):
+        """Forget the cached residual, the accumulated change and the previous step's input: the next step is computed, and the steps
+        after it depend on nothing that ran before this call.  (set_condition() and a timestep that does not decrease do the same.)"""
+        if self._sc is None:
+            return
+        self._sc_resolve()
+        self._sc.reset()
+        self._sc_have_prev = self._sc_have_residual = False
+        self._sc_last_t = None
+        self._sc_report = []
+
+    def _sc_resolve(self):
+        """Fill the output-side figures of report entries whose device sums were still on their way."""
+        if self._sc_pending:
+            self._sc_out_ev.synchronize()              # (copies on one stream complete in order: the last event covers all)
+            for row in self._sc_pending:
+                num, den = (float(v) for v in self._sc_out_host[row["index"]])
+                row["output_rel_l1"] = num / den if den != 0.0 else None
+            self._sc_pending = []
+
+    @property
+    def cache_report(self) -> list:
+        """One dict per step since the last reset: index, timestep, input_rel_l1 (None without a previous input), accumulated,
+        computed, output_rel_l1 (relative L1 change of the residual, on computed steps that replaced an older one; else None)."""
+        if self._sc is None:
+            return []
+        self._sc_resolve()
+        return self._sc_report
+
+    def _sc_keep_residual(self):
+        """Computed step, after the last main layer: residual = h - h0 (and, in the same pass, how far it moved from the older one)."""
+        if self._sc_have_residual:
+            row = self._sc_report[-1]
+            ops.residual_sub(self.h, self.sc_h0, self.sc_residual, old=self.sc_residual, out2=self._sc_out[row["index"]], workspace=self._sc_ws)
+            self._sc_out_host[row["index"]].copy_(self._sc_out[row["index"]], non_blocking=True)
+            self._sc_out_ev.record()
+            self._sc_pending.append(row)
+        else:
+            ops.residual_sub(self.h, self.sc_h0, self.sc_residual)
+        self._sc_have_residual = True
+
+    def _step_cached(self, x, timestep, c_out, c_skip, cfg_scale, out):
+        """step() with the cache on.  The indicator first: the main branch's time embedding and patch / text embedding (into sc_h0),
+        main layer 0's LayerNorm + modulate of it (the bf16 launch of _layer, in the fp8 modes too), its L1 distance from the previous
+        step's in one pass that also keeps it for the next step, two floats to the host, the policy.  A computed step then runs
+        _step() as it stands -- every launch of the uncached step in its order, so the same bits -- and keeps h - sc_h0 before
+        _final; a skipped step launches no layer on either stream: h = sc_h0 + residual, then _final.  -> (out, computed)."""
+        c, m, d = self.cfg, self.main, self.cfg.hidden
+        t = float(timestep)
+        if t not in self._sc_index:
+            raise ValueError(f"timestep {timestep} is not one of plan_timesteps")
+        if self._sc_last_t is not None and not t < self._sc_last_t:
+            self.reset_step_cache()                       # a new sampler run: the result depends on this run's inputs alone
+        self._sc_last_t = t
+        s, S = self._sc_index[t], len(self._sc_index)
+        self._use(0)
+        self._time_emb(m, timestep)
+        self._embed(m, x, self.sc_h0, self.txt_main, None)
+        ada, ada_bs = self._ada(m, 0)
+        lw = m.layers[0]
+        ops.layernorm(self.sc_h0, lw["ln1_w"], lw["ln1_b"], self.ln, c.block_ln_eps, shift_img=0, scale_img=d, shift_txt=6 * d,
+                      scale_txt=7 * d, mod=ada, mod_bstride=ada_bs, rows_per_batch=self.N, text_len=c.text_len)
+        sums = (None, None)
+        if self._sc_have_prev:
+            ops.absdiff_sums(self.ln, self.sc_prev_mod, out=self._sc_sums, workspace=self._sc_ws, update_prev=True)
+            self._sc_host.copy_(self._sc_sums, non_blocking=True)
+            self._sc_ev.record()
+            self._sc_ev.synchronize()                     # this copy alone: the policy needs the two floats
+            sums = (float(self._sc_host[0]), float(self._sc_host[1]))
+        else:
+            self.sc_prev_mod.copy_(self.ln)
+            self._sc_have_prev = True
+        dec = self._sc.decide(s, S, sums[0], sums[1], self._sc_have_residual)
+        self._sc_report.append(dict(index=s, timestep=timestep, input_rel_l1=dec.input_rel_l1, accumulated=dec.accumulated,
+                                    computed=dec.computed, output_rel_l1=None))
+        if dec.computed:
+            return self._step(x, timestep, c_out, c_skip, cfg_scale, out), True
+        ops.residual_add(self.sc_h0, self.sc_residual, self.h)
+        return self._final(self.h, x, c_out, c_skip, cfg_scale, out), False
 
     def step(self, x: torch.Tensor, timestep: int, c_out: float, c_skip: float, cfg_scale: float, out: torch.Tensor):
         """x, out: [1, T, C, H, W] fp32.  out = CFG(denoised_uncond, denoised_cond)."""
+        if self._sc is not None:
+            r, computed = self._step_cached(x, timestep, c_out, c_skip, cfg_scale, out)
+            if self.attn_auto and computed:               # (a skipped step launched no attention: no new counts)
+                self._attn_auto_end_of_step()
+            return r
         r = self._step(x, timestep, c_out, c_skip, cfg_scale, out)
         if self.attn_auto:
             self._attn_auto_end_of_step()
@@ -401,4 +521,6 @@ class ControlDiTRunner:
         self._time_emb(self.main, timestep)
         self._embed(self.main, x, self.h, self.txt_main, None)
         self._main_chain()
+        if self._sc is not None:
+            self._sc_keep_residual()
         return self._final(self.h, x, c_out, c_skip, cfg_scale, out)

@@ -696,6 +696,68 @@ def latent_to_cl(x, out, T, C, H, W, Cpad, mul, src_tchw):
           "ld_latent_to_cl")
 
 
+# ---- DiT step cache (ld_dit_cache.hip) ---------------------------------------------------------------
+DIT_CACHE_WS_FLOATS = 4096         # LD_DIT_CACHE_WS_FLOATS of include/landiff_hip.h
+
+
+def _cache_operands(name, *tensors):
+    """Same-shape contiguous bf16 tensors (None entries skipped) -> their element count."""
+    first = tensors[0]
+    for t in tensors:
+        if t is None:
+            continue
+        _bf16(t, name)
+        if not t.is_contiguous() or t.shape != first.shape:
+            raise ValueError(f"{name}: operands must be contiguous and of one shape, got {tuple(t.shape)} beside {tuple(first.shape)}")
+    if first.numel() < 1:
+        raise ValueError(f"{name}: empty operands")
+    return first.numel()
+
+
+def _cache_sums(name, out, workspace, device):
+    if out is None:
+        out = torch.empty(2, device=device, dtype=torch.float32)
+    if workspace is None:
+        workspace = torch.empty(DIT_CACHE_WS_FLOATS, device=device, dtype=torch.float32)
+    for t, n in ((out, 2), (workspace, DIT_CACHE_WS_FLOATS)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n:
+            raise ValueError(f"{name}: out / workspace must be contiguous float32 of at least 2 / {DIT_CACHE_WS_FLOATS} elements")
+    return out, workspace
+
+
+def absdiff_sums(cur, prev, out=None, workspace=None, update_prev=False):
+    """out f32 [2] = (sum|cur - prev|, sum|prev|) over bf16 tensors of one shape, fp32 sums that repeat bit for bit.
+    update_prev: the same pass writes prev <- cur (the sums are those against the old prev)."""
+    n = _cache_operands("absdiff_sums", cur, prev)
+    out, workspace = _cache_sums("absdiff_sums", out, workspace, cur.device)
+    check(_lib.load().ld_absdiff_sums(_ptr(cur), _ptr(prev), n, _ptr(out), _ptr(workspace), int(bool(update_prev)), _stream()),
+          "ld_absdiff_sums")
+    return out
+
+
+def residual_sub(a, b, out=None, old=None, out2=None, workspace=None):
+    """out = bf16(float(a) - float(b)).  With old (which may be `out` itself, read before it is overwritten): returns
+    (out, out2) with out2 f32 [2] = (sum|out - old|, sum|old|); without: returns out."""
+    if out is None:
+        out = torch.empty_like(a)
+    n = _cache_operands("residual_sub", a, b, out, old)
+    if old is None:
+        check(_lib.load().ld_residual_sub(_ptr(a), _ptr(b), _ptr(out), n, None, None, None, _stream()), "ld_residual_sub")
+        return out
+    out2, workspace = _cache_sums("residual_sub", out2, workspace, a.device)
+    check(_lib.load().ld_residual_sub(_ptr(a), _ptr(b), _ptr(out), n, _ptr(old), _ptr(out2), _ptr(workspace), _stream()),
+          "ld_residual_sub")
+    return out, out2
+
+
+def residual_add(a, r, out=None):
+    """out = bf16(float(a) + float(r)); out may be a (in place)."""
+    if out is None:
+        out = torch.empty_like(a)
+    n = _cache_operands("residual_add", a, r, out)
+    check(_lib.load().ld_residual_add(_ptr(a), _ptr(r), _ptr(out), n, _stream()), "ld_residual_add")
+    return out
+
 
 # ---- 3D-VAE encoder (ld_vae_enc.hip) ----------------------------------------------------------------
 def vae_enc_place_input(frames, out_padded):

@@ -18,6 +18,7 @@ from . import _lib
 from .config import PipelineConfig
 from .detokenizer import Detokenizer
 from .dit import ControlDiTRunner
+from .dit_cache import as_config
 from .llm import LLMRunner
 from .sampler import DiffusionSampler
 from .vae import VAEDecoder
@@ -41,7 +42,7 @@ class PromptInputs:
 
 class LanDiffPipeline:
     def __init__(self, cfg: PipelineConfig, states: dict, device="cuda:0", max_llm_frames: int | None = None,
-                 fp8_gemm: bool = False, theia=None, max_samples: int = 1, wide_samples: int = 0):
+                 fp8_gemm: bool = False, theia=None, max_samples: int = 1, wide_samples: int = 0, dit_cache=None):
         if not torch.cuda.is_available():
             raise _lib.LandiffHipError("LanDiffPipeline needs an MI355X GPU: there is no CPU fallback")
         _lib.load()
@@ -55,8 +56,15 @@ class LanDiffPipeline:
                              max_samples=max_samples, wide_samples=wide_samples) if "llm" in states else None
         self.detok = Detokenizer(states["tok"], states["ups"], cfg.tok, cfg.ups, self.dev)
         # fp8_gemm: BASELINE configs[4] (e4m3 operands for the DiT's four large linears); never the headline configuration
-        self.dit = ControlDiTRunner(states["dit_main"], states["dit_control"], cfg.dit, self.dev, fp8_gemm=fp8_gemm)
+        # dit_cache: None (off), a threshold or a dit_cache.StepCacheConfig -- sampler steps whose first-block input barely moved reuse
+        # the last computed step's residual across the transformer stack (ControlDiTRunner(step_cache=...)); never the headline
+        # configuration, and what a threshold costs in quality on a trained checkpoint is not measured
         self.sampler = DiffusionSampler(cfg.sampler)
+        self.dit_cache = as_config(dit_cache)
+        self.dit = ControlDiTRunner(states["dit_main"], states["dit_control"], cfg.dit, self.dev, fp8_gemm=fp8_gemm,
+                                    step_cache=self.dit_cache,
+                                    plan_timesteps=[sp.timestep for sp in self.sampler.plan] if self.dit_cache is not None else None)
+        self.dit_cache_reports = []       # one ControlDiTRunner.cache_report per sampler run (see dit_cache_report())
         self.vae = VAEDecoder(states["vae"], cfg.vae, self.dev)
         # the 3D-VAE encoder of extend_video(frames=...): built when the VAE state carries 'encoder.*' keys
         # (weights.load_vae_encoder_state, or a synthetic tree whose states["vae"] has them)
@@ -93,9 +101,24 @@ class LanDiffPipeline:
         t0 = time.perf_counter()
         if noise is None:
             noise = torch.randn(1, d.latent_frames, d.in_channels, d.latent_h, d.latent_w, device=self.dev, dtype=torch.float32)
-        z = self.sampler.run(self.dit.step, noise)
+        z = self._sample(noise)
         self._t("dit", t0)
         return z
+
+    def _sample(self, noise, **kw):
+        """One sampler run over the DiT (set_condition() before it has emptied the step cache); with dit_cache its report is kept."""
+        z = self.sampler.run(self.dit.step, noise, **kw)
+        if self.dit_cache is not None:
+            self.dit_cache_reports.append([dict(r) for r in self.dit.cache_report])
+        return z
+
+    def dit_cache_report(self):
+        """dit_cache: what the step cache did in the last sampler run -- one dict per step (index, timestep, input_rel_l1, accumulated,
+        computed, output_rel_l1; ControlDiTRunner.cache_report).  None with the cache off or before the first run.
+        self.dit_cache_reports holds the report of every run of the last generate_samples / generate_many / generate_stream /
+        extend_video call (one per sample, prompt or chunk; a streamed chunk is a sampler run of its own and starts with an empty
+        cache), and of every generate_latent / __call__ since."""
+        return self.dit_cache_reports[-1] if self.dit_cache_reports else None
 
     @torch.no_grad()
     def decode(self, latent: torch.Tensor, want_float: bool = False):
@@ -131,6 +154,7 @@ class LanDiffPipeline:
         near-tie of the draw that the engines' different summation orders decide differently."""
         from dataclasses import replace
         seeds = [int(s) for s in seeds]
+        self.dit_cache_reports = []
         if keep is not None and not 1 <= int(keep) <= len(seeds):
             raise ValueError(f"generate_samples: keep={keep} outside [1, {len(seeds)}] (the number of seeds)")
         kw = dict(motion_score=inp.motion_score, num_frames=self.cfg.llm.segment_length, guidance_scale=inp.cfg, temperature=1.0,
@@ -180,6 +204,7 @@ class LanDiffPipeline:
         from concurrent.futures import ThreadPoolExecutor
         if not inputs:
             return []
+        self.dit_cache_reports = []
         for inp in inputs:
             assert inp.seed, "generate_many needs a non-zero seed per prompt (a zero seed would draw from the shared default generator)"
         side = torch.cuda.Stream(device=self.dev, priority=-1)
@@ -214,7 +239,7 @@ class LanDiffPipeline:
                 sem = self.detok.semantic_condition(tokens.to(self.dev))
                 self.dit.set_condition(inp.dit_context, sem)
                 noise = torch.randn(1, d.latent_frames, d.in_channels, d.latent_h, d.latent_w, device=self.dev, dtype=torch.float32)
-                z = self.sampler.run(self.dit.step, noise)
+                z = self._sample(noise)
                 out.append(self.vae.decode(z.to(torch.bfloat16).float(), want_float=want_float))
         return out
 
@@ -263,10 +288,9 @@ class LanDiffPipeline:
         noise = noise.to(self.dev) if noise is not None else torch.randn(
             1, T, d.in_channels, d.latent_h, d.latent_w, device=self.dev, dtype=torch.float32)
         if prev is None:
-            z = self.sampler.run(self.dit.step, noise, randn_like=randn_like)
+            z = self._sample(noise, randn_like=randn_like)
         else:
-            z = self.sampler.run(self.dit.step, noise, randn_like=randn_like, prefix=prev[:, T - prefix_frames:],
-                                 fixed_frames=prefix_frames)
+            z = self._sample(noise, randn_like=randn_like, prefix=prev[:, T - prefix_frames:], fixed_frames=prefix_frames)
         first = prev is None
         prev = z.to(torch.bfloat16).float()              # samples.to(self.dtype) (diffusion_video.py:314)
         if latents_out is not None:
@@ -297,6 +321,7 @@ class LanDiffPipeline:
         d, lc = self.cfg.dit, self.cfg.llm
         T, new, n_seg = self.stream_plan(n_chunks, prefix_frames)
         per_seg = self.cfg.tok.num_latent_tokens
+        self.dit_cache_reports = []
         t0 = time.perf_counter()
         seg_tokens = None          # segment s -> its token ids, int64 [per_seg] on the device
         decode_thread = None
@@ -395,6 +420,7 @@ class LanDiffPipeline:
         d, lc = self.cfg.dit, self.cfg.llm
         T, new, n_seg = self.stream_plan(n_chunks + 1, prefix_frames)
         per_seg = self.cfg.tok.num_latent_tokens
+        self.dit_cache_reports = []
         if (frames is None) == (clip_latent is None):
             raise ValueError("extend_video takes the clip as exactly one of frames and clip_latent")
         if tokens is not None and clip_tokens is not None:
