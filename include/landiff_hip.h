@@ -192,6 +192,14 @@ int ld_layernorm_mxfp8(const void* x, int64_t ldx, const void* w, const void* b,
  * Npad % 128 == 0; rows/keys in [N, Npad) must be zero-filled.  fid_q/fid_k (int32 [Npad], or
  * both NULL) select the frame-block mask allowed(q,kv) <=> fid_k[kv] <= fid_q[q]; padding keys
  * carry INT32_MAX; kt_min/kt_max are the per-64-key-tile min/max of fid_k.
+ * Masked problems, pinned element by element in tests/test_gpu_attn_masked.py: Nq != Nk is supported (Nq query rows against
+ * Nk keys; the TiTok encoder launches its visual and its latent rows separately, the second from offset Q / fid_q / O
+ * pointers); the K and V^T padding in [Nk, Npad) must be zero, Q rows past Nq need NOT be (they are read up to Nq rounded up
+ * to 128, computed and never stored; their label is taken as fid_q[Nq - 1]); rows of O outside [0, Nq) are not touched; a
+ * query row with no visible key yields zeros, not NaN (as flex_attention does).  Masked problems and problems of fewer than
+ * 6 key tiles run the plain online-softmax kernel (ld_attn_kernel, ld_attn.hip) in this entry point and in
+ * ld_attn_fwd_bf16_exact alike.  The pipelined kernels of the other problems read Q in 256-row blocks up to row Npad - 1:
+ * do not call those with a Q pointer offset into a head (landiff_amd/ops.py: attn_fwd refuses it).
  * Replaces sat attention_fn_default/F.scaled_dot_product_attention behind AdaLNMixin.attention_fn
  * (landiff/diffusion/dit_video_concat.py:636-664) and flex_attention with VideoDecoderMask
  * (landiff/tokenizer/modules/blocks.py:172-212, flex_attention_mask.py:193-335).

@@ -91,13 +91,7 @@ class Detokenizer:
         N = tc.seq_len
         self.N, self.Npad = N, (N + 127) // 128 * 128
         fid = decoder_frame_ids(tc)
-        fq = np.zeros(self.Npad, np.int32); fq[:N] = fid
-        fk = np.full(self.Npad, np.iinfo(np.int32).max, np.int32); fk[:N] = fid
-        kt = fk.reshape(-1, 64)
-        self.fid_q = torch.from_numpy(fq).to(device)
-        self.fid_k = torch.from_numpy(fk).to(device)
-        self.kt_min = torch.from_numpy(kt.min(1).copy()).to(device)
-        self.kt_max = torch.from_numpy(kt.max(1).copy()).to(device)
+        self.fid_q, self.fid_k, self.kt_min, self.kt_max = ops.attn_mask_tables(fid, fid, self.Npad, device)
         cos, sin = rope3d_tables(tc)
         self.cos, self.sin = cos.to(device), sin.to(device)
         # upsampler weights

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -184,12 +185,35 @@ def conv_cl(x_padded: torch.Tensor, w: torch.Tensor, T: int, H: int, W: int,
     return out
 
 
+ATTN_KEY_TILE = 64                 # keys per tile of the attention kernels (kt_min / kt_max granularity)
+ATTN_PIPELINED_MIN_TILES = 6       # unmasked problems of at least this many key tiles take the pipelined kernels
+
+
+def attn_mask_tables(fid_q, fid_k, Npad: int, device=None):
+    """The four int32 arrays of ld_attn_fwd_bf16's label mask (allowed(q, kv) <=> fid_k[kv] <= fid_q[q]) from the labels of the
+    real rows: (fid_q [Npad] padded with 0, fid_k [Npad] padded with INT32_MAX so that no query sees a padding key,
+    kt_min, kt_max [Npad / 64] = the smallest / largest fid_k of each 64-key tile), as tensors on `device`."""
+    fid_q, fid_k = np.asarray(fid_q), np.asarray(fid_k)
+    assert fid_q.ndim == 1 and fid_k.ndim == 1 and Npad % 128 == 0 and len(fid_q) <= Npad and len(fid_k) <= Npad
+    fq = np.zeros(Npad, np.int32); fq[:len(fid_q)] = fid_q
+    fk = np.full(Npad, np.iinfo(np.int32).max, np.int32); fk[:len(fid_k)] = fid_k
+    kt = fk.reshape(-1, ATTN_KEY_TILE)
+    return tuple(torch.from_numpy(x).to(device) for x in (fq, fk, kt.min(1).copy(), kt.max(1).copy()))
+
+
 def attn_fwd(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, Nq: int, Nk: int,
              scale: float, fid_q=None, fid_k=None, kt_min=None, kt_max=None, q_row0: int = 0, exact: bool = False) -> torch.Tensor:
-    """q,k [B,H,Npad,64]; vt [B,H,64,Npad]; out [B,N,H*64] (bf16).  Optional frame mask arrays (int32).
+    """q,k [B,H,Npad,64]; vt [B,H,64,Npad]; out [B,N,H*64] (bf16).  Optional frame mask arrays (int32; attn_mask_tables).
     q_row0: the Nq query rows start at row q_row0 of q / fid_q / out (pointer offsets only; Npad must cover
     q_row0 + Nq rounded up to 128).  exact: ld_attn_fwd_bf16_exact -- the two-pass safe softmax at a fixed ~1.55 x, for logit
-    ranges beyond the window of the default launch's fast pass."""
+    ranges beyond the window of the default launch's fast pass.
+    q_row0 != 0 needs the label mask or fewer than 6 key tiles, i.e. the plain kernel, which reads Q rows only up to Nq rounded
+    up to 128 (the assert below keeps those inside this head's rows).  The pipelined kernels of unmasked problems of >= 6 key
+    tiles work in 256-row query blocks and clamp the Q row to Npad - 1 counted from the OFFSET pointer, so a live block could
+    read up to 128 rows past this head's rows -- past the end of the tensor for the last head: ValueError, before any launch."""
+    if q_row0 and fid_k is None and (Nk + ATTN_KEY_TILE - 1) // ATTN_KEY_TILE >= ATTN_PIPELINED_MIN_TILES:
+        raise ValueError(f"attn_fwd: q_row0={q_row0} without a label mask on {Nk} keys (>= {ATTN_PIPELINED_MIN_TILES} key tiles) "
+                         "would run a pipelined kernel that reads Q rows past the offset block")
     _bf16(q, "q"); _bf16(k, "k"); _bf16(vt, "vt"); _bf16(out, "out")
     B, H, Npad, D = q.shape
     assert D == 64 and k.shape == q.shape and tuple(vt.shape) == (B, H, 64, Npad)

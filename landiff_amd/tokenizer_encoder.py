@@ -50,6 +50,13 @@ def encoder_attention_labels(cfg: TokenizerConfig):
     return qv.astype(np.int32), kv.astype(np.int32), ql.astype(np.int32), kl.astype(np.int32)
 
 
+def encoder_padded_len(cfg: TokenizerConfig) -> int:
+    """Npad of the encoder's q / k / v^T buffers: the latent launch's 128-row query blocks start at row n_visual (which need not
+    be a multiple of 128), so the padding covers n_visual + the latent rows rounded up to 128, itself rounded up to 128."""
+    nv, nlat = cfg.n_visual, cfg.seq_len - cfg.n_visual
+    return (nv + (nlat + 127) // 128 * 128 + 127) // 128 * 128
+
+
 class TokenizerEncoder:
     def __init__(self, enc_sd: dict, tc: TokenizerConfig, device):
         self.tc, self.dev = tc, device
@@ -85,20 +92,10 @@ class TokenizerEncoder:
         self.pin_b[: tc.codebook_dim] = g("quantizer.project_in.bias")
         self.codebook = f32("quantizer._codebook.embed")[0].contiguous()             # [V, 16]
         # static tables: RoPE and the two label sets (+ per-64-key-tile min/max) of the mask
-        N, nv = tc.seq_len, tc.n_visual
-        nlat = N - nv
-        self.N = N
-        self.Npad = (nv + (nlat + 127) // 128 * 128 + 127) // 128 * 128               # latent q-blocks start at row n_visual
+        self.N = tc.seq_len
+        self.Npad = encoder_padded_len(tc)
         qv, kv, ql, kl = encoder_attention_labels(tc)
-        def padded(a, fill):
-            out = np.full(self.Npad, fill, np.int32); out[:N] = a
-            return out
-        self.labels = []
-        for fq, fk in ((qv, kv), (ql, kl)):
-            fkp = padded(fk, INF)
-            kt = fkp.reshape(-1, 64)
-            self.labels.append(tuple(torch.from_numpy(x).to(device) for x in
-                                     (padded(fq, 0), fkp, kt.min(1).copy(), kt.max(1).copy())))
+        self.labels = [ops.attn_mask_tables(fq, fk, self.Npad, device) for fq, fk in ((qv, kv), (ql, kl))]
         cos, sin = rope3d_tables(tc)
         self.cos, self.sin = cos.to(device), sin.to(device)
 

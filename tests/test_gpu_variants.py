@@ -49,6 +49,20 @@ for (B, H, N) in [(1, 2, 1122), (2, 1, 1400), (1, 1, 2175)]:
     s = (q.float() @ k.float().transpose(-1, -2)) * 0.125
     ref = (torch.softmax(s, -1) @ v.float()).permute(0, 2, 1, 3).reshape(B, N, H * 64)
     worst = max(worst, torch.nan_to_num((out.float() - ref).abs(), nan=1e9).max().item())      # (max(x, nan) would drop a NaN)
+# a masked problem (the 500-token TiTok decoder layout): every knob takes the plain kernel there, LD_ATTN_VARIANT=1 / 4 change its instantiation
+import numpy as np
+T, tpf, nI, nP = 5, 90, 22, 7
+fid = np.concatenate([np.repeat(np.arange(T), tpf), np.zeros(nI, np.int64), np.repeat(np.arange(1, T), nP)]).astype(np.int32)
+H, N, Npad = 2, len(fid), 512
+q = torch.randn(1, H, N, 64).cuda().bfloat16(); k = torch.randn(1, H, N, 64).cuda().bfloat16(); v = torch.randn(1, H, N, 64).cuda().bfloat16()
+def packm(x):
+    o = torch.zeros(1, H, Npad, 64, device="cuda", dtype=x.dtype); o[:, :, :N] = x; return o
+out = torch.full((1, N, H * 64), float("nan"), device="cuda", dtype=torch.bfloat16)
+ops.attn_fwd(packm(q), packm(k), packm(v).transpose(2, 3).contiguous(), out, N, N, 0.125, *ops.attn_mask_tables(fid, fid, Npad, "cuda"))
+f = torch.from_numpy(fid.astype(np.int64)).cuda()
+s = ((q.float() @ k.float().transpose(-1, -2)) * 0.125).masked_fill(~(f[None, :] <= f[:, None]), float("-inf"))
+ref = (torch.softmax(s, -1) @ v.float()).permute(0, 2, 1, 3).reshape(1, N, H * 64)
+worst = max(worst, torch.nan_to_num((out.float() - ref).abs(), nan=1e9).max().item())
 print("WORST", worst)
 ''' % ROOT
 
