@@ -32,7 +32,8 @@ extern "C" {
  * ld_qkv_split gained mode 2.  13: ld_gemm_route was added.  14: ld_gemv_pairs, ld_llm_decode_forward_pairs and
  * ld_llm_sample_advance_pairs were added.  15: ld_llm_token_logprobs and ld_llm_head_f32 were added;
  * ld_gemv_wide, ld_llm_decode_forward_wide and ld_llm_sample_advance_wide joined later, and so did ld_absdiff_sums,
- * ld_residual_sub and ld_residual_add (additions do not change the number: no existing signature moved). */
+ * ld_residual_sub, ld_residual_add, ld_attn_fwd_bf16_window and ld_attn_window_plan (additions do not change the number: no existing
+ * signature moved). */
 #define LD_ABI_VERSION 15
 
 int ld_version(void);
@@ -224,6 +225,31 @@ int ld_attn_fwd_bf16_exact(const void* Q, const void* K, const void* Vt, void* O
                            int64_t o_batch_stride, int64_t o_row_stride, float softmax_scale,
                            const int32_t* fid_q, const int32_t* fid_k,
                            const int32_t* kt_min, const int32_t* kt_max, void* stream);
+
+/* Opt-in frame-window attention for sequences laid out [prefix | frame 0 | frame 1 | ...] (N = Nq = Nk tokens, `prefix` text
+ * tokens, `group` tokens per frame, `window` frames each side): the pipelined kernel of ld_attn_fwd_bf16 walking fewer key tiles.
+ * Same layouts, padding rules and dispatch (static / dynamic, counter sets, graph capture) as ld_attn_fwd_bf16; sets
+ * ld_attn_last_kernel (ld_attn_q64_win_kernel / ld_attn_q64_win_dyn_kernel) and the source of ld_attn_last_fallbacks.
+ * The rule, per 256-row query block b with rows r0 = 256 b .. r1 = min(r0 + 256, N) - 1, n = ceil(N / 64), pt = ceil(prefix / 64):
+ *   r0 < prefix: the block holds a text row and walks every tile [0, n);
+ *   else f_lo = (r0 - prefix) / group, f_hi = (r1 - prefix) / group, k_lo = prefix + max(0, f_lo - window) * group,
+ *        k_hi = min(N, prefix + (f_hi + window + 1) * group), t_lo = max(pt, k_lo / 64), t_hi = ceil(k_hi / 64):
+ *        the block walks tiles 0 .. pt-1, t_lo .. t_hi-1 (n_eff = pt + t_hi - t_lo of them).
+ * Every row of the block sees exactly the keys k < N of the listed tiles: all text, at least every token within `window` frames
+ * of its own, plus up to one tile and one block of ragged extra at the window's edges -- a deliberate superset (no element mask).
+ * Refused before anything is launched: LD_ERR_INVALID for window < 0, group < 1, prefix outside [0, N]; LD_ERR_UNSUPPORTED for
+ * fewer than 6 key tiles or a block with n_eff < 6.  There is no masked, rectangular (Nq != Nk) or exact two-pass window form.
+ * What the window does to a trained checkpoint's output is unmeasured. */
+int ld_attn_fwd_bf16_window(const void* Q, const void* K, const void* Vt, void* O,
+                            int64_t B, int64_t H, int64_t N, int64_t Npad,
+                            int64_t o_batch_stride, int64_t o_row_stride, float softmax_scale,
+                            int64_t prefix, int64_t group, int64_t window, void* stream);
+
+/* The tile range of query block `block` under the rule above, from the function the launcher validates with and the kernels
+ * walk by: *t_lo, *t_hi, *n_eff (a text block reports t_lo = pt, t_hi = n).  Host logic only, no GPU needed.  LD_ERR_INVALID for
+ * bad arguments or a block outside [0, ceil(N / 256)); shapes ld_attn_fwd_bf16_window would refuse as unsupported still plan. */
+int ld_attn_window_plan(int64_t N, int64_t prefix, int64_t group, int64_t window, int64_t block,
+                        int32_t* t_lo, int32_t* t_hi, int32_t* n_eff);
 
 /* Forgets the stream -> counter-set assignments of the current device and zeroes its sets (asynchronously on `stream`).
  * Only for a process that keeps creating streams, or after a device error: the caller guarantees that no ld_attn_fwd_bf16

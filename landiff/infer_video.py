@@ -55,7 +55,17 @@ def parse_args(argv=None):
                              "(accumulated relative L1, a float >= 0) since the last computed step reuses that step's residual across "
                              "the transformer stack instead of running it.  0 computes every step.  What each step did is written "
                              "to <save_file_name>_dit_cache.json.  The quality at a given threshold is not measured.")
+    parser.add_argument("--attn_window", type=int, default=None, metavar="W",
+                        help="Frame-window attention in the DiT (off by default): a video token attends to the text and to the W "
+                             "latent frames each side of its own (W >= 0; per 256-row block, a ragged superset) instead of to every "
+                             "frame.  The effect on quality is not measured.")
+    parser.add_argument("--attn_window_dense_steps", type=int, default=0, metavar="K",
+                        help="With --attn_window: the first K sampler steps of a video run full attention.")
     args = parser.parse_args(argv)
+    if args.attn_window is not None and args.attn_window < 0:
+        parser.error(f"--attn_window takes an integer >= 0, got {args.attn_window}")
+    if args.attn_window_dense_steps < 0 or (args.attn_window_dense_steps and args.attn_window is None):
+        parser.error("--attn_window_dense_steps takes an integer >= 0 and goes with --attn_window")
     if args.dit_cache is not None:
         import math
         try:
@@ -179,10 +189,20 @@ def llm_infer_samples(args):
 
 
 def _diffusion_model(args):
-    """CogModelInferWrapper of the run; --dit_cache is handed on only when given (without it the call is the reference's)."""
-    if getattr(args, "dit_cache", None) is None:
-        return CogModelInferWrapper(ckpt_path=args.diffusion_ckpt)
-    return CogModelInferWrapper(ckpt_path=args.diffusion_ckpt, dit_cache=args.dit_cache)
+    """CogModelInferWrapper of the run; --dit_cache and --attn_window are handed on only when given (without them the call is the
+    reference's)."""
+    return CogModelInferWrapper(ckpt_path=args.diffusion_ckpt, **_dit_options(args))
+
+
+def _dit_options(args) -> dict:
+    """The opt-in DiT switches of the command line as keyword arguments, each present only when its flag was given."""
+    kw = {}
+    if getattr(args, "dit_cache", None) is not None:
+        kw["dit_cache"] = args.dit_cache
+    if getattr(args, "attn_window", None) is not None:
+        from landiff_amd.config import AttnWindowConfig
+        kw["attn_window"] = AttnWindowConfig(frames=args.attn_window, dense_steps=getattr(args, "attn_window_dense_steps", 0))
+    return kw
 
 
 def _write_dit_cache_report(args, stem, report):
@@ -252,7 +272,8 @@ def build_continuation(args):
     c = cfg.llm
     # the clip is chunk 0 of the stream: its multi-segment AR decode needs n_seg segments of KV cache
     _, _, n_seg = stream_plan(cfg, args.extend_chunks + 1, args.extend_prefix_frames)
-    pipe = LanDiffPipeline(cfg, st, dev, max_llm_frames=n_seg * c.segment_length, dit_cache=getattr(args, "dit_cache", None))
+    win = {k: v for k, v in _dit_options(args).items() if k == "attn_window"}
+    pipe = LanDiffPipeline(cfg, st, dev, max_llm_frames=n_seg * c.segment_length, dit_cache=getattr(args, "dit_cache", None), **win)
     text = encode_flan_t5([args.prompt], dev, max_length=c.max_cond_tokens, model_path=c.text_encoder_path)[0]
     ctx = encode_t5_v11([args.prompt], resolve_ckpt_path(dcfg.t5_dir), cfg.dit.text_len, dev)
     inp = PromptInputs(text, ctx, seed=args.seed, cfg=args.cfg, motion_score=args.motion_score)

@@ -71,6 +71,8 @@ SIGNATURES: dict[str, list] = {
     "ld_calib_stream_read": [P, I64, P, P],
     "ld_attn_fwd_bf16": _ATTN_FWD,
     "ld_attn_fwd_bf16_exact": _ATTN_FWD,
+    "ld_attn_fwd_bf16_window": [P, P, P, P, I64, I64, I64, I64, I64, I64, c_float, I64, I64, I64, P],
+    "ld_attn_window_plan": [I64, I64, I64, I64, I64, POINTER(I32), POINTER(I32), POINTER(I32)],
     "ld_attn_last_kernel": [],
     "ld_attn_last_fallbacks": [P, P],
     "ld_reset": [P],

@@ -190,6 +190,31 @@ class DiTConfig:
 
 
 @dataclass(frozen=True)
+class AttnWindowConfig:
+    """Opt-in frame-window attention of the DiT (ControlDiTRunner(attn_window=...); the rule is in DESIGN.md and
+    include/landiff_hip.h: ld_attn_fwd_bf16_window).  frames: a video token attends to the text and to the frames within this
+    many of its own, each side.  dense_steps: the first that many sampler steps of a video run full attention.  Off by default;
+    nothing here claims anything about the quality of a trained checkpoint under a window."""
+    frames: int
+    dense_steps: int = 0
+
+    def __post_init__(self):
+        for name in ("frames", "dense_steps"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError(f"AttnWindowConfig: {name} must be a non-negative integer, got {v!r}")
+
+    @staticmethod
+    def as_config(value) -> "AttnWindowConfig | None":
+        """None / a window in frames / an AttnWindowConfig -> AttnWindowConfig or None (what attn_window=... accepts)."""
+        if value is None or isinstance(value, AttnWindowConfig):
+            return value
+        if isinstance(value, bool) or not isinstance(value, int):
+            raise TypeError(f"attn_window must be None, a window in frames (int >= 0) or an AttnWindowConfig, got {value!r}")
+        return AttnWindowConfig(frames=value)
+
+
+@dataclass(frozen=True)
 class VAEConfig:
     ch: int = 128
     ch_mult: tuple = (1, 2, 2, 4)

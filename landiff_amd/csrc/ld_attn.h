@@ -29,6 +29,34 @@ constexpr int STAGE_BYTES = 2 * KTILE_BYTES;  // K + V^T
 constexpr float NEG_BIG = -1.0e30f;
 
 
+// Frame-window attention (ld_attn_fwd_bf16_window): the key tiles that 256-row query block `b` of a sequence
+// [P prefix keys | frames of G tokens ...] of N tokens walks with a window of w frames each side -- the logical list
+// 0 .. pt-1, t_lo .. t_hi-1 (pt = ceil(P / 64)), n_eff tiles long.  A block that holds a prefix row walks every tile (t_lo = pt,
+// t_hi = n).  The ONE statement of the rule: the kernels derive their tile list from it, the launcher validates with it and
+// ld_attn_window_plan reports it.  int arithmetic: the host clamps G to N and w to the frame count first (attn_window_clamp),
+// which changes no result and keeps (f_hi + w + 1) * G below 2^31 for N < 2^28.
+__host__ __device__ inline void attn_window_block(int N, int P, int G, int w, int b, int* t_lo, int* t_hi, int* n_eff) {
+  const int n = (N + 63) / 64, pt = (P + 63) / 64;
+  const int r0 = 256 * b, r1 = (r0 + 256 < N ? r0 + 256 : N) - 1;
+  int lo = pt, hi = n;
+  if (r0 >= P) {
+    const int f_lo = (r0 - P) / G, f_hi = (r1 - P) / G;
+    const int k_lo = P + (f_lo > w ? f_lo - w : 0) * G;
+    int k_hi = P + (f_hi + w + 1) * G;
+    k_hi = k_hi < N ? k_hi : N;
+    lo = k_lo / 64 > pt ? k_lo / 64 : pt;
+    hi = (k_hi + 63) / 64;
+  }
+  *t_lo = lo; *t_hi = hi; *n_eff = pt + hi - lo;
+}
+
+// G >= N is one frame and w >= the frame count is every frame: clamp both (same plan, no overflow in attn_window_block)
+inline void attn_window_clamp(int64_t N, int64_t P, int64_t* G, int64_t* w) {
+  if (*G > N) *G = N;
+  const int64_t frames = P < N ? (N - P + *G - 1) / *G : 0;
+  if (*w > frames) *w = frames;
+}
+
 __device__ __forceinline__ void glds16(const bf16_t* g, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds(
       (const __attribute__((address_space(1))) void*)g,

@@ -351,6 +351,7 @@ __global__ __launch_bounds__(256, WPS) void ld_attn_kernel(AttnParams p) {
 
 int ld_attn_p16_launch(const AttnParams& p, hipStream_t st);     // ld_attn_p16.hip
 int ld_attn_q64_launch(const AttnParams& p, hipStream_t st);     // ld_attn_q64.hip
+int ld_attn_q64_launch_any(const AttnParams& p, hipStream_t st, const int* win);   // ld_attn_q64.hip: win = {prefix, group, frames}
 #ifdef LD_VARIANTS   // measured alternatives, only in the variants build (build.sh: LD_BUILD_VARIANTS=1)
 int ld_attn_pipe2_launch(const AttnParams& p, hipStream_t st);   // ld_attn_pipe.hip
 int ld_attn_q128_launch(const AttnParams& p, hipStream_t st);    // ld_attn_q128.hip
@@ -457,4 +458,59 @@ LD_API int ld_attn_fwd_bf16_exact(const void* Q, const void* K, const void* Vt, 
                                   const int32_t* fid_q, const int32_t* fid_k,
                                   const int32_t* kt_min, const int32_t* kt_max, void* stream) {
   return attn_fwd_impl(Q, K, Vt, O, B, H, Nq, Nk, Npad, o_batch_stride, o_row_stride, softmax_scale, fid_q, fid_k, kt_min, kt_max, stream, true);
+}
+
+// ---- frame-window attention: every 256-row query block walks the prefix tiles and the tiles of the frames within `window` of its
+// own (attn_window_block, ld_attn.h).  Host side: arguments, the plan, the refusals. ----
+
+// The arguments of a window problem, checked and clamped (G to N, w to the frame count: the same plan, no overflow).  Pure.
+static int attn_window_args(const char* who, int64_t N, int64_t P, int64_t* G, int64_t* w) {
+  LD_REQUIRE(N > 0 && N < (1 << 28), "%s: N=%ld outside (0, 2^28)", who, (long)N);
+  LD_REQUIRE(P >= 0 && P <= N, "%s: prefix=%ld outside [0, N=%ld]", who, (long)P, (long)N);
+  LD_REQUIRE(*G >= 1, "%s: group=%ld (tokens per frame) must be >= 1", who, (long)*G);
+  LD_REQUIRE(*w >= 0, "%s: window=%ld (frames each side) must be >= 0", who, (long)*w);
+  attn_window_clamp(N, P, G, w);
+  return LD_OK;
+}
+
+LD_API int ld_attn_window_plan(int64_t N, int64_t prefix, int64_t group, int64_t window, int64_t block,
+                               int32_t* t_lo, int32_t* t_hi, int32_t* n_eff) {
+  LD_REQUIRE(t_lo && t_hi && n_eff, "ld_attn_window_plan: null pointer");
+  if (int rc = attn_window_args("ld_attn_window_plan", N, prefix, &group, &window)) return rc;
+  LD_REQUIRE(block >= 0 && block < (N + 255) / 256, "ld_attn_window_plan: block %ld of %ld", (long)block, (long)((N + 255) / 256));
+  int lo, hi, ne;
+  attn_window_block((int)N, (int)prefix, (int)group, (int)window, (int)block, &lo, &hi, &ne);
+  *t_lo = lo; *t_hi = hi; *n_eff = ne;
+  return LD_OK;
+}
+
+LD_API int ld_attn_fwd_bf16_window(const void* Q, const void* K, const void* Vt, void* O,
+                                   int64_t B, int64_t H, int64_t N, int64_t Npad,
+                                   int64_t o_batch_stride, int64_t o_row_stride, float softmax_scale,
+                                   int64_t prefix, int64_t group, int64_t window, void* stream) {
+  // the window's own rules first (pure host arithmetic: a caller may probe a shape without a device)
+  if (int rc = attn_window_args("ld_attn_fwd_bf16_window", N, prefix, &group, &window)) return rc;
+  const int64_t n = (N + KT - 1) / KT, pt = (prefix + KT - 1) / KT;
+  if (n < 6) return ld_set_error(LD_ERR_UNSUPPORTED, "ld_attn_fwd_bf16_window: %ld key tiles; the pipelined kernel needs at least 6", (long)n);
+  for (int64_t b = 0; b < (N + 255) / 256; ++b) {
+    int lo, hi, ne;
+    attn_window_block((int)N, (int)prefix, (int)group, (int)window, (int)b, &lo, &hi, &ne);
+    if (ne < 6)
+      return ld_set_error(LD_ERR_UNSUPPORTED, "ld_attn_fwd_bf16_window: query block %ld would walk %d key tiles (prefix %ld, group %ld, window %ld); "
+                          "the pipelined kernel needs at least 6", (long)b, ne, (long)prefix, (long)group, (long)window);
+    if (!(lo >= pt && lo <= hi && hi <= n))     // (cannot happen: the rule keeps every list inside [0, n))
+      return ld_set_error(LD_ERR_INVALID, "ld_attn_fwd_bf16_window: block %ld: tile range [%d, %d) outside [%ld, %ld]", (long)b, lo, hi, (long)pt, (long)n);
+  }
+  LD_REQUIRE(Q && K && Vt && O, "ld_attn_fwd_bf16_window: null pointer");
+  LD_REQUIRE(B > 0 && H > 0, "ld_attn_fwd_bf16_window: empty problem");
+  LD_REQUIRE(Npad % QB == 0 && Npad >= N, "ld_attn_fwd_bf16_window: Npad=%ld must be a multiple of %d and >= N", (long)Npad, QB);
+  LD_REQUIRE(o_row_stride % 4 == 0 && ((uintptr_t)O & 7) == 0, "ld_attn_fwd_bf16_window: output alignment");
+  LD_REQUIRE(B * H * ((Npad + 255) / 256) < (1LL << 31), "ld_attn_fwd_bf16_window: grid too large");
+  AttnParams p{};
+  p.Q = (const bf16_t*)Q; p.K = (const bf16_t*)K; p.Vt = (const bf16_t*)Vt; p.O = (bf16_t*)O;
+  p.B = (int)B; p.H = (int)H; p.Nq = (int)N; p.Nk = (int)N; p.Npad = (int)Npad;
+  p.o_bs = o_batch_stride; p.o_rs = o_row_stride;
+  p.c = softmax_scale * 1.4426950408889634f;
+  const int win[3] = {(int)prefix, (int)group, (int)window};
+  return ld_attn_q64_launch_any(p, (hipStream_t)stream, win);
 }

@@ -33,6 +33,14 @@ __global__ __launch_bounds__(256, 2) void ld_attn_q64_kernel(AttnParams p, int f
   attn_q64_body<Q64_FAST>(p, force_safe, smem, xcd_remap(blockIdx.x, gridDim.x));
 }
 
+// Frame-window form (ld_attn_fwd_bf16_window): the same body walking each query block's own key-tile list (ld_attn_q64_body.h: WIN;
+// the rule is attn_window_block, ld_attn.h).  prefix / group / frames = (P, G, w), validated by the launcher: every list is in
+// bounds and at least 6 tiles long.
+__global__ __launch_bounds__(256, 2) void ld_attn_q64_win_kernel(AttnParams p, int force_safe, int prefix, int group, int frames) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  attn_q64_body<Q64_FAST, true>(p, force_safe, smem, xcd_remap(blockIdx.x, gridDim.x), prefix, group, frames);
+}
+
 // ---- dynamic form: the XCDs of one chip do not run at one speed ----
 // tools/attn_q64_trace.py (profiles/r04_attn_q64_wg_trace.txt): under the package power cap the eight XCDs hold different clocks
 // (1741 ... 1876 MHz in one launch), the hardware deals workgroups to them round-robin -- 525 each -- and the launch ends when
@@ -97,6 +105,50 @@ __global__ __launch_bounds__(256, 2) void ld_attn_q64_dyn_kernel(AttnParams p, i
   }
 }
 
+// The window form pulled through the same counter sets, with the same fallback count word: the loop of ld_attn_q64_dyn_kernel
+// around the WIN body (a copy, so that the dense kernel's instruction stream stays what it was).
+__global__ __launch_bounds__(256, 2) void ld_attn_q64_win_dyn_kernel(AttnParams p, int force_safe, int total, int set,
+                                                                     int prefix, int group, int frames) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int* bcast = (int*)(smem + 8 * KTILE_BYTES + 32);
+  int* flags = (int*)(smem + 8 * KTILE_BYTES);             // the body's per-wave "a row left the window" words
+  unsigned* Q = g_q64_queue[set];
+  unsigned xcc;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  xcc &= 7u;
+  const int per = total / 8, rem = total % 8;            // xcd_remap: XCD x owns [base(x), base(x) + cnt(x))
+  auto base = [&](int x) { return x < rem ? x * (per + 1) : rem * (per + 1) + (x - rem) * per; };
+  auto cnt = [&](int x) { return per + (x < rem ? 1 : 0); };
+#ifndef LD_Q64_NO_FBCOUNT
+  if (threadIdx.x == 0) flags[0] = flags[1] = flags[2] = flags[3] = 0;
+#endif
+  for (;;) {
+    if (threadIdx.x == 0) {
+#ifndef LD_Q64_NO_FBCOUNT
+      // (counted and cleared inside the ONE thread-0 section of the iteration: see ld_attn_q64_dyn_kernel)
+      if ((flags[0] | flags[1] | flags[2] | flags[3]) != 0) __hip_atomic_fetch_add(&Q[8], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      int z = 0;
+      asm volatile("" : "+v"(z));                         // a zero made HERE: hoisted out of the loop, the four-register zero of this store was spilled to scratch
+      flags[0] = flags[1] = flags[2] = flags[3] = z;      // (a block past Nq returns before it writes them)
+#endif
+      int bid = -1;
+      for (int kx = 0; kx < 8 && bid < 0; ++kx) {        // own range first, then the neighbours'
+        const int x = (int)((xcc + kx) & 7u);
+        if (__hip_atomic_load(&Q[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)cnt(x)) continue;
+        const unsigned i = __hip_atomic_fetch_add(&Q[x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (i < (unsigned)cnt(x)) bid = base(x) + (int)i;
+      }
+      bcast[0] = bid;
+    }
+    __syncthreads();
+    const int bid = __builtin_amdgcn_readfirstlane(bcast[0]);   // a scalar: the block's tile list and loop bounds derive from it
+    __syncthreads();
+    if (bid < 0) break;
+    attn_q64_body<Q64_FAST, true>(p, force_safe, smem, bid, prefix, group, frames);
+    __syncthreads();
+  }
+}
+
 __global__ void ld_q64_queue_fill_kernel(int set, unsigned value) {
   const int s = blockIdx.x;
   if ((set < 0 || s == set) && threadIdx.x < 16) g_q64_queue[s][threadIdx.x] = value;
@@ -144,15 +196,21 @@ int q64_device_info(int* dev_out, unsigned** base_out, int* slots_out) {
 
 void ld_attn_set_last_kernel(const char* name);   // ld_attn.hip
 void ld_attn_set_fallback_source(const unsigned* src, int kind);   // ld_attn.hip
+int ld_attn_q64_launch_any(const AttnParams& p, hipStream_t st, const int* win);
 
 // LD_ATTN_SAFE=1 forces the running-max pass (testing).  LD_ATTN_DYN=0: the hardware's round-robin dispatch of one workgroup per
 // query block instead of the dynamic form (the default for grids of at least four rounds of the chip's slots).
-int ld_attn_q64_launch(const AttnParams& p, hipStream_t st) {
+int ld_attn_q64_launch(const AttnParams& p, hipStream_t st) { return ld_attn_q64_launch_any(p, st, nullptr); }
+
+// win: null = the dense kernels; else {prefix, group, frames} of the frame-window form (validated by ld_attn_fwd_bf16_window)
+int ld_attn_q64_launch_any(const AttnParams& p, hipStream_t st, const int* win) {
   constexpr int SMEM = 8 * KTILE_BYTES + 64;
   static int k_safe = LD_KNOB_UNSET, k_dyn = LD_KNOB_UNSET;
   const int safe = ld_knob("LD_ATTN_SAFE", 0, &k_safe);
   static thread_local LdSmemCache cache{};
-  if (int rc = ld_ensure_dyn_smem((const void*)ld_attn_q64_kernel, SMEM, &cache)) return rc;
+  static thread_local LdSmemCache cache_w{};
+  if (int rc = win ? ld_ensure_dyn_smem((const void*)ld_attn_q64_win_kernel, SMEM, &cache_w)
+                   : ld_ensure_dyn_smem((const void*)ld_attn_q64_kernel, SMEM, &cache)) return rc;
   const int total = (int)((long)p.B * p.H * ((p.Npad + Q64_ROWS - 1) / Q64_ROWS));
   if (ld_knob("LD_ATTN_DYN", 1, &k_dyn) > 0 && !safe) {
     int dev = -1, slots = 0; unsigned* base = nullptr;
@@ -161,19 +219,30 @@ int ld_attn_q64_launch(const AttnParams& p, hipStream_t st) {
     if (dev >= 0 && total >= 4 * slots && hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {
       const int set = q64_set_for(dev, st);
       if (set >= 0) {
-        static thread_local LdSmemCache cache_d{};
-        if (int rc = ld_ensure_dyn_smem((const void*)ld_attn_q64_dyn_kernel, SMEM, &cache_d)) return rc;
+        static thread_local LdSmemCache cache_d{}, cache_wd{};
+        if (int rc = win ? ld_ensure_dyn_smem((const void*)ld_attn_q64_win_dyn_kernel, SMEM, &cache_wd)
+                         : ld_ensure_dyn_smem((const void*)ld_attn_q64_dyn_kernel, SMEM, &cache_d)) return rc;
         hipError_t e = hipMemsetAsync(base + set * 16, 0, 64, st);
         if (e != hipSuccess) return ld_set_error(LD_ERR_LAUNCH, "ld_attn_fwd_bf16(q64 dynamic): zeroing counter set %d: %s", set, hipGetErrorString(e));
-        ld_attn_set_last_kernel("ld_attn_q64_dyn_kernel");
         ld_attn_set_fallback_source(base + set * 16 + 8, 1);
+        if (win) {
+          ld_attn_set_last_kernel("ld_attn_q64_win_dyn_kernel");
+          hipLaunchKernelGGL(ld_attn_q64_win_dyn_kernel, dim3((unsigned)slots), dim3(256), SMEM, st, p, safe, total, set, win[0], win[1], win[2]);
+          return ld_check_launch("ld_attn_fwd_bf16_window(q64 dynamic)");
+        }
+        ld_attn_set_last_kernel("ld_attn_q64_dyn_kernel");
         hipLaunchKernelGGL(ld_attn_q64_dyn_kernel, dim3((unsigned)slots), dim3(256), SMEM, st, p, safe, total, set);
         return ld_check_launch("ld_attn_fwd_bf16(q64 dynamic)");
       }
     }
   }
-  ld_attn_set_last_kernel(safe ? "ld_attn_q64_kernel[safe pass forced]" : "ld_attn_q64_kernel");
   ld_attn_set_fallback_source(nullptr, safe ? 0 : 2);
+  if (win) {
+    ld_attn_set_last_kernel(safe ? "ld_attn_q64_win_kernel[safe pass forced]" : "ld_attn_q64_win_kernel");
+    hipLaunchKernelGGL(ld_attn_q64_win_kernel, dim3((unsigned)total), dim3(256), SMEM, st, p, safe, win[0], win[1], win[2]);
+    return ld_check_launch("ld_attn_fwd_bf16_window(q64)");
+  }
+  ld_attn_set_last_kernel(safe ? "ld_attn_q64_kernel[safe pass forced]" : "ld_attn_q64_kernel");
   hipLaunchKernelGGL(ld_attn_q64_kernel, dim3((unsigned)total), dim3(256), SMEM, st, p, safe);
   return ld_check_launch("ld_attn_fwd_bf16(q64)");
 }

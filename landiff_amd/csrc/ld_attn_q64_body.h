@@ -17,17 +17,40 @@ constexpr int Q64_ROWS = Q64_NW * 64;   // query rows per workgroup
 //              in [1, Nk]: exact safe softmax for any logit range at ~1.55 x the fast pass, with no data-dependent re-run.
 enum { Q64_FAST = 0, Q64_EXACT = 1 };
 
-template <int MODE>
-__device__ __forceinline__ void attn_q64_body(const AttnParams& p, int force_safe, char* smem, const int bid) {   // smem: K slots 0..3 | V^T slots 0..3 | flag words; bid: remapped block index
+// WIN (ld_attn_q64_win_kernel / ld_attn_q64_win_dyn_kernel, Q64_FAST only): frame-window attention.  The query block walks the
+// LOGICAL tile list 0 .. pt-1, t_lo .. t_hi-1 of attn_window_block (ld_attn.h) instead of all n tiles: logical tile t is source
+// tile t < pt ? t : t + shift (in dma_piece, so every pass follows it), n is the list's length and the tail handling sees the
+// logical key count.  Wave-uniform scalars derived once per block; the loops, phases and barriers are the dense ones.
+template <int MODE, bool WIN = false>
+__device__ __forceinline__ void attn_q64_body(const AttnParams& p, int force_safe, char* smem, const int bid,
+                                              int win_prefix = 0, int win_group = 0, int win_frames = 0) {   // smem: K slots 0..3 | V^T slots 0..3 | flag words; bid: remapped block index
+  static_assert(!WIN || MODE == Q64_FAST, "the window form exists for the fast pass only");
   constexpr int NW = Q64_NW;
   constexpr int VBASE = 4 * KTILE_BYTES;
-  const int tid = threadIdx.x;
+  int tid_ = threadIdx.x;
+  // WIN: an opaque copy, so that the per-lane offsets are values of THIS block: hoisted out of the dynamic form's block loop they
+  // stayed live across the pipelined loop, which has no register to spare (11 VGPRs spilled to scratch)
+  if constexpr (WIN) asm volatile("" : "+v"(tid_));
+  const int tid = tid_;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l16 = lane & 15, h4 = lane >> 4;
   constexpr int NPW = 16 / NW;                    // LDS-DMA pieces per wave and tile
   const int nqb = (p.Npad + Q64_ROWS - 1) / Q64_ROWS;
-  const int n = (p.Nk + KT - 1) / KT;             // >= 6 (launcher)
+  int n_ = (p.Nk + KT - 1) / KT, nk_ = p.Nk, wshift_ = 0, wpt_ = 0;
+  if constexpr (WIN) {
+    int t_lo, t_hi, n_eff;
+    attn_window_block(p.Nk, win_prefix, win_group, win_frames, bid % nqb, &t_lo, &t_hi, &n_eff);
+    const int pt = (win_prefix + KT - 1) / KT;
+    // bid may come out of LDS (dynamic form): make what the loops branch on scalars again
+    wpt_ = pt;
+    wshift_ = __builtin_amdgcn_readfirstlane(t_lo - pt);
+    nk_ = __builtin_amdgcn_readfirstlane(t_hi == n_ ? p.Nk - KT * (t_lo - pt) : KT * n_eff);
+    n_ = __builtin_amdgcn_readfirstlane(n_eff);
+  }
+  const int n = n_;                               // >= 6 (launcher); WIN: tiles of this block's list
+  const int nk = nk_;                             // keys at or past nk are masked; WIN: the list's logical key count
+  const int wshift = wshift_, wpt = wpt_;
   const int NH = 2 * n;                           // halves
 
   const int bh = bid / nqb, qblk = bid - bh * nqb;
@@ -75,7 +98,7 @@ __device__ __forceinline__ void attn_q64_body(const AttnParams& p, int force_saf
   }
   auto dma_piece = [&](int i, int slot, int t) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(smem + slot * KTILE_BYTES + ldsoff[i]),
-                                             16, goff[i], t * tstride, 0, 0);
+                                             16, goff[i], (WIN ? (t < wpt ? t : t + wshift) : t) * tstride, 0, 0);
   };
   auto dma = [&](int slot, int t) {
 #pragma unroll
@@ -99,14 +122,14 @@ __device__ __forceinline__ void attn_q64_body(const AttnParams& p, int force_saf
   f32x4_t cinit[4] = {zero4, zero4, zero4, zero4};  // Q64_EXACT: -max of query l16 of block qb, the score blocks' initial accumulator
   auto C0 = [&](int qb) -> f32x4_t { if constexpr (MODE == Q64_EXACT) return cinit[qb]; else return zero4; };
 
-  // keys of half hh (tile hh >> 1, key group hh & 1) past Nk -> -inf-like scores
+  // keys of half hh (tile hh >> 1, key group hh & 1) past Nk (nk) -> -inf-like scores
   auto mask_half = [&](f32x4_t (&s)[2][4], int hh) {
 #pragma unroll
     for (int bb = 0; bb < 2; ++bb) {
       const int key0 = (hh >> 1) * KT + (hh & 1) * 32 + h4 * 8 + bb * 4;
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (key0 + r >= p.Nk) {
+        if (key0 + r >= nk) {
 #pragma unroll
           for (int qb = 0; qb < 4; ++qb) s[bb][qb][r] = NEG_BIG;
         }
@@ -270,8 +293,8 @@ __device__ __forceinline__ void attn_q64_body(const AttnParams& p, int force_saf
     //      other four hold no key) instead of 28 peeled iteration
     //      bodies whose register pressure spilled (640 MB of scratch writes per launch).  The trips that need no mask run
     //      from a copy of the loop without the mask tests: a uniform branch per half costs the whole step 2.5 %. ----
-    const int hmask = p.Nk / 32;                    // first half that holds a key >= Nk
-    const int hend = (p.Nk + 31) / 32;              // first half that holds no key at all
+    const int hmask = nk / 32;                      // first half that holds a key >= Nk
+    const int hend = (nk + 31) / 32;                // first half that holds no key at all
     int hh = 0;
     for (; hh + 8 < hmask; hh += 8) {               // trips that compute no half >= hmask: no mask tests in the instruction stream
       iter(sA, sB, hh,     P0{}, false);
@@ -321,7 +344,7 @@ __device__ __forceinline__ void attn_q64_body(const AttnParams& p, int force_saf
         f32x4_t s[2][4];
         load_kh(kf, 0, kg); load_vh(vf, 0, kg);
         qk_half(s, kf);
-        if ((t + 1) * KT > p.Nk) mask_half(s, 2 * t + kg);
+        if ((t + 1) * KT > nk) mask_half(s, 2 * t + kg);
 #pragma unroll
         for (int qb = 0; qb < 4; ++qb) {
           float mx = NEG_BIG;

@@ -15,7 +15,7 @@ import os
 import torch
 
 from . import ops
-from .config import DiTConfig
+from .config import AttnWindowConfig, DiTConfig
 from .dit_cache import StepCacheConfig, StepCachePolicy
 
 BF = torch.bfloat16
@@ -80,7 +80,8 @@ class ControlDiTRunner:
     B = 2
 
     def __init__(self, main_sd: dict, control_sd: dict, cfg: DiTConfig, device, fp8_gemm: bool = False,
-                 attn_exact: "bool | str | None" = None, step_cache: "StepCacheConfig | None" = None, plan_timesteps=None):
+                 attn_exact: "bool | str | None" = None, step_cache: "StepCacheConfig | None" = None, plan_timesteps=None,
+                 attn_window: "AttnWindowConfig | int | None" = None):
         """fp8_gemm: BASELINE configs[4] -- the qkv / dense / 4h / 4h->h linears run on e4m3 operands; attention, norms,
         residual stream and every other layer stay bf16.  True / "row": weights quantised once per output channel,
         activations per row by a pass in front of each GEMM.  "mx": MXFP8 (one power-of-two scale per 32 K elements, applied
@@ -102,6 +103,24 @@ class ControlDiTRunner:
             attn_exact = {"1": True, "0": False}.get(os.environ.get("LD_DIT_ATTN_EXACT", "auto"), "auto")
         self.attn_auto = attn_exact == "auto"
         self.attn_exact = (not self.attn_auto) and bool(attn_exact)
+        # attn_window (None = off: _attention() is the code path it always was): frame-window attention, ld_attn_fwd_bf16_window -- a
+        # video token attends to the text and to the frames within `frames` of its own (per 256-row block, a deliberate ragged
+        # superset), in both branches, from sampler step `dense_steps` of a video on.  There is no exact two-pass window
+        # form: attn_exact=True with a window is refused, and under "auto" the fallback counts are still read but a windowed launch
+        # is never switched -- outside the logit window the kernel's own safe pass keeps it correct, at a cost.  A shape the window
+        # form cannot take is refused here, with the reason: nothing silently runs dense.  Quality under a window: unmeasured.
+        self._win = AttnWindowConfig.as_config(attn_window)
+        self._win_step = 0                      # sampler steps since set_condition()
+        self._win_on = False                    # this step's launches take the window form
+        if self._win is not None:
+            if self.attn_exact:
+                raise ValueError("attn_exact=True and attn_window: there is no exact two-pass window kernel")
+            if cfg.head_dim != 64:
+                raise ValueError(f"attn_window: the window kernel is for head_dim 64, got {cfg.head_dim}")
+            try:
+                ops.attn_window_check(cfg.seq_len, cfg.text_len, cfg.grid_h * cfg.grid_w, self._win.frames)
+            except ValueError as e:
+                raise ValueError(f"attn_window={self._win.frames} does not fit this DiT shape: {e}") from None
         self.main = _Branch(main_sd, cfg, False, device, fp8_gemm)
         self.ctrl = _Branch(control_sd, cfg, True, device, fp8_gemm)
         c, B = cfg, self.B
@@ -185,6 +204,7 @@ class ControlDiTRunner:
                 ops.gemm(ctx[b], br.text_w, out=dst[b], bias=br.text_b, add2=br.pos[: c.text_len])
         self.sem = semantic_feature.to(self.dev, BF).contiguous()
         self.reset_step_cache()
+        self._win_step = 0
 
     # ---- pieces ----------------------------------------------------------------------------
     def _time_emb(self, br: _Branch, timestep: float):
@@ -241,6 +261,8 @@ class ControlDiTRunner:
 
     def _attention(self):
         c, N = self.cfg, self.N
+        if self._win_on:
+            return self._attention_window()
         exact = self.attn_exact or (self._attn_slot in self.exact_layers)
         if self.attn_events is not None:       # bench.py: HIP events around every attention launch (roofline.achieved)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -252,6 +274,21 @@ class ControlDiTRunner:
             ops.attn_fwd(self.q, self.k, self.vt, self.attn, N, N, c.head_dim ** -0.5, exact=exact)
         if self.attn_auto and not exact:
             ops.attn_last_fallbacks(self._fb[self._attn_slot:self._attn_slot + 1])     # (on the stream of the launch)
+
+    def _attention_window(self):
+        """_attention() on a windowed step: the window launch, never the exact form (there is none); "auto" still reads the count."""
+        c, N = self.cfg, self.N
+        args = (self.q, self.k, self.vt, self.attn, N, c.head_dim ** -0.5, c.text_len, c.grid_h * c.grid_w, self._win.frames)
+        if self.attn_events is not None:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            ops.attn_fwd_window(*args)
+            e1.record()
+            self.attn_events.append((e0, e1, self._solo))
+        else:
+            ops.attn_fwd_window(*args)
+        if self.attn_auto:
+            ops.attn_last_fallbacks(self._fb[self._attn_slot:self._attn_slot + 1])
 
     def _attn_auto_end_of_step(self):
         """attn_exact="auto": hand this step's per-layer fallback counts to the host (asynchronously) and act on the previous step's."""
@@ -502,6 +539,9 @@ class ControlDiTRunner:
 
     def step(self, x: torch.Tensor, timestep: int, c_out: float, c_skip: float, cfg_scale: float, out: torch.Tensor):
         """x, out: [1, T, C, H, W] fp32.  out = CFG(denoised_uncond, denoised_cond)."""
+        if self._win is not None:                         # (every sampler step counts, computed or skipped by the step cache)
+            self._win_on = self._win_step >= self._win.dense_steps
+            self._win_step += 1
         if self._sc is not None:
             r, computed = self._step_cached(x, timestep, c_out, c_skip, cfg_scale, out)
             if self.attn_auto and computed:               # (a skipped step launched no attention: no new counts)

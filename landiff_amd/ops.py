@@ -233,6 +233,48 @@ def attn_fwd(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tens
     return out
 
 
+def attn_window_plan(N: int, prefix: int, group: int, window: int) -> list:
+    """ld_attn_window_plan for every 256-row query block of an N-token sequence [prefix | frames of `group` tokens]: a list of
+    (t_lo, t_hi, n_eff) -- the block walks key tiles 0 .. ceil(prefix / 64) - 1 and t_lo .. t_hi - 1 (n_eff tiles).  Host only."""
+    lib = _lib.load()
+    lo, hi, ne = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+    plan = []
+    for b in range((N + 255) // 256):
+        check(lib.ld_attn_window_plan(N, prefix, group, window, b, ctypes.byref(lo), ctypes.byref(hi), ctypes.byref(ne)),
+              "ld_attn_window_plan")
+        plan.append((lo.value, hi.value, ne.value))
+    return plan
+
+
+def attn_window_check(N: int, prefix: int, group: int, window: int) -> list:
+    """The plan of attn_window_plan, or ValueError with the reason ld_attn_fwd_bf16_window would refuse the shape for (fewer than 6
+    key tiles in the sequence or in one block's list): for callers that must know before they launch (ControlDiTRunner)."""
+    plan = attn_window_plan(N, prefix, group, window)
+    n = (N + ATTN_KEY_TILE - 1) // ATTN_KEY_TILE
+    if n < ATTN_PIPELINED_MIN_TILES:
+        raise ValueError(f"frame-window attention needs at least {ATTN_PIPELINED_MIN_TILES} key tiles of {ATTN_KEY_TILE}; {N} tokens are {n}")
+    short = [(b, p[2]) for b, p in enumerate(plan) if p[2] < ATTN_PIPELINED_MIN_TILES]
+    if short:
+        raise ValueError(f"frame-window attention (prefix {prefix}, {group} tokens per frame, window {window}): query block {short[0][0]} "
+                         f"would walk {short[0][1]} key tiles, the pipelined kernel needs at least {ATTN_PIPELINED_MIN_TILES}")
+    return plan
+
+
+def attn_fwd_window(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, N: int, scale: float,
+                    prefix: int, group: int, window: int) -> torch.Tensor:
+    """ld_attn_fwd_bf16_window: attn_fwd's unmasked square problem (Nq = Nk = N) where every 256-row query block walks only the
+    key tiles of the prefix and of the frames within `window` of its own (attn_window_plan).  Shapes the window form does not
+    take raise; nothing runs dense instead."""
+    _bf16(q, "q"); _bf16(k, "k"); _bf16(vt, "vt"); _bf16(out, "out")
+    B, H, Npad, D = q.shape
+    assert D == 64 and k.shape == q.shape and tuple(vt.shape) == (B, H, 64, Npad)
+    assert q.is_contiguous() and k.is_contiguous() and vt.is_contiguous() and out.stride(-1) == 1
+    assert out.shape[0] == B and out.shape[2] == H * 64 and out.shape[1] >= N
+    check(_lib.load().ld_attn_fwd_bf16_window(_ptr(q), _ptr(k), _ptr(vt), _ptr(out), B, H, N, Npad, out.stride(0), out.stride(1),
+                                              float(scale), prefix, group, window, _stream()), "ld_attn_fwd_bf16_window")
+    return out
+
+
 def attn_last_fallbacks(out: torch.Tensor) -> torch.Tensor:
     """ld_attn_last_fallbacks: out int32 [1] on the device <- the number of 256-row query blocks of this thread's last attn_fwd launch
     (on the current stream) that left the fast pass's window and were recomputed; 0: kernel without a window, -1: no count kept."""

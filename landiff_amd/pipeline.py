@@ -15,7 +15,7 @@ from dataclasses import dataclass
 import torch
 
 from . import _lib
-from .config import PipelineConfig
+from .config import AttnWindowConfig, PipelineConfig
 from .detokenizer import Detokenizer
 from .dit import ControlDiTRunner
 from .dit_cache import as_config
@@ -42,7 +42,7 @@ class PromptInputs:
 
 class LanDiffPipeline:
     def __init__(self, cfg: PipelineConfig, states: dict, device="cuda:0", max_llm_frames: int | None = None,
-                 fp8_gemm: bool = False, theia=None, max_samples: int = 1, wide_samples: int = 0, dit_cache=None):
+                 fp8_gemm: bool = False, theia=None, max_samples: int = 1, wide_samples: int = 0, dit_cache=None, attn_window=None):
         if not torch.cuda.is_available():
             raise _lib.LandiffHipError("LanDiffPipeline needs an MI355X GPU: there is no CPU fallback")
         _lib.load()
@@ -61,8 +61,13 @@ class LanDiffPipeline:
         # configuration, and what a threshold costs in quality on a trained checkpoint is not measured
         self.sampler = DiffusionSampler(cfg.sampler)
         self.dit_cache = as_config(dit_cache)
+        # attn_window: None (off), a window in frames or a config.AttnWindowConfig -- frame-window attention in the DiT
+        # (ControlDiTRunner(attn_window=...)); never the headline configuration, and what a window does to a trained
+        # checkpoint's output is not measured; handed on only when given
+        self.attn_window = AttnWindowConfig.as_config(attn_window)
+        win = {} if self.attn_window is None else {"attn_window": self.attn_window}
         self.dit = ControlDiTRunner(states["dit_main"], states["dit_control"], cfg.dit, self.dev, fp8_gemm=fp8_gemm,
-                                    step_cache=self.dit_cache,
+                                    step_cache=self.dit_cache, **win,
                                     plan_timesteps=[sp.timestep for sp in self.sampler.plan] if self.dit_cache is not None else None)
         self.dit_cache_reports = []       # one ControlDiTRunner.cache_report per sampler run (see dit_cache_report())
         self.vae = VAEDecoder(states["vae"], cfg.vae, self.dev)
