@@ -32,7 +32,7 @@ extern "C" {
  * ld_qkv_split gained mode 2.  13: ld_gemm_route was added.  14: ld_gemv_pairs, ld_llm_decode_forward_pairs and
  * ld_llm_sample_advance_pairs were added.  15: ld_llm_token_logprobs and ld_llm_head_f32 were added;
  * ld_gemv_wide, ld_llm_decode_forward_wide and ld_llm_sample_advance_wide joined later, and so did ld_absdiff_sums,
- * ld_residual_sub, ld_residual_add, ld_attn_fwd_bf16_window and ld_attn_window_plan (additions do not change the number: no existing
+ * ld_residual_sub, ld_residual_add, ld_attn_fwd_bf16_window, ld_attn_window_plan, ld_unpatchify_cfg_keep and ld_unpatchify_cond (additions do not change the number: no existing
  * signature moved). */
 #define LD_ABI_VERSION 15
 
@@ -627,6 +627,25 @@ int ld_residual_sub(const void* a, const void* b, void* out, int64_t n, const vo
 
 /* out = bf16(float(a) + float(r)); out == a is allowed. */
 int ld_residual_add(const void* a, const void* r, void* out, int64_t n, void* stream);
+
+/* ---- DiT CFG branch skipping (ld_dit_guidance.hip; landiff_amd/dit_guidance.py).  No reference op site: the reference evaluates
+ * both branches on every step.  The final pass of a step in its three forms; fp32, every product and sum rounded on its own:
+ *   xs = x*c_skip, d_u = e_u*c_out + xs, d_c = e_c*c_out + xs   (e_u, e_c: the bf16 rows of lin)
+ * H and W must be multiples of p.  The sums are reproducible bit for bit (ld_dit_cache.hip's scheme);
+ * workspace: LD_DIT_GUIDANCE_WS_FLOATS floats of device memory, free for reuse once the call's launches have run. ---- */
+#define LD_DIT_GUIDANCE_WS_FLOATS 5120
+
+/* A full step: lin [2][T*hp*wp][C*p*p] bf16 (uncond, cond), x / out / delta [T][C][H][W] f32.  delta = d_c - d_u,
+ * out = fma(scale, delta, d_u) (the bits of ld_unpatchify_cfg as built: its last multiply-add is one fused operation).  sums5 (device memory) = Sum e_u*e_c, Sum e_u^2, Sum e_c^2,
+ * Sum|delta - delta_old|, Sum|delta_old|; delta_old may be null (the last two are 0) or the buffer delta overwrites. */
+int ld_unpatchify_cfg_keep(const void* lin, const float* x, float* out, float* delta, const float* delta_old, float* sums5,
+                           float* workspace, int64_t T, int64_t C, int64_t H, int64_t W, int64_t p, float c_out, float c_skip,
+                           float scale, void* stream);
+
+/* A cond-only step: lin_cond [T*hp*wp][C*p*p] bf16.  delta null: out = d_c (scale is not read); else out = d_c + (scale - 1)*delta,
+ * scale - 1 formed in fp32. */
+int ld_unpatchify_cond(const void* lin_cond, const float* x, float* out, const float* delta, int64_t T, int64_t C, int64_t H,
+                       int64_t W, int64_t p, float c_out, float c_skip, float scale, void* stream);
 
 /* ---- 3D-VAE encoder (ld_vae_enc.hip; ContextParallelEncoder3D, cp_enc_dec.py:785-911, + DiagonalGaussianRegularizer,
  * regularizers.py:10-28,96-114).  Its convolutions, GroupNorms and residual adds are ld_conv_cl_bf16[_gn] / ld_groupnorm_*. ---- */

@@ -15,6 +15,7 @@ from landiff_amd.detokenizer import Detokenizer
 from landiff_amd.dit import ControlDiTRunner
 from landiff_amd.config import AttnWindowConfig
 from landiff_amd.dit_cache import as_config
+from landiff_amd.dit_guidance import as_config as as_guidance_config
 from landiff_amd.sampler import DiffusionSampler
 from landiff_amd.text import encode_t5_v11
 from landiff_amd.vae import VAEDecoder
@@ -63,7 +64,8 @@ class CogWrapper(torch.nn.Module):
     used only when forward() gets no seed (then hashed with the prompt, :190-194)."""
 
     def __init__(self, cfg: DiffusionInferConfig, ckpt_path: str, device, seed: int = 1234, text_encoder=None,
-                 feature_extractor=None, theia_ckpt: str | None = None, dit_cache=None, attn_window=None):
+                 feature_extractor=None, theia_ckpt: str | None = None, dit_cache=None, attn_window=None,
+                 dit_guidance=None):
         super().__init__()
         if feature_extractor is not None and theia_ckpt is not None:
             raise ValueError("give the Theia extractor as one of feature_extractor and theia_ckpt")
@@ -83,8 +85,13 @@ class CogWrapper(torch.nn.Module):
         # attn_window (not in the reference): None, a window in frames or a landiff_amd.config.AttnWindowConfig -- frame-window attention
         self.attn_window = AttnWindowConfig.as_config(attn_window)
         win = {} if self.attn_window is None else {"attn_window": self.attn_window}
+        # dit_guidance (not in the reference): None, a scale tolerance or a landiff_amd.dit_guidance.GuidanceSkipConfig -- cond-only steps
+        self.dit_guidance = as_guidance_config(dit_guidance)
+        if self.dit_guidance is not None:
+            win["dit_guidance"] = self.dit_guidance
+        planned = self.dit_cache is not None or self.dit_guidance is not None
         self.dit = ControlDiTRunner(st["dit_main"], st["dit_control"], cfg.dit, device, step_cache=self.dit_cache, **win,
-                                    plan_timesteps=[sp.timestep for sp in self.sampler.plan] if self.dit_cache is not None else None)
+                                    plan_timesteps=[sp.timestep for sp in self.sampler.plan] if planned else None)
         self.vae = VAEDecoder(st["vae"], cfg.vae, device)
         self._encoder = None            # tokenizer encoder half: built on the first video-conditioned call
         self._vae_encoder = None        # 3D-VAE encoder: built on the first encode_first_stage call
@@ -201,22 +208,30 @@ class CogModelInferWrapper(torch.nn.Module):
     theia_ckpt: a Theia model.safetensors (or its directory) that the HIP extractor is built from (landiff_amd.theia).
     dit_cache: None, a threshold or a landiff_amd.dit_cache.StepCacheConfig -- the opt-in DiT step cache (not in the reference).
     attn_window: None, a window in frames or a landiff_amd.config.AttnWindowConfig -- the opt-in frame-window attention of the DiT (not in
-    the reference; its effect on a trained checkpoint's output is unmeasured)."""
+    the reference; its effect on a trained checkpoint's output is unmeasured).
+    dit_guidance: None, a scale tolerance or a landiff_amd.dit_guidance.GuidanceSkipConfig -- the opt-in CFG branch skipping of the DiT (not
+    in the reference; its effect on a trained checkpoint's output is unmeasured; refused together with dit_cache)."""
 
     def __init__(self, ckpt_path: str, infer_cfg_path: str = DEFAULT_INFER_CFG, model_cfg_path: str = DEFAULT_MODEL_CFG,
                  device="cuda", text_encoder=None, feature_extractor=None, theia_ckpt: str | None = None, dit_cache=None,
-                 attn_window=None):
+                 attn_window=None, dit_guidance=None):
         super().__init__()
         self.infer_cfg_path, self.model_cfg_path, self.ckpt_path = infer_cfg_path, model_cfg_path, ckpt_path
         cfg = load_diffusion_config(_cfg_path(model_cfg_path), _cfg_path(infer_cfg_path))
         dev = torch.device(device if device != "cuda" else f"cuda:{torch.cuda.current_device()}")
         self.init_infer_model = CogWrapper(cfg, ckpt_path, dev, text_encoder=text_encoder, feature_extractor=feature_extractor,
-                                           theia_ckpt=theia_ckpt, dit_cache=dit_cache, attn_window=attn_window)
+                                           theia_ckpt=theia_ckpt, dit_cache=dit_cache, attn_window=attn_window,
+                                           dit_guidance=dit_guidance)
 
     def dit_cache_report(self):
         """dit_cache: the step cache's report of the last forward() (ControlDiTRunner.cache_report), else None."""
         m = self.init_infer_model
         return [dict(r) for r in m.dit.cache_report] if m.dit_cache is not None else None
+
+    def dit_guidance_report(self):
+        """dit_guidance: the report of the last forward() (ControlDiTRunner.guidance_report), else None."""
+        m = self.init_infer_model
+        return [dict(r) for r in m.dit.guidance_report] if m.dit_guidance is not None else None
 
     @torch.no_grad()
     def forward(self, x: VideoTask) -> VideoTask:

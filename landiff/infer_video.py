@@ -61,7 +61,27 @@ def parse_args(argv=None):
                              "frame.  The effect on quality is not measured.")
     parser.add_argument("--attn_window_dense_steps", type=int, default=0, metavar="K",
                         help="With --attn_window: the first K sampler steps of a video run full attention.")
+    parser.add_argument("--dit_cfg_tol", type=float, default=None, metavar="T",
+                        help="CFG branch skipping in the DiT (off by default): a sampler step whose guidance scale lies within T of 1 "
+                             "(T >= 0) evaluates the cond branch alone.  What each step did is written to "
+                             "<save_file_name>_dit_guidance.json.  The effect on quality is not measured.  (--cfg is the AR scale.)")
+    parser.add_argument("--dit_cfg_refresh", type=int, default=None, metavar="K",
+                        help="CFG branch skipping: both branches every K-th guided step (K >= 1), the steps between evaluate the cond "
+                             "branch alone and reuse the last cond - uncond difference.  The effect on quality is not measured.")
+    parser.add_argument("--dit_cfg_cos", type=float, default=None, metavar="C",
+                        help="CFG branch skipping: once the two branches' outputs reach a cosine of C (-1 < C <= 1) every later step "
+                             "of the video evaluates the cond branch alone.  The effect on quality is not measured.")
     args = parser.parse_args(argv)
+    args.dit_guidance = None
+    if args.dit_cfg_tol is not None or args.dit_cfg_refresh is not None or args.dit_cfg_cos is not None:
+        from landiff_amd.dit_guidance import REFUSE_STEP_CACHE, GuidanceSkipConfig
+        if args.dit_cache is not None:
+            parser.error(f"--dit_cache with --dit_cfg_tol / --dit_cfg_refresh / --dit_cfg_cos: {REFUSE_STEP_CACHE}")
+        try:
+            args.dit_guidance = GuidanceSkipConfig(scale_tolerance=args.dit_cfg_tol, refresh=args.dit_cfg_refresh,
+                                                   cos_threshold=args.dit_cfg_cos)
+        except ValueError as e:
+            parser.error(str(e))
     if args.attn_window is not None and args.attn_window < 0:
         parser.error(f"--attn_window takes an integer >= 0, got {args.attn_window}")
     if args.attn_window_dense_steps < 0 or (args.attn_window_dense_steps and args.attn_window is None):
@@ -199,6 +219,8 @@ def _dit_options(args) -> dict:
     kw = {}
     if getattr(args, "dit_cache", None) is not None:
         kw["dit_cache"] = args.dit_cache
+    if getattr(args, "dit_guidance", None) is not None:
+        kw["dit_guidance"] = args.dit_guidance
     if getattr(args, "attn_window", None) is not None:
         from landiff_amd.config import AttnWindowConfig
         kw["attn_window"] = AttnWindowConfig(frames=args.attn_window, dense_steps=getattr(args, "attn_window_dense_steps", 0))
@@ -215,6 +237,16 @@ def _write_dit_cache_report(args, stem, report):
     write_report_json(str(path), report)
 
 
+def _write_dit_guidance_report(args, stem, report):
+    """--dit_cfg_*: <stem>_dit_guidance.json, what each sampler step of the run that produced <stem>.mp4 evaluated."""
+    if getattr(args, "dit_guidance", None) is None:
+        return
+    from landiff_amd.dit_guidance import write_report_json
+    path = Path(f"{stem}_dit_guidance.json")
+    path.parent.mkdir(parents=True, exist_ok=True)
+    write_report_json(str(path), report)
+
+
 def infer_diffusion_samples(args, tokens, kept=None):
     """kept (--keep): the candidate indices to run, in rank order; None: every candidate."""
     model = _diffusion_model(args)
@@ -223,6 +255,7 @@ def infer_diffusion_samples(args, tokens, kept=None):
         row, (seed, stem) = tokens[i], names[i]
         task = model(VideoTask(save_file_name=f"{stem}.mp4", prompt=args.prompt, seed=seed, fps=8, semantic_token=row))
         _write_dit_cache_report(args, stem, model.dit_cache_report() if args.dit_cache is not None else None)
+        _write_dit_guidance_report(args, stem, model.dit_guidance_report() if getattr(args, "dit_guidance", None) is not None else None)
         save_video_tensor(task.result, task.save_file_name, fps=task.fps)
         print(f"save video to {task.save_file_name}")
 
@@ -233,6 +266,8 @@ def infer_diffusion(args, semantic_token):
                      semantic_token=semantic_token)
     task = model(task)
     _write_dit_cache_report(args, args.save_file_name, model.dit_cache_report() if args.dit_cache is not None else None)
+    _write_dit_guidance_report(args, args.save_file_name,
+                               model.dit_guidance_report() if getattr(args, "dit_guidance", None) is not None else None)
     save_video_tensor(task.result, task.save_file_name, fps=task.fps)
     print(f"save video to {task.save_file_name}")
 
@@ -272,7 +307,7 @@ def build_continuation(args):
     c = cfg.llm
     # the clip is chunk 0 of the stream: its multi-segment AR decode needs n_seg segments of KV cache
     _, _, n_seg = stream_plan(cfg, args.extend_chunks + 1, args.extend_prefix_frames)
-    win = {k: v for k, v in _dit_options(args).items() if k == "attn_window"}
+    win = {k: v for k, v in _dit_options(args).items() if k in ("attn_window", "dit_guidance")}
     pipe = LanDiffPipeline(cfg, st, dev, max_llm_frames=n_seg * c.segment_length, dit_cache=getattr(args, "dit_cache", None), **win)
     text = encode_flan_t5([args.prompt], dev, max_length=c.max_cond_tokens, model_path=c.text_encoder_path)[0]
     ctx = encode_t5_v11([args.prompt], resolve_ckpt_path(dcfg.t5_dir), cfg.dit.text_len, dev)
@@ -297,6 +332,7 @@ def extend_diffusion(args):
     new = pipe.extend_video(inp, args.extend_chunks, frames=clip, clip_tokens=clip_tokens,
                             prefix_frames=args.extend_prefix_frames)
     _write_dit_cache_report(args, args.save_file_name, pipe.dit_cache_reports)        # one list per appended chunk
+    _write_dit_guidance_report(args, args.save_file_name, pipe.dit_guidance_reports)
     frames = torch.cat([clip, new.cpu()], dim=0)
     path = f"{args.save_file_name}.mp4"
     save_video_tensor(frames, path, fps=8)

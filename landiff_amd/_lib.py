@@ -118,6 +118,8 @@ SIGNATURES: dict[str, list] = {
     "ld_absdiff_sums": [P, P, I64, P, P, I32, P],
     "ld_residual_sub": [P, P, P, I64, P, P, P, P],
     "ld_residual_add": [P, P, P, I64, P],
+    "ld_unpatchify_cfg_keep": [P, P, P, P, P, P, P, I64, I64, I64, I64, I64, c_float, c_float, c_float, P],
+    "ld_unpatchify_cond": [P, P, P, P, I64, I64, I64, I64, I64, c_float, c_float, c_float, P],
     "ld_place_cl": [P, P, I64, I64, I64, I64, I64, I64, I32, I32, I64, I64, I64, P],
     "ld_to_uint8": [P, I64, P, P, I64, P],
     "ld_latent_to_cl": [P, P, I64, I64, I64, I64, I64, c_float, I32, P],

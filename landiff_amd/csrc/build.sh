@@ -25,7 +25,7 @@ build_lib() {   # $1 = object dir, $2 = output, $3 = extra flags, $4.. = sources
       # round 5) it emits v_pk_*_f32 whose LOW lane reads the HIGH register of an operand pair (op_sel) for RoPE-like expressions, and
       # that operand form reads 0.0 in lanes 48-63 when MFMA waves of another kernel share the SIMD (tools/probe/pk_f32_coresidency.hip).
       # tools/audit_pk_f32.py checks the BUILT library for the form (a CPU test), whatever the flags of a file are.
-      case $s in ld_attn_pipe.hip|ld_attn_p16.hip|ld_attn_q64.hip|ld_attn_q64_exact.hip|ld_attn_q128.hip|ld_norm.hip|ld_dit_cache.hip) extra="-fno-slp-vectorize";; esac
+      case $s in ld_attn_pipe.hip|ld_attn_p16.hip|ld_attn_q64.hip|ld_attn_q64_exact.hip|ld_attn_q128.hip|ld_norm.hip|ld_dit_cache.hip|ld_dit_guidance.hip) extra="-fno-slp-vectorize";; esac
       # the forms of the decode step (one launch per operation / chained / one persistent launch) must produce the same bits: no
       # implicit mul+add fusion, whose outcome depends on the code around an expression (explicit fmaf / dot2 are unaffected).
       # -fno-slp-vectorize (round 5): the vectoriser turns e.g. RoPE's `a*c - b*s` / `a*s + b*c` into v_pk_mul_f32 / v_pk_add_f32 with
@@ -37,6 +37,10 @@ build_lib() {   # $1 = object dir, $2 = output, $3 = extra flags, $4.. = sources
       # ld_llm_wide.hip restates ld_gemv_kernel's RMSNorm staging and epilogue: the same rounding points need the same unfused mul / add.
       # The pattern covers the whole family, so that a new file of it cannot miss the flags.
       case $s in ld_llm*.hip) extra="-ffp-contract=off -fno-slp-vectorize";; esac
+      # ld_dit_guidance.hip (also named in the first case above; this later case is the one that takes effect): its cond / reuse
+      # forms promise separately rounded products and sums, and its full form states the one fma ld_unpatchify_cfg_kernel compiles
+      # to -- neither may depend on what the compiler chooses to contract.
+      case $s in ld_dit_guidance.hip) extra="-ffp-contract=off -fno-slp-vectorize";; esac
       hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -fvisibility=hidden -Wno-unused-result $extra $flags -c "$s" -o "$o" &
       pids+=($!)
     fi

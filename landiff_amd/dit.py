@@ -17,6 +17,7 @@ import torch
 from . import ops
 from .config import AttnWindowConfig, DiTConfig
 from .dit_cache import StepCacheConfig, StepCachePolicy
+from .dit_guidance import REFUSE_FP8, REFUSE_STEP_CACHE, GuidanceSkipConfig, GuidanceSkipPolicy, cosine
 
 BF = torch.bfloat16
 
@@ -81,7 +82,7 @@ class ControlDiTRunner:
 
     def __init__(self, main_sd: dict, control_sd: dict, cfg: DiTConfig, device, fp8_gemm: bool = False,
                  attn_exact: "bool | str | None" = None, step_cache: "StepCacheConfig | None" = None, plan_timesteps=None,
-                 attn_window: "AttnWindowConfig | int | None" = None):
+                 attn_window: "AttnWindowConfig | int | None" = None, dit_guidance: "GuidanceSkipConfig | None" = None):
         """fp8_gemm: BASELINE configs[4] -- the qkv / dense / 4h / 4h->h linears run on e4m3 operands; attention, norms,
         residual stream and every other layer stay bf16.  True / "row": weights quantised once per output channel,
         activations per row by a pass in front of each GEMM.  "mx": MXFP8 (one power-of-two scale per 32 K elements, applied
@@ -121,6 +122,15 @@ class ControlDiTRunner:
                 ops.attn_window_check(cfg.seq_len, cfg.text_len, cfg.grid_h * cfg.grid_w, self._win.frames)
             except ValueError as e:
                 raise ValueError(f"attn_window={self._win.frames} does not fit this DiT shape: {e}") from None
+        # dit_guidance (landiff_amd/dit_guidance.py; None = off): refused before any weight is touched where a cond-only step has no
+        # batch-1 form -- see _init_guidance()
+        if dit_guidance is not None:
+            if not isinstance(dit_guidance, GuidanceSkipConfig):
+                raise TypeError(f"dit_guidance must be None or a GuidanceSkipConfig, got {dit_guidance!r}")
+            if step_cache is not None:
+                raise ValueError(REFUSE_STEP_CACHE)
+            if fp8_gemm:
+                raise ValueError(REFUSE_FP8)
         self.main = _Branch(main_sd, cfg, False, device, fp8_gemm)
         self.ctrl = _Branch(control_sd, cfg, True, device, fp8_gemm)
         c, B = cfg, self.B
@@ -178,6 +188,7 @@ class ControlDiTRunner:
             self._fb_ev = [torch.cuda.Event(), torch.cuda.Event()]
             self._fb_pending = [False, False]
             self._fb_par = 0
+            self._fb_blocks = [0, 0]
             self._attn_blocks = B * c.heads * ((self.Npad + 255) // 256)
         self.attn_events = None                 # bench.py: list of (start, end, solo) HIP events around every attention launch
         self.gemm_events = None                 # bench.py: list of (start, end, flops) around the large linears (qkv, dense, 4h, 4h->h, zero)
@@ -186,6 +197,11 @@ class ControlDiTRunner:
         self._sc = None
         if step_cache is not None:
             self._init_step_cache(step_cache, plan_timesteps)
+        # dit_guidance (None = off: nothing is allocated and _final() ends in ld_unpatchify_cfg as it always did): steps that evaluate
+        # the cond branch alone, see _step_guided()
+        self._gd = None
+        if dit_guidance is not None:
+            self._init_guidance(dit_guidance, plan_timesteps)
 
     def _use(self, i: int):
         """Select the workspace set the layer methods read through self.ln / self.q / ... (set 1 exists only when the two chains overlap)."""
@@ -204,6 +220,7 @@ class ControlDiTRunner:
                 ops.gemm(ctx[b], br.text_w, out=dst[b], bias=br.text_b, add2=br.pos[: c.text_len])
         self.sem = semantic_feature.to(self.dev, BF).contiguous()
         self.reset_step_cache()
+        self.reset_guidance()
         self._win_step = 0
 
     # ---- pieces ----------------------------------------------------------------------------
@@ -290,17 +307,20 @@ class ControlDiTRunner:
         if self.attn_auto:
             ops.attn_last_fallbacks(self._fb[self._attn_slot:self._attn_slot + 1])
 
-    def _attn_auto_end_of_step(self):
+    def _attn_auto_end_of_step(self, step_B: int = B):
         """attn_exact="auto": hand this step's per-layer fallback counts to the host (asynchronously) and act on the previous step's."""
         par = self._fb_par
         self._fb_host[par].copy_(self._fb, non_blocking=True)
         self._fb_ev[par].record()
         self._fb_pending[par] = True
+        # step_B: batch rows of this step's launches (1 on a cond-only step of dit_guidance) -- the fraction is taken against the blocks
+        # of the launches that were made
+        self._fb_blocks[par] = self._attn_blocks * step_B // ControlDiTRunner.B
         prev = 1 - par
         if self._fb_pending[prev]:
             self._fb_ev[prev].synchronize()          # the step before this one: done, or about to be -- the GPU stays one step ahead
             self._fb_pending[prev] = False
-            limit = self.AUTO_EXACT_FRACTION * self._attn_blocks
+            limit = self.AUTO_EXACT_FRACTION * self._fb_blocks[prev]
             self.exact_layers.update(i for i, n in enumerate(self._fb_host[prev].tolist()) if n > limit)
         self._fb_par = prev
 
@@ -397,7 +417,10 @@ class ControlDiTRunner:
         lnv = self.ln.view(self.B, N, d)
         for b in range(self.B):
             ops.gemm(lnv[b, c.text_len:], m.lin_w, out=self.lin[b], bias=m.lin_b)
-        ops.unpatchify_cfg(self.lin, x, out, c.patch, c_out, c_skip, cfg_scale)
+        if self._gd is None:
+            ops.unpatchify_cfg(self.lin, x, out, c.patch, c_out, c_skip, cfg_scale)
+        else:
+            self._gd_final(x, c_out, c_skip, cfg_scale, out)
         return out
 
     def _step_overlapped(self, x, timestep, c_out, c_skip, cfg_scale, out):
@@ -537,11 +560,136 @@ class ControlDiTRunner:
         ops.residual_add(self.sc_h0, self.sc_residual, self.h)
         return self._final(self.h, x, c_out, c_skip, cfg_scale, out), False
 
+    # ---- CFG branch skipping ---------------------------------------------------------------
+    _GD_SET_KEYS = ("ln", "qkv", "q", "k", "vt", "attn", "mlp", "temb", "emb_h", "emb", "tvec")      # (patches has no batch dimension)
+    _GD_ATTRS = ("h", "hc", "ada_main", "ada_ctrl", "fada", "lin", "txt_main", "txt_ctrl")
+
+    def _init_guidance(self, cfg: GuidanceSkipConfig, plan_timesteps):
+        if plan_timesteps is None:
+            raise ValueError("ControlDiTRunner(dit_guidance=...) needs plan_timesteps (the timesteps of schedule.build_plan, in sampler "
+                             "order): a step is identified by the position of its timestep")
+        ts = [float(t) for t in plan_timesteps]
+        if len(set(ts)) != len(ts) or len(ts) < 1:
+            raise ValueError("plan_timesteps must be distinct")
+        if cfg.plan is not None and len(cfg.plan) != len(ts):
+            raise ValueError(f"GuidanceSkipConfig.plan has {len(cfg.plan)} entries for {len(ts)} timesteps")
+        self._gd = GuidanceSkipPolicy(cfg)
+        self._gd_index = {t: i for i, t in enumerate(ts)}
+        c, N, S = self.cfg, self.N, len(ts)
+        # the cond row of every batch-major buffer as a batch-1 view: no second set of activations.  [B*N, ...] buffers split at row N,
+        # [B, ...] buffers at row 1; both are contiguous, and a view keeps the batch stride its kernels are given (_ada()).
+        row1 = lambda t: t[N:] if t.shape[0] == self.M else t[1:]
+        self._gd_full = dict(_sets=self._sets, ctrl_out=self.ctrl_out, **{k: getattr(self, k) for k in self._GD_ATTRS})
+        self._gd_cond = dict(_sets=[dict(ws, **{k: row1(ws[k]) for k in self._GD_SET_KEYS}) for ws in self._sets],
+                             ctrl_out=[row1(t) for t in self.ctrl_out], **{k: row1(getattr(self, k)) for k in self._GD_ATTRS})
+        f32 = lambda *s: torch.empty(*s, device=self.dev, dtype=torch.float32)
+        self._gd_delta = f32(c.latent_frames, c.in_channels, c.latent_h, c.latent_w)      # d_c - d_u of the latest full step
+        self._gd_sums = torch.zeros(S, 5, device=self.dev, dtype=torch.float32)           # the five sums of step s in row s
+        self._gd_ws = f32(ops.DIT_GUIDANCE_WS_FLOATS)
+        self._gd_sums_host = torch.zeros(S, 5, dtype=torch.float32).pin_memory()
+        self._gd_ev = torch.cuda.Event()
+        self._gd_report, self._gd_pending = [], []
+        self.reset_guidance()
+
+    def _gd_select(self, cond: bool):
+        """Point the step's buffers at the cond row (B = 1, M = N) or back at the CFG pair."""
+        for k, v in (self._gd_cond if cond else self._gd_full).items():
+            setattr(self, k, v)
+        self.B = 1 if cond else ControlDiTRunner.B
+        self.M = self.B * self.N
+        self._use(0)
+
+    def reset_guidance(self):
+        """Forget the kept difference, the reuse count and the cos rule: the steps after this call depend on nothing that ran before
+        it.  (set_condition() and a timestep that does not decrease do the same.)"""
+        if self._gd is None:
+            return
+        self._gd_resolve()
+        self._gd.reset()
+        self._gd_have_delta = False
+        self._gd_delta_from = None
+        self._gd_last_full = None            # report row of the latest full step
+        self._gd_last_t = None
+        self._gd_report = []
+
+    def _gd_resolve(self):
+        """Fill cos / delta_rel_l1 of report rows whose five sums were still on their way."""
+        if self._gd_pending:
+            self._gd_ev.synchronize()                  # (copies on one stream complete in order: the last event covers all)
+            for row, had_old in self._gd_pending:
+                uc, uu, cc, num, den = (float(v) for v in self._gd_sums_host[row["index"]])
+                row["cos"] = cosine(uc, uu, cc)
+                if had_old:
+                    row["delta_rel_l1"] = num / den if den != 0.0 else None
+            self._gd_pending = []
+
+    @property
+    def guidance_report(self) -> list:
+        """One dict per step since the last reset: index, timestep, cfg_scale, mode ("full" / "reuse" / "cond"), cos (full steps: the
+        cosine of the two branches' network outputs), delta_rel_l1 (full steps that replaced an older difference: its relative L1
+        change), delta_from (reuse steps: index of the full step whose difference was used); None where a figure does not apply."""
+        if self._gd is None:
+            return []
+        self._gd_resolve()
+        return self._gd_report
+
+    @property
+    def guidance_delta(self):
+        """The kept d_c - d_u [T, C, H, W] fp32 of the latest full step (None: feature off, or no full step since the last reset)."""
+        return self._gd_delta if self._gd is not None and self._gd_have_delta else None
+
+    def _gd_final(self, x, c_out, c_skip, cfg_scale, out):
+        """The last launch of _final() with dit_guidance on, by the mode _step_guided() chose."""
+        p, row = self.cfg.patch, self._gd_report[-1]
+        if row["mode"] == "full":
+            s = row["index"]
+            old = self._gd_delta if self._gd_have_delta else None
+            ops.unpatchify_cfg_keep(self.lin, x, out, self._gd_delta, p, c_out, c_skip, cfg_scale, delta_old=old, sums=self._gd_sums[s],
+                                    workspace=self._gd_ws)
+            self._gd_sums_host[s].copy_(self._gd_sums[s], non_blocking=True)
+            self._gd_ev.record()
+            self._gd_pending.append((row, old is not None))
+            self._gd_have_delta, self._gd_delta_from, self._gd_last_full = True, s, row
+        else:                                                   # (self.lin is the cond row's view here)
+            ops.unpatchify_cond(self.lin[0], x, out, p, c_out, c_skip, cfg_scale, delta=self._gd_delta if row["mode"] == "reuse" else None)
+
+    def _step_guided(self, x, timestep, c_out, c_skip, cfg_scale, out):
+        """step() with dit_guidance on.  A full step is _step() as it stands -- every launch in its order, so the same bits -- ending
+        in ld_unpatchify_cfg_keep instead of ld_unpatchify_cfg.  A cond or reuse step is _step() too, over batch-1 views of the cond
+        row of every buffer with B = 1, M = N, ending in ld_unpatchify_cond.  Only with cos_threshold does a step wait for anything:
+        the five floats of the latest full step, sent by a pinned non-blocking copy when that step ended."""
+        t = float(timestep)
+        if t not in self._gd_index:
+            raise ValueError(f"timestep {timestep} is not one of plan_timesteps")
+        if self._gd_last_t is not None and not t < self._gd_last_t:
+            self.reset_guidance()                         # a new sampler run: the result depends on this run's inputs alone
+        self._gd_last_t = t
+        s, S = self._gd_index[t], len(self._gd_index)
+        last_cos = None
+        if self._gd.cfg.cos_threshold is not None and not self._gd.cos_fired and self._gd_last_full is not None:
+            self._gd_resolve()
+            last_cos = self._gd_last_full["cos"]
+        mode = self._gd.decide(s, S, cfg_scale, self._gd_have_delta, last_cos)
+        self._gd_report.append(dict(index=s, timestep=timestep, cfg_scale=float(cfg_scale), mode=mode, cos=None, delta_rel_l1=None,
+                                    delta_from=self._gd_delta_from if mode == "reuse" else None))
+        if mode == "full":
+            return self._step(x, timestep, c_out, c_skip, cfg_scale, out)
+        self._gd_select(True)
+        try:
+            return self._step(x, timestep, c_out, c_skip, cfg_scale, out)
+        finally:
+            self._gd_select(False)
+
     def step(self, x: torch.Tensor, timestep: int, c_out: float, c_skip: float, cfg_scale: float, out: torch.Tensor):
         """x, out: [1, T, C, H, W] fp32.  out = CFG(denoised_uncond, denoised_cond)."""
         if self._win is not None:                         # (every sampler step counts, computed or skipped by the step cache)
             self._win_on = self._win_step >= self._win.dense_steps
             self._win_step += 1
+        if self._gd is not None:
+            r = self._step_guided(x, timestep, c_out, c_skip, cfg_scale, out)
+            if self.attn_auto:                            # (a cond-only step's launches had one batch row)
+                self._attn_auto_end_of_step(self.B if self._gd_report[-1]["mode"] == "full" else 1)
+            return r
         if self._sc is not None:
             r, computed = self._step_cached(x, timestep, c_out, c_skip, cfg_scale, out)
             if self.attn_auto and computed:               # (a skipped step launched no attention: no new counts)

@@ -825,6 +825,52 @@ def residual_add(a, r, out=None):
     return out
 
 
+# ---- DiT CFG branch skipping (ld_dit_guidance.hip) ---------------------------------------------------
+DIT_GUIDANCE_WS_FLOATS = 5120      # LD_DIT_GUIDANCE_WS_FLOATS of include/landiff_hip.h
+
+
+def _guidance_f32(name, x, *tensors):
+    """x [1, T, C, H, W] (or [T, C, H, W]) contiguous fp32; the other tensors (None skipped) fp32, contiguous, of x's element count."""
+    for t in (x,) + tensors:
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != x.numel():
+            raise ValueError(f"{name}: x / out / delta must be contiguous float32 of one size, got {tuple(t.shape)} {t.dtype}")
+    return tuple(x.shape[-4:])
+
+
+def unpatchify_cfg_keep(lin, x, out, delta, p, c_out, c_skip, scale, delta_old=None, sums=None, workspace=None):
+    """A full CFG step that keeps its difference: out = d_u + scale * delta with delta = d_c - d_u (out: the bits of unpatchify_cfg).
+    delta_old (may be `delta` itself, read before it is overwritten) or None.  Returns sums f32 [5] = (sum e_u e_c, sum e_u^2,
+    sum e_c^2, sum|delta - delta_old|, sum|delta_old|), fp32 sums that repeat bit for bit; the last two are 0 without delta_old."""
+    T, C, H, W = _guidance_f32("unpatchify_cfg_keep", x, out, delta, delta_old)
+    _bf16(lin, "lin")
+    if not lin.is_contiguous() or lin.numel() != 2 * x.numel():
+        raise ValueError(f"unpatchify_cfg_keep: lin must be contiguous [2, n_img, C*p*p], got {tuple(lin.shape)}")
+    if sums is None:
+        sums = torch.empty(5, device=x.device, dtype=torch.float32)
+    if workspace is None:
+        workspace = torch.empty(DIT_GUIDANCE_WS_FLOATS, device=x.device, dtype=torch.float32)
+    for t, n in ((sums, 5), (workspace, DIT_GUIDANCE_WS_FLOATS)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < n:
+            raise ValueError(f"unpatchify_cfg_keep: sums / workspace must be contiguous float32 of at least 5 / {DIT_GUIDANCE_WS_FLOATS} elements")
+    check(_lib.load().ld_unpatchify_cfg_keep(_ptr(lin), _ptr(x), _ptr(out), _ptr(delta), _ptr(delta_old), _ptr(sums), _ptr(workspace),
+                                             T, C, H, W, p, float(c_out), float(c_skip), float(scale), _stream()),
+          "ld_unpatchify_cfg_keep")
+    return sums
+
+
+def unpatchify_cond(lin_cond, x, out, p, c_out, c_skip, scale=1.0, delta=None):
+    """A cond-only step: out = d_c (delta None) or d_c + (scale - 1) * delta (the kept difference of an earlier full step)."""
+    T, C, H, W = _guidance_f32("unpatchify_cond", x, out, delta)
+    _bf16(lin_cond, "lin_cond")
+    if not lin_cond.is_contiguous() or lin_cond.numel() != x.numel():
+        raise ValueError(f"unpatchify_cond: lin_cond must be contiguous [n_img, C*p*p], got {tuple(lin_cond.shape)}")
+    check(_lib.load().ld_unpatchify_cond(_ptr(lin_cond), _ptr(x), _ptr(out), _ptr(delta), T, C, H, W, p, float(c_out), float(c_skip),
+                                         float(scale), _stream()), "ld_unpatchify_cond")
+    return out
+
+
 # ---- 3D-VAE encoder (ld_vae_enc.hip) ----------------------------------------------------------------
 def vae_enc_place_input(frames, out_padded):
     """frames uint8 / f32 [F, H, W, 3] -> out_padded bf16 [F+2, H+2, W+2, Cpad] (every element written)."""

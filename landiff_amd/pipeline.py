@@ -19,6 +19,7 @@ from .config import AttnWindowConfig, PipelineConfig
 from .detokenizer import Detokenizer
 from .dit import ControlDiTRunner
 from .dit_cache import as_config
+from .dit_guidance import as_config as as_guidance_config
 from .llm import LLMRunner
 from .sampler import DiffusionSampler
 from .vae import VAEDecoder
@@ -42,7 +43,8 @@ class PromptInputs:
 
 class LanDiffPipeline:
     def __init__(self, cfg: PipelineConfig, states: dict, device="cuda:0", max_llm_frames: int | None = None,
-                 fp8_gemm: bool = False, theia=None, max_samples: int = 1, wide_samples: int = 0, dit_cache=None, attn_window=None):
+                 fp8_gemm: bool = False, theia=None, max_samples: int = 1, wide_samples: int = 0, dit_cache=None, attn_window=None,
+                 dit_guidance=None):
         if not torch.cuda.is_available():
             raise _lib.LandiffHipError("LanDiffPipeline needs an MI355X GPU: there is no CPU fallback")
         _lib.load()
@@ -66,9 +68,17 @@ class LanDiffPipeline:
         # checkpoint's output is not measured; handed on only when given
         self.attn_window = AttnWindowConfig.as_config(attn_window)
         win = {} if self.attn_window is None else {"attn_window": self.attn_window}
+        # dit_guidance: None (off), a scale tolerance or a dit_guidance.GuidanceSkipConfig -- sampler steps that evaluate the cond
+        # branch alone (ControlDiTRunner(dit_guidance=...)); never the headline configuration, and what any setting costs in quality on
+        # a trained checkpoint is not measured; handed on only when given.  With dit_cache or fp8_gemm the runner refuses.
+        self.dit_guidance = as_guidance_config(dit_guidance)
+        if self.dit_guidance is not None:
+            win["dit_guidance"] = self.dit_guidance
+        planned = self.dit_cache is not None or self.dit_guidance is not None
         self.dit = ControlDiTRunner(states["dit_main"], states["dit_control"], cfg.dit, self.dev, fp8_gemm=fp8_gemm,
                                     step_cache=self.dit_cache, **win,
-                                    plan_timesteps=[sp.timestep for sp in self.sampler.plan] if self.dit_cache is not None else None)
+                                    plan_timesteps=[sp.timestep for sp in self.sampler.plan] if planned else None)
+        self.dit_guidance_reports = []    # one ControlDiTRunner.guidance_report per sampler run (see dit_guidance_report())
         self.dit_cache_reports = []       # one ControlDiTRunner.cache_report per sampler run (see dit_cache_report())
         self.vae = VAEDecoder(states["vae"], cfg.vae, self.dev)
         # the 3D-VAE encoder of extend_video(frames=...): built when the VAE state carries 'encoder.*' keys
@@ -115,7 +125,15 @@ class LanDiffPipeline:
         z = self.sampler.run(self.dit.step, noise, **kw)
         if self.dit_cache is not None:
             self.dit_cache_reports.append([dict(r) for r in self.dit.cache_report])
+        if self.dit_guidance is not None:
+            self.dit_guidance_reports.append([dict(r) for r in self.dit.guidance_report])
         return z
+
+    def dit_guidance_report(self):
+        """dit_guidance: what the last sampler run did -- one dict per step (index, timestep, cfg_scale, mode, cos, delta_rel_l1,
+        delta_from; ControlDiTRunner.guidance_report).  None with the feature off or before the first run.
+        self.dit_guidance_reports holds one report per sampler run, cleared where dit_cache_reports is."""
+        return self.dit_guidance_reports[-1] if self.dit_guidance_reports else None
 
     def dit_cache_report(self):
         """dit_cache: what the step cache did in the last sampler run -- one dict per step (index, timestep, input_rel_l1, accumulated,
@@ -160,6 +178,7 @@ class LanDiffPipeline:
         from dataclasses import replace
         seeds = [int(s) for s in seeds]
         self.dit_cache_reports = []
+        self.dit_guidance_reports = []
         if keep is not None and not 1 <= int(keep) <= len(seeds):
             raise ValueError(f"generate_samples: keep={keep} outside [1, {len(seeds)}] (the number of seeds)")
         kw = dict(motion_score=inp.motion_score, num_frames=self.cfg.llm.segment_length, guidance_scale=inp.cfg, temperature=1.0,
@@ -210,6 +229,7 @@ class LanDiffPipeline:
         if not inputs:
             return []
         self.dit_cache_reports = []
+        self.dit_guidance_reports = []
         for inp in inputs:
             assert inp.seed, "generate_many needs a non-zero seed per prompt (a zero seed would draw from the shared default generator)"
         side = torch.cuda.Stream(device=self.dev, priority=-1)
@@ -327,6 +347,7 @@ class LanDiffPipeline:
         T, new, n_seg = self.stream_plan(n_chunks, prefix_frames)
         per_seg = self.cfg.tok.num_latent_tokens
         self.dit_cache_reports = []
+        self.dit_guidance_reports = []
         t0 = time.perf_counter()
         seg_tokens = None          # segment s -> its token ids, int64 [per_seg] on the device
         decode_thread = None
@@ -426,6 +447,7 @@ class LanDiffPipeline:
         T, new, n_seg = self.stream_plan(n_chunks + 1, prefix_frames)
         per_seg = self.cfg.tok.num_latent_tokens
         self.dit_cache_reports = []
+        self.dit_guidance_reports = []
         if (frames is None) == (clip_latent is None):
             raise ValueError("extend_video takes the clip as exactly one of frames and clip_latent")
         if tokens is not None and clip_tokens is not None:
