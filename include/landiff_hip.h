@@ -32,8 +32,8 @@ extern "C" {
  * ld_qkv_split gained mode 2.  13: ld_gemm_route was added.  14: ld_gemv_pairs, ld_llm_decode_forward_pairs and
  * ld_llm_sample_advance_pairs were added.  15: ld_llm_token_logprobs and ld_llm_head_f32 were added;
  * ld_gemv_wide, ld_llm_decode_forward_wide and ld_llm_sample_advance_wide joined later, and so did ld_absdiff_sums,
- * ld_residual_sub, ld_residual_add, ld_attn_fwd_bf16_window, ld_attn_window_plan, ld_unpatchify_cfg_keep and ld_unpatchify_cond (additions do not change the number: no existing
- * signature moved). */
+ * ld_residual_sub, ld_residual_add, ld_attn_fwd_bf16_window, ld_attn_window_plan, ld_unpatchify_cfg_keep, ld_unpatchify_cond, ld_latent_pin and ld_mask_to_latent (additions do not change
+ * the number: no existing signature moved). */
 #define LD_ABI_VERSION 15
 
 int ld_version(void);
@@ -591,6 +591,20 @@ int ld_unpatchify_cfg(const void* lin, const float* x, float* out, int64_t T, in
 
 /* out = a*x + b*y + c*z (y, z optional), products rounded separately, summed left to right (sampling.py:613-644,771-781). */
 int ld_axpbypcz(float* out, const float* x, float a, const float* y, float b, const float* z, float c, int64_t n, void* stream);
+
+/* ---- clip editing (ld_edit.hip; LanDiffPipeline.edit_video) ----
+ * The sampler's re-noise / pin of known latents, the `sdedit` branch of VPSDEDPMPP2MSampler.__call__ (sampling.py:800-835) over any
+ * set of latent cells: x [T][C][H][W] f32 in place, mask [T][H][W] u8 broadcast over C (null: every element).  Where the mask is
+ * non-zero x = alpha*known + sigma*noise, the two products and the sum rounded separately; with noise null x = known (a copy).
+ * Elsewhere x is not written.  noise may alias x; known may not. */
+int ld_latent_pin(float* x, const float* known, const float* noise, const uint8_t* mask, float alpha, float sigma, int64_t T,
+                  int64_t C, int64_t H, int64_t W, void* stream);
+
+/* Pixel keep-mask [F][Hp][Wp] u8 (non-zero = keep) -> latent keep-mask [(F + 3) / 4][Hp / 8][Wp / 8] u8 (1 / 0): cell (t, i, j)
+ * is kept only if every pixel of its block is -- frames {0} for t = 0 and {4t-3 .. 4t} for t >= 1 (the VAE's causal 1 + 4k frame
+ * mapping), rows 8i .. 8i+7, columns 8j .. 8j+7.  LD_ERR_INVALID unless F % 4 == 1, Hp % 8 == 0, Wp % 8 == 0 and mask_px is
+ * 8-byte aligned. */
+int ld_mask_to_latent(const uint8_t* mask_px, uint8_t* out, int64_t F, int64_t Hp, int64_t Wp, void* stream);
 
 /* timestep_embedding (sgm/modules/diffusionmodules/util.py:207-233): t [B] f32 -> [B][dim] bf16 (cos || sin). */
 int ld_timestep_embedding(const float* t, void* out, int64_t B, int64_t dim, float max_period, void* stream);

@@ -50,6 +50,23 @@ def parse_args(argv=None):
     parser.add_argument("--first_frame", type=str, default=None,
                         help="Image-guided generation (use_gt_first_frame): a uint8 [H, W, 3] .npy or an image imageio can "
                              "read, tokenized by the Theia extractor; its I-frame tokens start the AR decode.")
+    parser.add_argument("--edit_video", type=str, default=None,
+                        help="Edit this clip instead of generating from scratch (LanDiffPipeline.edit_video): a uint8 [4T-3, H, W, 3] "
+                             ".npy or an mp4 when imageio can read it -- exactly one chunk at the model's frame size (49 frames of "
+                             "480 x 720), never resized.  Writes the edited clip and <save_file_name>_edit.json.")
+    parser.add_argument("--edit_strength", type=float, default=0.6, metavar="S",
+                        help="With --edit_video: the share of the sampler's steps that run, in (0, 1].  1.0 regenerates from pure "
+                             "noise; smaller values start later, from the re-noised clip, and stay closer to it.")
+    parser.add_argument("--edit_mask", type=str, default=None,
+                        help="With --edit_video: a .npy keep-mask (bool or uint8, non-zero = keep the clip), [4T-3, H, W] in pixels or "
+                             "[T, H/8, W/8] in latent cells; the rest is regenerated.")
+    parser.add_argument("--edit_tokens", type=str, default=None, metavar="{from_frames,prompt,PATH.npy}",
+                        help="With --edit_video: where the semantic tokens come from -- the clip's own frames (Theia extractor; the "
+                             "default with --theia_ckpt), an AR decode from the prompt (the default without), or a token .npy of "
+                             "llm_infer.")
+    parser.add_argument("--edit_clean_known", action="store_true",
+                        help="With --edit_video and --edit_mask: pin the kept cells to the clean clip latent at every step instead "
+                             "of its re-noised version.")
     parser.add_argument("--dit_cache", type=str, default=None, metavar="THRESH",
                         help="DiT step cache (off by default): a sampler step whose first-block input moved by less than THRESH "
                              "(accumulated relative L1, a float >= 0) since the last computed step reuses that step's residual across "
@@ -60,7 +77,8 @@ def parse_args(argv=None):
                              "latent frames each side of its own (W >= 0; per 256-row block, a ragged superset) instead of to every "
                              "frame.  The effect on quality is not measured.")
     parser.add_argument("--attn_window_dense_steps", type=int, default=0, metavar="K",
-                        help="With --attn_window: the first K sampler steps of a video run full attention.")
+                        help="With --attn_window: the first K sampler steps of a video run full attention (executed steps: with "
+                             "--edit_video they count from the step the edit starts at).")
     parser.add_argument("--dit_cfg_tol", type=float, default=None, metavar="T",
                         help="CFG branch skipping in the DiT (off by default): a sampler step whose guidance scale lies within T of 1 "
                              "(T >= 0) evaluates the cond branch alone.  What each step did is written to "
@@ -97,6 +115,19 @@ def parse_args(argv=None):
     max_n = 16 if args.decode_engine == "mfma" else 4
     if not 1 <= args.num_samples <= max_n:
         parser.error(f"--num_samples must be between 1 and {max_n}" + ("" if max_n == 16 else " (1 and 16 with --decode_engine mfma)"))
+    if args.edit_video:
+        if args.extend_video:
+            parser.error("--edit_video changes a clip, --extend_video continues one: give one of them")
+        if args.keep is not None:
+            parser.error("--keep ranks candidates generated from a prompt, not --edit_video")
+        if args.num_samples > 1:
+            parser.error("--num_samples applies to generation from a prompt, not to --edit_video")
+        if args.first_frame:
+            parser.error("--first_frame guides generation from a prompt, not --edit_video")
+        if not 0.0 < args.edit_strength <= 1.0:
+            parser.error(f"--edit_strength (the share of steps --edit_video runs) must be in (0, 1], got {args.edit_strength}")
+        if args.edit_tokens is None:
+            args.edit_tokens = "from_frames" if args.theia_ckpt else "prompt"
     if args.num_samples > 1 and args.extend_video:
         parser.error("--num_samples applies to generation from a prompt, not to --extend_video")
     if args.num_samples > 1 and not all(args.seed + i for i in range(args.num_samples)):
@@ -287,8 +318,8 @@ def load_clip(path: str) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(arr))
 
 
-def build_continuation(args):
-    """The pipeline and prompt inputs --extend_video runs: the diffusion stage's YAML files and checkpoint tree (as
+def build_continuation(args, n_seg=None, theia=None):
+    """The pipeline and prompt inputs --extend_video runs (and, with n_seg = 1 and its own `theia` choice, --edit_video): the diffusion stage's YAML files and checkpoint tree (as
     CogModelInferWrapper reads them), the VAE encoder's weights ('encoder.*' of the VAE checkpoint, then of the diffusion
     checkpoint's first stage), the LLM checkpoint, and the prompt through both T5 encoders.  -> (LanDiffPipeline, PromptInputs)."""
     from landiff.diffusion.dif_infer import DEFAULT_INFER_CFG, DEFAULT_MODEL_CFG, _cfg_path
@@ -306,13 +337,14 @@ def build_continuation(args):
     st["llm"] = load_llm_state(args.llm_ckpt)
     c = cfg.llm
     # the clip is chunk 0 of the stream: its multi-segment AR decode needs n_seg segments of KV cache
-    _, _, n_seg = stream_plan(cfg, args.extend_chunks + 1, args.extend_prefix_frames)
+    if n_seg is None:
+        _, _, n_seg = stream_plan(cfg, args.extend_chunks + 1, args.extend_prefix_frames)
     win = {k: v for k, v in _dit_options(args).items() if k in ("attn_window", "dit_guidance")}
     pipe = LanDiffPipeline(cfg, st, dev, max_llm_frames=n_seg * c.segment_length, dit_cache=getattr(args, "dit_cache", None), **win)
     text = encode_flan_t5([args.prompt], dev, max_length=c.max_cond_tokens, model_path=c.text_encoder_path)[0]
     ctx = encode_t5_v11([args.prompt], resolve_ckpt_path(dcfg.t5_dir), cfg.dit.text_len, dev)
     inp = PromptInputs(text, ctx, seed=args.seed, cfg=args.cfg, motion_score=args.motion_score)
-    if args.theia_ckpt and not args.extend_tokens:
+    if (args.theia_ckpt and not args.extend_tokens) if theia is None else theia:
         pipe.theia = build_theia_tokenizer(args, dev)
     return pipe, inp
 
@@ -340,6 +372,42 @@ def extend_diffusion(args):
     return frames
 
 
+def load_mask(path: str) -> torch.Tensor:
+    """--edit_mask: a bool or uint8 .npy [F, H, W] (pixels) or [T, h, w] (latent cells), non-zero = keep -> bool tensor."""
+    arr = np.load(path)
+    if arr.dtype not in (np.bool_, np.uint8) or arr.ndim != 3:
+        raise ValueError(f"{path}: expected a bool or uint8 keep-mask [F, H, W] or [T, h, w], got {arr.dtype} {arr.shape}")
+    return torch.from_numpy(np.ascontiguousarray(arr != 0))
+
+
+def edit_diffusion(args):
+    """--edit_video: LanDiffPipeline.edit_video on the clip -- the sampler started at the step --edit_strength picks from the
+    re-noised clip latent, the cells --edit_mask keeps held on the clip, the semantic tokens from the clip's frames (--edit_tokens
+    from_frames: the default with --theia_ckpt), from the prompt or from a file.  Writes the edited clip and <name>_edit.json."""
+    from landiff_amd.pipeline import write_edit_json
+    clip = load_clip(args.edit_video)
+    mask = load_mask(args.edit_mask) if args.edit_mask else None
+    pipe, inp = build_continuation(args, n_seg=1, theia=args.edit_tokens == "from_frames")
+    kw = {}
+    if args.edit_tokens == "from_frames":
+        kw["clip_tokens"] = "from_frames"
+    elif args.edit_tokens != "prompt":
+        kw["tokens"] = torch.from_numpy(np.load(args.edit_tokens)).reshape(-1)
+    frames = pipe.edit_video(inp, frames=clip, strength=args.edit_strength, keep_mask=mask,
+                             known_noise=not args.edit_clean_known, **kw).cpu()
+    _write_dit_cache_report(args, args.save_file_name, pipe.dit_cache_report() if getattr(args, "dit_cache", None) is not None else None)
+    _write_dit_guidance_report(args, args.save_file_name,
+                               pipe.dit_guidance_report() if getattr(args, "dit_guidance", None) is not None else None)
+    path = Path(f"{args.save_file_name}_edit.json")
+    path.parent.mkdir(parents=True, exist_ok=True)
+    write_edit_json(str(path), pipe.last_edit)
+    save_video_tensor(frames, f"{args.save_file_name}.mp4", fps=8)
+    e = pipe.last_edit
+    print(f"save video to {args.save_file_name}.mp4 (steps {e['start_step']}..{e['start_step'] + e['steps_run'] - 1}, "
+          f"{e['kept_cells']} of {e['total_cells']} latent cells kept, tokens: {e['tokens_source']})")
+    return frames
+
+
 def main():
     import os
 
@@ -349,6 +417,9 @@ def main():
         from landiff_amd.pipeline import pin_rank_cores
         pin_rank_cores(local_rank, int(os.environ["LOCAL_WORLD_SIZE"]))
     torch.cuda.set_device(local_rank)
+    if args.edit_video:
+        edit_diffusion(args)
+        return
     if args.extend_video:
         extend_diffusion(args)
         return

@@ -742,6 +742,50 @@ def axpbypcz(out, x, a, y=None, b=0.0, z=None, c=0.0):
     return out
 
 
+# ---- clip editing (ld_edit.hip) ----------------------------------------------------------------------
+def _keep_mask(mask, name):
+    if mask.dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f"{name}: the mask must be uint8 or bool, got {mask.dtype}")
+    if mask.dim() != 3 or not mask.is_contiguous():
+        raise ValueError(f"{name}: the mask must be a contiguous 3-d tensor, got {tuple(mask.shape)}")
+
+
+def latent_pin(x, known, noise=None, mask=None, alpha=1.0, sigma=0.0):
+    """In place on x [T, C, H, W] fp32 (leading 1s allowed): where mask [T, H, W] (uint8 / bool, broadcast over C; None: everywhere)
+    is set, x = alpha * known + sigma * noise with separately rounded products -- or x = known, a copy, with noise None.  Elsewhere
+    x keeps its bits.  noise may be x itself."""
+    if x.dim() < 4 or any(s != 1 for s in x.shape[:-4]):
+        raise ValueError(f"latent_pin: x must be [T, C, H, W] (leading 1s allowed), got {tuple(x.shape)}")
+    T, C, H, W = x.shape[-4:]
+    for t, name in ((x, "x"), (known, "known"), (noise, "noise")):
+        if t is None:
+            continue
+        if t.dtype != torch.float32:
+            raise TypeError(f"latent_pin: {name} must be float32, got {t.dtype}")
+        if t.shape != x.shape or not t.is_contiguous():
+            raise ValueError(f"latent_pin: {name} must be contiguous and of x's shape {tuple(x.shape)}, got {tuple(t.shape)}")
+    if mask is not None:
+        _keep_mask(mask, "latent_pin")
+        if tuple(mask.shape) != (T, H, W):
+            raise ValueError(f"latent_pin: the mask must be [{T}, {H}, {W}] for x {tuple(x.shape)}, got {tuple(mask.shape)}")
+    check(_lib.load().ld_latent_pin(_ptr(x), _ptr(known), _ptr(noise), _ptr(mask), float(alpha), float(sigma), T, C, H, W, _stream()),
+          "ld_latent_pin")
+    return x
+
+
+def mask_to_latent(mask_px, out=None):
+    """Pixel keep-mask [F, Hp, Wp] (uint8 / bool, non-zero = keep) -> latent keep-mask uint8 [(F + 3) // 4, Hp // 8, Wp // 8]: a cell
+    is kept only if every pixel of its block is (frames {0} / {4t-3 .. 4t}, an 8 x 8 tile).  F % 4 != 1, Hp % 8 or Wp % 8: refused."""
+    _keep_mask(mask_px, "mask_to_latent")
+    F, Hp, Wp = mask_px.shape
+    if out is None:
+        out = torch.empty((F + 3) // 4, Hp // 8, Wp // 8, dtype=torch.uint8, device=mask_px.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != ((F + 3) // 4, Hp // 8, Wp // 8) or not out.is_contiguous():
+        raise ValueError(f"mask_to_latent: out must be contiguous uint8 [{(F + 3) // 4}, {Hp // 8}, {Wp // 8}], got {out.dtype} {tuple(out.shape)}")
+    check(_lib.load().ld_mask_to_latent(_ptr(mask_px), _ptr(out), F, Hp, Wp, _stream()), "ld_mask_to_latent")
+    return out
+
+
 def timestep_embedding(t, out, max_period=10000.0):
     B, dim = out.shape
     check(_lib.load().ld_timestep_embedding(_ptr(t), _ptr(out), B, dim, float(max_period), _stream()),

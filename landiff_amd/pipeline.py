@@ -14,7 +14,7 @@ from dataclasses import dataclass
 
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .config import AttnWindowConfig, PipelineConfig
 from .detokenizer import Detokenizer
 from .dit import ControlDiTRunner
@@ -90,6 +90,7 @@ class LanDiffPipeline:
         self.theia = theia
         self.timings = {}
         self.last_candidates = None       # generate_samples(keep=k): every candidate's ids and scores
+        self.last_edit = None             # edit_video: what the last call ran (strength, start_step, steps_run, ...)
 
     def _t(self, name, t0):
         torch.cuda.current_stream(self.dev).synchronize()      # (the stage's own stream: an overlapped AR decode keeps running)
@@ -497,6 +498,118 @@ class LanDiffPipeline:
         return (out, torch.cat(vids, dim=1)) if want_float else out
 
 
+    # ---- editing a given clip --------------------------------------------------------------------------
+    @torch.no_grad()
+    def edit_video(self, inp: PromptInputs, *, frames: torch.Tensor | None = None, clip_latent: torch.Tensor | None = None,
+                   strength: float = 1.0, keep_mask: torch.Tensor | None = None, tokens: torch.Tensor | None = None,
+                   clip_tokens: str | None = None, known_noise: bool = True, composite: bool = True,
+                   noise: torch.Tensor | None = None, want_float: bool = False, latents_out: list | None = None):
+        """Changes a given clip, training-free: an SDEdit start (`strength` < 1: the sampler begins at step start =
+        edit_start_step(num_steps, strength) from alpha[start] * clip latent + sigma[start] * noise and runs the remaining steps) and /
+        or masked inpainting (`keep_mask`: the marked cells are held on the clip's own trajectory, the rest is generated) -- the
+        sampler's start / known / known_mask arguments (DiffusionSampler.run) over one chunk.  DESIGN 8.8.
+
+        The clip (exactly one of the two): `frames` uint8 [4T-3, 8h, 8w, 3], exactly that shape (no resizing), encoded as extend_video
+        encodes its window (posterior sample on the device's generator seeded with inp.seed, rounded to bf16); or `clip_latent`
+        [1, T, 16, h, w], rounded to bf16 likewise.
+
+        Semantic tokens: `tokens` as given; clip_tokens="from_frames": the clip's own Theia tokens (needs frames= and theia=; timed
+        as "theia") -- the clip's layout and motion, re-rendered under the prompt; neither: generate_tokens(inp), from the prompt.
+
+        keep_mask: bool, True = keep the clip; [4T-3, 8h, 8w] in pixels (a latent cell is kept only if every pixel of its block is:
+        ld_mask_to_latent) or [T, h, w] in latent cells.  All True is refused (nothing left to edit), all False is no mask.
+        known_noise=False pins the kept cells to the clean clip latent at every step instead of its re-noised version.  With a pixel
+        mask, frames= and `composite`, the kept pixels of the returned uint8 frames are the clip's own (the fp32 video of want_float
+        is the decoder's output as it is).
+
+        The run is generate_latent's: seeds, semantic condition, the same initial-noise draw (or `noise`), the sampler, the decode;
+        strength 1.0 without a mask returns what self.decode(self.generate_latent(tokens, inp)) returns.  -> uint8 frames [4T-3, 8h,
+        8w, 3] (+ the fp32 video when want_float; with an even T the decoder leaves the last latent frame undecoded, as in
+        generation, and the composite covers the frames it returns).  latents_out receives the sampled latent (fp32 values of the bf16 result);
+        self.last_edit says what ran: strength, start_step, steps_run, alpha_start, sigma_start, kept_cells, total_cells,
+        tokens_source.  With dit_cache / dit_guidance the reports have steps_run rows whose index begins at start_step;
+        attn_window's dense_steps counts executed steps."""
+        d = self.cfg.dit
+        T, S = d.latent_frames, len(self.sampler.plan)
+        shape = (1, T, d.in_channels, d.latent_h, d.latent_w)
+        self.dit_cache_reports = []
+        self.dit_guidance_reports = []
+        if (frames is None) == (clip_latent is None):
+            raise ValueError("edit_video takes the clip as exactly one of frames and clip_latent")
+        if tokens is not None and clip_tokens is not None:
+            raise ValueError("edit_video: tokens already holds the clip's segment; clip_tokens='from_frames' computes it instead")
+        if clip_tokens is not None and clip_tokens != "from_frames":
+            raise ValueError(f"edit_video: clip_tokens must be None or 'from_frames', got {clip_tokens!r}")
+        if clip_tokens == "from_frames" and (frames is None or self.theia is None):
+            raise ValueError("edit_video(clip_tokens='from_frames') needs frames= and a pipeline built with theia=")
+        start = edit_start_step(S, strength)
+        if frames is not None:
+            frames = edit_clip(frames, self.cfg)
+            if self.encoder is None:
+                raise ValueError("edit_video(frames=...) needs the VAE encoder's weights ('encoder.*' in the VAE state)")
+        elif tuple(clip_latent.shape) != shape:
+            raise ValueError(f"clip_latent must be [1, {T}, {d.in_channels}, {d.latent_h}, {d.latent_w}], got {tuple(clip_latent.shape)}")
+        mask, mask_px = None, None
+        if keep_mask is not None:
+            px, lat = (4 * T - 3, 8 * d.latent_h, 8 * d.latent_w), (T, d.latent_h, d.latent_w)
+            if keep_mask.dtype != torch.bool or tuple(keep_mask.shape) not in (px, lat):
+                raise ValueError(f"keep_mask must be bool [{px[0]}, {px[1]}, {px[2]}] (pixels) or [{lat[0]}, {lat[1]}, {lat[2]}] "
+                                 f"(latent cells), got {keep_mask.dtype} {tuple(keep_mask.shape)}")
+            keep_mask = keep_mask.to(self.dev).contiguous()
+            if tuple(keep_mask.shape) == px:
+                mask_px = keep_mask
+                mask = ops.mask_to_latent(mask_px)
+            else:
+                mask = keep_mask.to(torch.uint8)
+            kept = int(mask.sum())
+            if kept == mask.numel():
+                raise ValueError("edit_video: keep_mask keeps every latent cell: nothing is left to edit")
+            if kept == 0:
+                mask = None
+        if clip_tokens == "from_frames":
+            t0 = time.perf_counter()
+            tokens = self.tokenize_frames(frames)
+            self._t("theia", t0)
+            source = "from_frames"
+        elif tokens is not None:
+            source = "given"
+        else:
+            t0 = time.perf_counter()
+            tokens = self.generate_tokens(inp)
+            self._t("llm", t0)
+            source = "prompt"
+        if frames is not None:
+            t0 = time.perf_counter()
+            torch.manual_seed(inp.seed); torch.cuda.manual_seed(inp.seed)
+            clip_latent = self.encoder.encode(frames.to(self.dev), sample=True)
+            self._t("vae_encode", t0)
+        if self.encoder is not None:
+            self.encoder.release()                        # its windows (13 GB at 480 x 720) are not needed by the DiT loop
+        z0 = clip_latent.to(self.dev).to(torch.bfloat16).float().contiguous()
+        torch.manual_seed(inp.seed)
+        torch.cuda.manual_seed(inp.seed)
+        t0 = time.perf_counter()
+        sem = self.detok.semantic_condition(tokens.to(self.dev))
+        self.dit.set_condition(inp.dit_context, sem)
+        self._t("detokenize", t0)
+        t0 = time.perf_counter()
+        noise = noise.to(self.dev) if noise is not None else torch.randn(*shape, device=self.dev, dtype=torch.float32)
+        z = self._sample(noise, start=start, known=z0, known_mask=mask, known_noise=known_noise)
+        self._t("dit", t0)
+        alpha, sigma = self.sampler.alphas[start]
+        self.last_edit = dict(strength=float(strength), start_step=start, steps_run=S - start, alpha_start=alpha, sigma_start=sigma,
+                              kept_cells=int(mask.sum()) if mask is not None else 0, total_cells=T * d.latent_h * d.latent_w,
+                              tokens_source=source)
+        if latents_out is not None:
+            latents_out.append(z.to(torch.bfloat16).float())
+        out = self.decode(z, want_float=want_float)
+        if composite and mask_px is not None and frames is not None:
+            edited = out[0] if want_float else out
+            n = edited.shape[0]           # (4T-3; an even T leaves its last latent frame undecoded, as in generation: VAEDecoder.decode)
+            edited = torch.where(mask_px[:n, :, :, None], frames[:n].to(self.dev), edited)      # uint8 select (plumbing)
+            out = (edited, out[1]) if want_float else edited
+        return out
+
     @torch.no_grad()
     def tokenize_frames(self, frames: torch.Tensor) -> torch.Tensor:
         """uint8 frames [F, H, W, 3] -> the clip's semantic token ids int64 [num_latent_tokens]: T = tok.temporal equally spaced
@@ -528,6 +641,41 @@ def write_scores_json(path: str, seeds, scores, kept) -> list:
     with open(path, "w") as f:
         json.dump(rows, f, indent=1)
     return rows
+
+
+def edit_start_step(S: int, strength: float) -> int:
+    """The sampler step LanDiffPipeline.edit_video starts at: of S steps the last n_run = floor(strength * S + 0.5) run, so
+    start = S - n_run (strength 1.0: 0, a fresh run).  strength must lie in (0, 1] and run at least one step."""
+    import math
+    strength = float(strength)
+    if not 0.0 < strength <= 1.0:
+        raise ValueError(f"edit strength must be in (0, 1], got {strength!r}")
+    n_run = math.floor(strength * S + 0.5)
+    if n_run < 1:
+        raise ValueError(f"edit strength {strength!r} runs no step of {S}: the smallest strength that runs one step is {0.5 / S!r}")
+    return S - n_run
+
+
+def edit_clip(frames, cfg: PipelineConfig):
+    """The clip LanDiffPipeline.edit_video takes: uint8 frames [4T-3, 8 latent_h, 8 latent_w, 3], exactly (T = cfg.dit.latent_frames:
+    49 frames of 480 x 720 in the shipped config).  Anything else raises ValueError with the expected shape; nothing is resized."""
+    d = cfg.dit
+    want = (4 * d.latent_frames - 3, 8 * d.latent_h, 8 * d.latent_w, 3)
+    if frames.dtype != torch.uint8 or tuple(frames.shape) != want:
+        raise ValueError(f"edit_video: clip frames must be uint8 [{want[0]}, {want[1]}, {want[2]}, 3], got {frames.dtype} "
+                         f"{tuple(frames.shape)} (one chunk, not resized)")
+    return frames
+
+
+def write_edit_json(path: str, last_edit: dict) -> dict:
+    """<name>_edit.json of infer_video --edit_video: LanDiffPipeline.last_edit (a float that is not finite is written as null: JSON
+    has no infinity)."""
+    import json
+    import math
+    row = {k: (None if isinstance(v, float) and not math.isfinite(v) else v) for k, v in last_edit.items()}
+    with open(path, "w") as f:
+        json.dump(row, f, indent=1, allow_nan=False)
+    return row
 
 
 def stream_plan(cfg: PipelineConfig, n_chunks: int, prefix_frames: int):

@@ -55,6 +55,21 @@ class StepPlan:
     has_prev: bool = False
 
 
+def step_alphas(cfg: SamplerConfig) -> list[tuple[float, float]]:
+    """(alpha[i], sigma[i]) for i = 0 .. num_steps: the signal and noise weights of the sampler's state on entry to step i, and,
+    at i = num_steps, of its result.  alpha[i] is build_plan's a[i] (fp32, zero-SNR: alpha[0] == 0.0, alpha[num_steps] == 1.0) and
+    sigma[i] = (1 - alpha[i]**2) ** 0.5 as fp32 torch scalars in that order -- the reference's re-noising of known frames,
+    `alpha_cumprod_sqrt[i] * prefix + randn * (1 - alpha_cumprod_sqrt[i]**2) ** 0.5` (sampling.py:800-817).  Python floats."""
+    a, _ = _zero_snr(_alphas_cumprod(cfg), cfg.num_steps, cfg.num_idx)
+    a = torch.cat([a, a.new_ones([1])])
+    one = torch.ones(1)
+    out = []
+    for i in range(cfg.num_steps + 1):
+        cur = one * a[i]
+        out.append((float(cur), float((1 - cur ** 2) ** 0.5)))
+    return out
+
+
 def build_plan(cfg: SamplerConfig) -> list[StepPlan]:
     ac = _alphas_cumprod(cfg)
     a, ts = _zero_snr(ac, cfg.num_steps, cfg.num_idx)
