@@ -539,7 +539,13 @@ int ld_llm_head_f32(const float* A, int64_t lda, const float* W, int64_t ldw, fl
 /* LayerNorm over D (fp32 statistics) with optional AdaLN modulate `x*(1+scale)+shift` (bf16 ops) whose vectors are
  * picked per row: batch = row / rows_per_batch, region = text if (row % rows_per_batch) < text_len else image;
  * vector = mod + batch*mod_bstride + {shift,scale}_{img,txt}.  (dit_video_concat.py:388,577-586,601-611;
- * also nn.LayerNorm in TiTok blocks.py:292-304 with fp32 in / bf16 out.) */
+ * also nn.LayerNorm in TiTok blocks.py:292-304 with fp32 in / bf16 out.)
+ * x is bf16, or f32 when x_f32; out likewise (out_f32); w, b, mod are bf16, w and b both given or both null.
+ * D % 8 == 0 and 0 < D <= 4096 (LD_ERR_INVALID otherwise).  NOT checked -- the rows are read and written in 16-byte pieces: x, out,
+ * w, b and every modulation vector 16-byte aligned, hence ldx, ldo multiples of 8 elements for bf16 and 4 for f32, and mod_bstride and
+ * the four offsets multiples of 8.  Columns [D, ldo) of out and rows >= `rows` are not written.
+ * With mod, bf16 x and out, affine weights and D <= 2048 a two-rows-per-wave kernel runs (LD_LN_FAST=0, read once per process: never);
+ * it stores the same bf16 values as the general kernel. */
 int ld_layernorm(const void* x, int64_t ldx, int32_t x_f32, const void* w, const void* b, void* out, int64_t ldo,
                  int32_t out_f32, int64_t rows, int64_t D, float eps, const void* mod, int64_t mod_bstride,
                  int64_t shift_img, int64_t scale_img, int64_t shift_txt, int64_t scale_txt,
@@ -548,7 +554,10 @@ int ld_layernorm(const void* x, int64_t ldx, int32_t x_f32, const void* w, const
 /* qkv [B*N][3*H*64] (thirds q|k|v, sat SelfAttention layout) -> Q,K [B][H][Npad][64] (zero padded) and
  * V^T [B][H][64][Npad].  mode 0: LayerNorm(64, eps) on q,k heads (dit_video_concat.py:649-653);
  * mode 1: interleaved-pair RoPE with cos/sin [N][32] (blocks.py:172-180, pos_emb.py:16-46);
- * mode 2: the plain split, no normalisation or rotation (HF ViTSelfAttention of the Theia backbone; no weights needed). */
+ * mode 2: the plain split, no normalisation or rotation (HF ViTSelfAttention of the Theia backbone; no weights needed).
+ * Npad % 64 == 0 and Npad >= N; mode 0 needs the four bf16 [64] weight vectors, mode 1 the two f32 tables (LD_ERR_INVALID
+ * otherwise).  Rows [N, Npad) of Q and K and columns [N, Npad) of V^T are written as zeros; nothing behind the three tensors is
+ * touched.  NOT checked: qkv, Q, K and Vt 16-byte aligned (the qkv row is 3*H*64 elements, so every row is). */
 int ld_qkv_split(const void* qkv, void* Q, void* K, void* Vt, int64_t B, int64_t N, int64_t H, int64_t Npad,
                  int32_t mode, const void* q_w, const void* q_b, const void* k_w, const void* k_b, float eps,
                  const float* cos_t, const float* sin_t, void* stream);
@@ -556,7 +565,9 @@ int ld_qkv_split(const void* qkv, void* Q, void* K, void* Vt, int64_t B, int64_t
 /* GroupNorm statistics of channels-last x [F][P][C] (torch.nn.GroupNorm inside Normalize, vq_gan_blocks.py:35-38, and
  * SpatialNorm3D, cp_enc_dec.py:546-569): stats[f][g] = (sum, sum of squares) in double.  No floating-point atomics:
  * partials is a caller-owned workspace of F * ld_groupnorm_stats_blocks(P) * G * 2 doubles, reduced in a fixed order, so
- * the result is bit-identical from run to run.  stats need not be zeroed. */
+ * the result is bit-identical from run to run.  stats need not be zeroed.
+ * C % 8 == 0, C <= 2048, G <= 64, C % G == 0 and C / G either a multiple of 8 or one of 2, 4 (LD_ERR_INVALID otherwise: a thread
+ * keeps four sub-group sums of its 8 channels, so one channel per group is not supported).  x 16-byte aligned (not checked). */
 int64_t ld_groupnorm_stats_blocks(int64_t P);
 int ld_groupnorm_stats(const void* x, double* stats, double* partials, int64_t F, int64_t P, int64_t C, int64_t G, void* stream);
 
@@ -585,11 +596,15 @@ int ld_patchify(const float* x, const void* sem, void* out, int64_t B, int64_t T
                 int64_t p, void* stream);
 
 /* unpatchify (:392-410) + Denoiser.forward `net*c_out + x*c_skip` (denoiser.py:25-41) + CFG `u + s*(c-u)`
- * (guiders.py:75-79): lin [2][T*hp*wp][C*p*p] bf16 (uncond, cond), x/out [T][C][H][W] f32. */
+ * (guiders.py:75-79): lin [2][T*hp*wp][C*p*p] bf16 (uncond, cond), x/out [T][C][H][W] f32.  fp32; xs = x*c_skip, u = e_u*c_out + xs,
+ * c = e_c*c_out + xs and D = c - u are rounded operation by operation as eager torch rounds them; out = fma(s, D, u), one rounding
+ * (eager torch rounds s*D first: that rounding, 2^-24 |s*D| at most, is all the two differ by before the last rounding). */
 int ld_unpatchify_cfg(const void* lin, const float* x, float* out, int64_t T, int64_t C, int64_t H, int64_t W,
                       int64_t p, float c_out, float c_skip, float scale, void* stream);
 
-/* out = a*x + b*y + c*z (y, z optional), products rounded separately, summed left to right (sampling.py:613-644,771-781). */
+/* out = a*x + b*y + c*z (y, z optional) of sampling.py:613-644,771-781, left to right as fma(c, z, fma(b, y, a*x)): a*x is rounded,
+ * b*y and c*z enter through one fused multiply-add each (eager torch rounds the products first: a rounding or two of the partial sums
+ * apart, bit-equal with x alone).  out may be x, y or z (an element is read before it is written, by the thread that writes it). */
 int ld_axpbypcz(float* out, const float* x, float a, const float* y, float b, const float* z, float c, int64_t n, void* stream);
 
 /* ---- clip editing (ld_edit.hip; LanDiffPipeline.edit_video) ----
@@ -611,7 +626,12 @@ int ld_timestep_embedding(const float* t, void* out, int64_t B, int64_t dim, flo
 
 /* Place a channels-last tensor in [F][Ti][Hi][Wi][Cin] into the interior of a zero-bordered buffer
  * [F][To+tpad][Ho+2*hpad][Wo+2*wpad][Cout].  mode 0 copy (+channel zero pad); mode 1 nearest x2 (time too when
- * time_up, first frame single for odd Ti: Upsample3D, cp_enc_dec.py:605-627); mode 2 PixelShuffle(2). */
+ * time_up, first frame single for odd Ti: Upsample3D, cp_enc_dec.py:605-627); mode 2 PixelShuffle(2).
+ * Only the interior is written (To x Ho x Wo positions, all Cout channels, behind tpad leading frames): the caller zeroes the
+ * border once.  Cout % 8 == 0; mode 0 Cin <= Cout (any Cin: channels [Cin, Cout) are written as zeros), mode 1 Cin == Cout,
+ * mode 2 Cin == 4*Cout (LD_ERR_INVALID otherwise).  NOT checked: out_padded 16-byte aligned; `in` 16-byte aligned with
+ * Cin % 8 == 0 in modes 0 (when Cin >= 8) and 1 -- whole 8-channel chunks are moved as one 16-byte word; a mode-0 tail chunk and
+ * mode 2 read element by element. */
 int ld_place_cl(const void* in, void* out_padded, int64_t F, int64_t Ti, int64_t Hi, int64_t Wi, int64_t Cin,
                 int64_t Cout, int32_t mode, int32_t time_up, int64_t tpad, int64_t hpad, int64_t wpad, void* stream);
 
@@ -713,11 +733,16 @@ int ld_vit_tail(const float* x, const float* ln_w, const float* ln_b, float eps,
 /* ---- T5 text encoders (HF transformers T5EncoderModel called from
  * landiff/llm/modules/text_encoder.py:36-42,82-112 and landiff/diffusion/sgm/modules/encoders/modules.py:249-292) ---- */
 
-/* T5LayerNorm (transformers modeling_t5.py): fp32 variance, bf16(x*rsqrt) then bf16(weight * that); bf16 weight. */
+/* T5LayerNorm (transformers modeling_t5.py): fp32 variance, bf16(x*rsqrt) then bf16(weight * that); bf16 weight.
+ * x and out are dense [rows][D] (row stride D, no leading dimension), D % 8 == 0, rows > 0 (LD_ERR_INVALID otherwise);
+ * x, w and out 16-byte aligned (not checked). */
 int ld_t5_rmsnorm(const void* x, const void* w, void* out, int64_t rows, int64_t D, float eps, void* stream);
 
 /* T5 self-attention, head_dim 64, N <= 512: q/k/v/out [N][ld] bf16 (head h at columns 64h..64h+63), no score scaling,
- * additive relative-position bias bias_table[bucket[j - i + N - 1]][h] (bf16 [num_buckets][H]), softmax in fp32. */
+ * additive relative-position bias bias_table[bucket[j - i + N - 1]][h] (bf16 [num_buckets][H]), softmax in fp32.
+ * bf16 rounding points: q.k, q.k + bias, the probabilities, the output; bucket is int32 [2N - 1].  0 < N <= 512, H > 0,
+ * ld >= 64*H and ld % 8 == 0 (LD_ERR_INVALID otherwise); q, k, v and out share ld (they may be column views of one fused
+ * [N][3*H*64] buffer) and q, k 16-byte aligned (not checked).  Only columns [0, 64*H) of the N rows of out are written. */
 int ld_t5_attn(const void* q, const void* k, const void* v, void* out, int64_t ld, const void* bias_table,
                const int32_t* bucket, int64_t N, int64_t H, void* stream);
 

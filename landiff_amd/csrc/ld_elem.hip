@@ -34,7 +34,14 @@ __global__ void ld_patchify_kernel(const float* x, const bf16_t* sem, bf16_t* ou
 }
 
 // lin [2][T*hp*wp][C*p*p] bf16 (rows 0: uncond, 1: cond), x [1][T][C][H][W] f32
-//   den_b = lin_b * c_out + x * c_skip ; out = den_u + scale * (den_c - den_u)           (fp32, unfused ops)
+//   den_b = lin_b * c_out + x * c_skip ; D = den_c - den_u ; out = fma(scale, D, den_u)                     (fp32)
+// Every product, sum and difference up to D is rounded on its own, as eager torch rounds them; the last step is ONE fused
+// multiply-add (a single rounding of scale * D + den_u).  That is what this kernel has always compiled to under hipcc's default
+// contraction, where __fmul_rn / __fadd_rn are a plain `*` / `+` that the compiler may fuse (stating only the last fma with the
+// rest left to it made it fuse den_b as well).  Now the fma is stated and `#pragma clang fp contract(off)` keeps every other
+// operation of the loop body apart, so the bits no longer hang on the compiler's choice; the instructions are the ones it emitted
+// before.  ld_unpatchify_cfg_keep (ld_dit_guidance.hip) states the same fma.  Against the unfused `den_u + scale * D` of
+// guiders.py:75-79 the result differs by the product's rounding, 2^-24 |scale * D| at most (tests/test_gpu_elem_kernels.py checks both).
 __global__ void ld_unpatchify_cfg_kernel(const bf16_t* lin, const float* x, float* out, int T, int C, int H, int W, int p,
                                          float c_out, float c_skip, float scale) {
   const int hp = H / p, wp = W / p, K = C * p * p;
@@ -49,19 +56,28 @@ __global__ void ld_unpatchify_cfg_kernel(const bf16_t* lin, const float* x, floa
     const long row = ((long)t * hp + hh / p) * wp + ww / p;
     const int k = c * p * p + (hh % p) * p + (ww % p);
     const float eu = bf2f(lin[row * K + k]), ec = bf2f(lin[(n_img + row) * K + k]);
-    const float xs = __fmul_rn(x[i], c_skip);
-    const float du = __fadd_rn(__fmul_rn(eu, c_out), xs);
-    const float dc = __fadd_rn(__fmul_rn(ec, c_out), xs);
-    out[i] = __fadd_rn(du, __fmul_rn(scale, __fsub_rn(dc, du)));
+    {
+#pragma clang fp contract(off)
+      const float xs = x[i] * c_skip;
+      const float pu = eu * c_out, pc = ec * c_out;
+      const float du = pu + xs, dc = pc + xs;
+      const float dl = dc - du;
+      out[i] = __builtin_fmaf(scale, dl, du);
+    }
   }
 }
 
-// out = a*x + b*y + c*z evaluated left to right with separately rounded products (matches eager torch)
+// out = fma(c, z, fma(b, y, a*x)), left to right: a*x is rounded, every further term enters through ONE fused multiply-add (its
+// product is not rounded on its own).  As with ld_unpatchify_cfg_kernel this is what the `__fadd_rn(v, __fmul_rn(..))` spelling
+// always compiled to (two v_fmac_f32); it is now stated.  Eager torch's `a*x + b*y + c*z` (sampling.py:613-644) rounds each product:
+// the two differ by a rounding of each fused product (and what that moves in the partial sums' own roundings), and not at all in the
+// x-only form.
 __global__ void ld_axpbypcz_kernel(float* out, const float* x, float a, const float* y, float b, const float* z, float c, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    float v = __fmul_rn(a, x[i]);
-    if (y) v = __fadd_rn(v, __fmul_rn(b, y[i]));
-    if (z) v = __fadd_rn(v, __fmul_rn(c, z[i]));
+#pragma clang fp contract(off)
+    float v = a * x[i];
+    if (y) v = __builtin_fmaf(b, y[i], v);
+    if (z) v = __builtin_fmaf(c, z[i], v);
     out[i] = v;
   }
 }

@@ -550,7 +550,8 @@ __global__ __launch_bounds__(256) void ld_qkv_split_kernel(SplitParams p) {
 // GroupNorm statistics over a channels-last tensor x [F][P][C]: per (frame-group f, group g) sum and sum of
 // squares in double.  No floating-point atomics anywhere: every workgroup writes its partial pair to
 // partials [F][nblk][G][2] and ld_gn_stats_reduce_kernel sums them in a fixed order, so the statistics -- and with them the
-// whole VAE / upsampler decode -- are bit-identical from run to run.
+// whole VAE / upsampler decode -- are bit-identical from run to run.  Channels per group: a multiple of 8 (whole chunks per group),
+// or 2 or 4 (4 or 2 groups inside a thread's 8-channel chunk, one slot each of its four); anything else is refused.
 // ---------------------------------------------------------------------------------------------
 constexpr int GN_ROWS_PER_BLOCK = 512;
 constexpr int LD_GN_FOLD_BLOCKS = 256;          // ld_groupnorm_stats_from_conv: workgroups of the fold = double pairs per group in `partials`
@@ -568,7 +569,7 @@ __global__ __launch_bounds__(256) void ld_gn_stats_kernel(const bf16_t* x, doubl
   const int chunk = tid % chunks_per_row;
   const int rlane = tid / chunks_per_row;
   const int rstep = 256 / chunks_per_row;
-  const int nsub = cpg >= 8 ? 1 : 8 / cpg;       // groups inside one 8-channel chunk (cpg in {2,4} -> 4, 2)
+  const int nsub = cpg >= 8 ? 1 : 8 / cpg;       // groups inside one 8-channel chunk (cpg in {2,4} -> 4, 2; cpg 1 would need 8 slots: refused)
   float gs[4] = {0.f, 0.f, 0.f, 0.f}, gss[4] = {0.f, 0.f, 0.f, 0.f};
   if (rlane < rstep) {
     // Round 5: GN_U rows are requested before the first is consumed (the loop used to hold ONE 16-byte load in flight per thread:
@@ -880,7 +881,8 @@ LD_API int ld_groupnorm_stats(const void* x, double* stats, double* partials, in
   LD_REQUIRE(x && stats && partials, "ld_groupnorm_stats: null pointer");
   LD_REQUIRE(C % 8 == 0 && C / 8 <= 256 && G <= 64 && C % G == 0, "ld_groupnorm_stats: unsupported C=%ld G=%ld", (long)C, (long)G);
   const int cpg = (int)(C / G);
-  LD_REQUIRE(cpg % 8 == 0 || 8 % cpg == 0, "ld_groupnorm_stats: channels per group %d unsupported", cpg);
+  // (cpg == 1 is 8 groups per 16-byte chunk, and a thread keeps four sub-group slots: `8 % cpg == 0` used to let it through to aliased sums)
+  LD_REQUIRE(cpg % 8 == 0 || cpg == 2 || cpg == 4, "ld_groupnorm_stats: channels per group %d unsupported (a multiple of 8, or 2 or 4)", cpg);
   const int rows_per_block = GN_ROWS_PER_BLOCK;
   const int nblk = (int)ld_groupnorm_stats_blocks(P);
   dim3 grid((unsigned)nblk, (unsigned)F), block(256);
