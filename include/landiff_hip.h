@@ -33,8 +33,8 @@ extern "C" {
  * ld_llm_sample_advance_pairs were added.  15: ld_llm_token_logprobs and ld_llm_head_f32 were added;
  * ld_gemv_wide, ld_llm_decode_forward_wide and ld_llm_sample_advance_wide joined later, and so did ld_absdiff_sums,
  * ld_residual_sub, ld_residual_add, ld_attn_fwd_bf16_window, ld_attn_window_plan, ld_unpatchify_cfg_keep, ld_unpatchify_cond, ld_latent_pin and ld_mask_to_latent (additions do not change
- * the number: no existing signature moved). */
-#define LD_ABI_VERSION 15
+ * the number: no existing signature moved).  16: ld_attn_route was added. */
+#define LD_ABI_VERSION 16
 
 int ld_version(void);
 const char* ld_last_error(void);
@@ -100,7 +100,8 @@ int ld_gemm_qkv_heads(const void* A, int64_t lda, const void* W, const void* bia
  * else: other activations, mul, fp32 residual or output, N or a leading dimension not a multiple of 8).  The fused qkv split
  * (ld_gemm_qkv_heads, epilogue 5) takes the route of ld_gemm_route(M, 3 * heads * 64, K, ...).  As for convolutions, the routes
  * give bit-identical outputs: the 8-phase rounds, the half-tile tail and the row tail equal 256-row slices of the same GEMM run on
- * the 128x128 route, bit for bit (measured at the DiT's shapes, tests/test_gpu_gemm_routes.py).  Host logic only. */
+ * the 128x128 route, bit for bit (measured at the DiT's shapes, tests/test_gpu_gemm_routes.py).  Host logic only.  (The same
+ * query for attention: ld_attn_route, with the attention entry points below.) */
 int ld_gemm_route(int64_t M, int64_t N, int64_t K, int64_t ldo, const ld_epilogue_t* epi, int32_t* epilogue_kind);
 
 /* Channels-last implicit-GEMM convolution, stride 1.
@@ -250,6 +251,23 @@ int ld_attn_fwd_bf16_window(const void* Q, const void* K, const void* Vt, void* 
  * bad arguments or a block outside [0, ceil(N / 256)); shapes ld_attn_fwd_bf16_window would refuse as unsupported still plan. */
 int ld_attn_window_plan(int64_t N, int64_t prefix, int64_t group, int64_t window, int64_t block,
                         int32_t* t_lo, int32_t* t_hi, int32_t* n_eff);
+
+/* Which kernel family an attention launch of these shapes runs, without launching anything (no GPU needed, no HIP call): the
+ * launch's own plan run dry, under the same LD_ATTN_* knobs.  form: 0 = ld_attn_fwd_bf16, 1 = ld_attn_fwd_bf16_exact,
+ * 2 = ld_attn_fwd_bf16_window (Nq = Nk = N, masked = 0); masked != 0: a label mask is given.  Returns
+ *   0 = the plain online-softmax kernel (ld_attn_kernel: masked problems and problems of fewer than 6 key tiles, in both of the
+ *       first two forms; every problem under LD_ATTN_VARIANT=9, 1 or 4),
+ *   1 = the 64-row wave tile (ld_attn_q64_kernel, or ld_attn_q64_dyn_kernel where the launcher can go dynamic: that depends on the
+ *       device, the stream and graph capture, which this query does not see),
+ *   2 = its two-pass exact form (ld_attn_q64_exact_kernel),  3 = its frame-window form (ld_attn_q64_win_kernel / _win_dyn_kernel),
+ *   4 = the 32-row wave tile (ld_attn_p16_*_kernel: LD_ATTN_Q64=0),
+ *   5 = the 128-row tile (ld_attn_q128_*kernel) and 6 = the round-1 pipeline (ld_attn_pipe2_*_kernel): VARIANTS build only, under
+ *       LD_ATTN_Q128 / LD_ATTN_VARIANT=8,
+ * negative = refused, with the message the launch would give for the shape (empty problem, Npad not a multiple of 128 or below
+ * Nq / Nk; form 2: fewer than 6 key tiles, a mask or Nq != Nk).  For form 2 it answers from the sequence alone: whether every query
+ * block's own tile list is long enough is ld_attn_window_plan's business.  After a launch, ld_attn_last_kernel names a kernel of the
+ * family reported here (tests/test_gpu_attn.py). */
+int ld_attn_route(int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t Npad, int32_t masked, int32_t form);
 
 /* Forgets the stream -> counter-set assignments of the current device and zeroes its sets (asynchronously on `stream`).
  * Only for a process that keeps creating streams, or after a device error: the caller guarantees that no ld_attn_fwd_bf16

@@ -44,7 +44,7 @@ class LlmLayer(Structure):
 
 
 _lib = None
-ABI_VERSION = 15         # LD_ABI_VERSION of include/landiff_hip.h that SIGNATURES below were written against
+ABI_VERSION = 16         # LD_ABI_VERSION of include/landiff_hip.h that SIGNATURES below were written against
 
 I64 = c_int64
 I32 = c_int32
@@ -73,6 +73,7 @@ SIGNATURES: dict[str, list] = {
     "ld_attn_fwd_bf16_exact": _ATTN_FWD,
     "ld_attn_fwd_bf16_window": [P, P, P, P, I64, I64, I64, I64, I64, I64, c_float, I64, I64, I64, P],
     "ld_attn_window_plan": [I64, I64, I64, I64, I64, POINTER(I32), POINTER(I32), POINTER(I32)],
+    "ld_attn_route": [I64, I64, I64, I64, I64, I32, I32],
     "ld_attn_last_kernel": [],
     "ld_attn_last_fallbacks": [P, P],
     "ld_reset": [P],

@@ -1,8 +1,12 @@
-// Shared declarations of the gfx950 attention kernels (ld_attn.hip, ld_attn_pipe.hip).
+// Shared declarations of the gfx950 attention family.  ld_attn.hip: the plain online-softmax kernel, the plan (which kernel a
+// problem gets, every LD_ATTN_* knob), the executor and the entry points.  The pipelined kernels and their launchers:
+// ld_attn_q64.hip (64-row wave tile: dense, frame-window and dynamic forms; shared body ld_attn_q64_body.h), ld_attn_q64_exact.hip
+// (two-pass exact softmax), ld_attn_p16.hip (32-row wave tile) and, in the variants build only, ld_attn_pipe.hip (round-1 pipeline)
+// and ld_attn_q128.hip (128-row tile).  A launcher takes its knob values as arguments -- it reads no environment -- and reports
+// what it launched through an AttnRan; attn_run (ld_attn.hip) is the one writer of what ld_attn_last_kernel / _fallbacks answer.
 #pragma once
 #include "ld_common.h"
 #include "../../include/landiff_hip.h"
-#include <stdlib.h>
 #include <type_traits>
 
 struct AttnParams {
@@ -19,11 +23,33 @@ struct AttnParams {
   const int* kt_max;
 };
 
+// What a launcher launched.  name: the kernel, as ld_attn_last_kernel reports it.  Where the launch counts the query blocks that left
+// the fast pass's window (ld_attn_last_fallbacks): fb_kind 0 = the kernel has no such window (running-max or two-pass softmax:
+// nothing to count), 1 = counted at fb_src (device address, valid until the next launch on that stream), 2 = a max-free fast pass
+// that keeps no count (static dispatch, 32-row tile).  Left untouched by a launcher that fails before its launch.
+struct AttnRan {
+  const char* name;
+  const unsigned* fb_src;
+  int fb_kind;
+};
+
+// The launchers.  safe != 0 forces the running-max pass; the other arguments are the knobs of the table at attn_plan.
+// q64: win = null for the dense kernels, else {prefix, group, frames} of the frame-window form (validated by
+// ld_attn_fwd_bf16_window); want_dyn asks for the dynamic form, which the launcher grants by device, grid, stream and capture.
+int ld_attn_q64_launch(const AttnParams& p, hipStream_t st, const int* win, int safe, bool want_dyn, AttnRan* ran);
+int ld_attn_q64_exact_launch(const AttnParams& p, hipStream_t st, AttnRan* ran);
+int ld_attn_p16_launch(const AttnParams& p, hipStream_t st, int safe, int msum, int nw, AttnRan* ran);
+#ifdef LD_VARIANTS   // measured alternatives, only in the variants build (build.sh: LD_BUILD_VARIANTS=1)
+int ld_attn_pipe2_launch(const AttnParams& p, hipStream_t st, int safe, int nw, AttnRan* ran);
+int ld_attn_q128_launch(const AttnParams& p, hipStream_t st, int safe, int npre, AttnRan* ran);
+#endif
+
 namespace {
 
 constexpr int QB = 128;   // query rows per workgroup
 constexpr int KT = 64;    // keys per tile
 constexpr int D = 64;
+constexpr int ATTN_PIPELINED_MIN_TILES = 6;   // unmasked problems of at least this many key tiles take the pipelined kernels, whose loops count on it
 constexpr int KTILE_BYTES = KT * D * 2;       // 8 KB
 constexpr int STAGE_BYTES = 2 * KTILE_BYTES;  // K + V^T
 constexpr float NEG_BIG = -1.0e30f;

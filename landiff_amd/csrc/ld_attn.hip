@@ -34,17 +34,15 @@
 
 namespace {
 
-template <int TPS, bool DEFER, bool PRIO, bool MFMASUM, int WPS>   // WPS = waves/SIMD of the register budget
+template <bool MFMASUM, int WPS>   // WPS = waves/SIMD of the register budget
 __global__ __launch_bounds__(256, WPS) void ld_attn_kernel(AttnParams p) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 stages x TPS x (K 8 KB + V^T 8 KB) + 64 B
-  constexpr int STAGE = TPS * STAGE_BYTES;
+  extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 stages of one key tile (K 8 KB + V^T 8 KB) + 64 B
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hi = lane >> 5;
   const int nqb = p.Npad / QB;
   const int nkt_all = (p.Nk + KT - 1) / KT;
-  const int nst_all = (nkt_all + TPS - 1) / TPS;
 
   const int bid = xcd_remap(blockIdx.x, gridDim.x);
   const int bh = bid / nqb, qb = bid - bh * nqb;
@@ -70,7 +68,7 @@ __global__ __launch_bounds__(256, WPS) void ld_attn_kernel(AttnParams p) {
       mx = max(mx, __shfl_xor(mx, o, 64));
     }
     wqmin = mn; wqmax = mx;
-    int* red = (int*)(smem + 2 * STAGE);
+    int* red = (int*)(smem + 2 * STAGE_BYTES);
     if (lane == 0) red[wave] = mx;
     __syncthreads();
     bqmax = max(max(red[0], red[1]), max(red[2], red[3]));
@@ -104,36 +102,24 @@ __global__ __launch_bounds__(256, WPS) void ld_attn_kernel(AttnParams p) {
     else goff[i] = (long)r * p.Npad + chunk * 8;             // + kv0
     ldsoff[i] = (idx < 8 ? 0 : KTILE_BYTES) + (idx & 7) * 1024;
   }
-  auto stage = [&](int buf, int st) {
-    char* base = smem + buf * STAGE;
+  auto stage = [&](int buf, int t) {            // a stage is one key tile
+    char* base = smem + buf * STAGE_BYTES;
+    const long kv0 = (long)t * KT;
 #pragma unroll
-    for (int j = 0; j < TPS; ++j) {
-      const int t = st * TPS + j;
-      if (t < nkt_all) {
-        const long kv0 = (long)t * KT;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int idx = wave * 4 + i;
-          const bf16_t* src = (idx < 8) ? (Kb + kv0 * D + goff[i]) : (Vb + kv0 + goff[i]);
-          glds16(src, base + j * STAGE_BYTES + ldsoff[i]);
-        }
-      }
+    for (int i = 0; i < 4; ++i) {
+      const int idx = wave * 4 + i;
+      const bf16_t* src = (idx < 8) ? (Kb + kv0 * D + goff[i]) : (Vb + kv0 + goff[i]);
+      glds16(src, base + ldsoff[i]);
     }
   };
-  auto stage_needed = [&](int st) {
+  auto tile_needed = [&](int t) {               // can some query of the workgroup see a key of tile t?
     if (!masked) return true;
-    bool need = false;
-#pragma unroll
-    for (int j = 0; j < TPS; ++j) {
-      const int t = st * TPS + j;
-      if (t < nkt_all && p.kt_min[t] <= bqmax) need = true;
-    }
-    return need;
+    return t < nkt_all && p.kt_min[t] <= bqmax;   // (the bound is the caller's too: stated twice, as the instruction stream was tuned)
   };
-  auto next_stage = [&](int st) {
-    ++st;
-    while (st < nst_all && !stage_needed(st)) ++st;
-    return st;
+  auto next_tile = [&](int t) {
+    ++t;
+    while (t < nkt_all && !tile_needed(t)) ++t;
+    return t;
   };
 
   // fragment read byte offsets within a 64-key tile, one per (row block i, k-step): loop invariant, so the
@@ -166,10 +152,10 @@ __global__ __launch_bounds__(256, WPS) void ld_attn_kernel(AttnParams p) {
   for (int r = 0; r < 16; ++r) lacc[r] = 0.f;
   const bf16x8_t ones = {0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80, 0x3f80};
   bool unset = true;                 // no valid key seen yet for this query
-  constexpr float THR = 8.0f;
+  constexpr float THR = 8.0f;        // deferred rescale: P may grow to 2^THR before the running max is rebased
 
-  auto tile = [&](auto bufc, auto jc, int t) {
-    constexpr int OFF = decltype(bufc)::value * STAGE + decltype(jc)::value * STAGE_BYTES;
+  auto tile = [&](auto bufc, int t) {
+    constexpr int OFF = decltype(bufc)::value * STAGE_BYTES;
     bool skip = false, need_mask = false;
     if (masked) {
       const int tmin = p.kt_min[t], tmax = p.kt_max[t];
@@ -209,14 +195,12 @@ __global__ __launch_bounds__(256, WPS) void ld_attn_kernel(AttnParams p) {
     for (int kk = 0; kk < 4; ++kk)
 #pragma unroll
       for (int i = 0; i < 2; ++i) kf[i][kk] = *(const bf16x8_t*)(smem + kofs[kk] + OFF + i * 4096);
-    if (PRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
 #pragma unroll
       for (int i = 0; i < 2; ++i)
         sacc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[i][kk], qf[kk], kk == 0 ? negm : sacc[i], 0, 0, 0);
     }
-    if (PRIO) __builtin_amdgcn_s_setprio(0);
     }
     // V^T fragments for the PV product: requested now so their LDS latency hides under the softmax VALU work
     bf16x8_t vf[2][4];
@@ -260,7 +244,7 @@ __global__ __launch_bounds__(256, WPS) void ld_attn_kernel(AttnParams p) {
     mx = fmaxf(mx, sacc[1][15]);
     mx = lane32_max(mx);            // = max_k(S') - m_old for this query (S' in log2 units)
     const bool valid = mx > -1.0e29f;                       // at least one unmasked key in this tile
-    if (!__all(!(valid && (unset || mx > (DEFER ? THR : 0.0f))))) {
+    if (!__all(!(valid && (unset || mx > THR)))) {
       // rare: (re)base the running max.  d = how much m grows for this lane; everything held at the old max scales by 2^-d
       const float d = valid ? (unset ? mx : fmaxf(mx, 0.0f)) : 0.0f;
       unset = unset && !valid;
@@ -288,7 +272,6 @@ __global__ __launch_bounds__(256, WPS) void ld_attn_kernel(AttnParams p) {
       }
     lsum += psum;
     // ---- O^T += V^T P^T ----
-    if (PRIO) __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       u32x4_t pw;
@@ -303,29 +286,27 @@ __global__ __launch_bounds__(256, WPS) void ld_attn_kernel(AttnParams p) {
       }
       if (MFMASUM) lacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ones, pb, lacc, 0, 0, 0);
     }
-    if (PRIO) __builtin_amdgcn_s_setprio(0);
   };
-  auto stage_tiles = [&](auto bufc, int st) {
-    tile(bufc, std::integral_constant<int, 0>{}, st * TPS);
-    if (TPS > 1 && st * TPS + 1 < nkt_all) tile(bufc, std::integral_constant<int, TPS - 1>{}, st * TPS + 1);
-  };
+  // (a forwarding level kept on purpose: with tile() called from the loop directly hipcc allocates the registers of all three
+  //  instantiations differently, and this kernel's instruction stream is what was measured)
+  auto stage_tile = [&](auto bufc, int t) { tile(bufc, t); };
 
-  // two stages per trip with compile-time buffer indices; the second half sits under an `if`, not behind a `break`
+  // two tiles per trip with compile-time buffer indices; the second half sits under an `if`, not behind a `break`
   // (a mid-loop exit makes hipcc keep two copies of the O accumulators and shuffle them every trip)
-  int st = next_stage(-1);
-  if (st < nst_all) stage(0, st);
-  while (st < nst_all) {
-    int stn = next_stage(st);
+  int t = next_tile(-1);
+  if (t < nkt_all) stage(0, t);
+  while (t < nkt_all) {
+    int tn = next_tile(t);
     __syncthreads();
-    if (stn < nst_all) stage(1, stn);
-    stage_tiles(std::integral_constant<int, 0>{}, st);
-    st = stn;
-    if (st < nst_all) {
-      stn = next_stage(st);
+    if (tn < nkt_all) stage(1, tn);
+    stage_tile(std::integral_constant<int, 0>{}, t);
+    t = tn;
+    if (t < nkt_all) {
+      tn = next_tile(t);
       __syncthreads();
-      if (stn < nst_all) stage(0, stn);
-      stage_tiles(std::integral_constant<int, 1>{}, st);
-      st = stn;
+      if (tn < nkt_all) stage(0, tn);
+      stage_tile(std::integral_constant<int, 1>{}, t);
+      t = tn;
     }
   }
 
@@ -349,99 +330,148 @@ __global__ __launch_bounds__(256, WPS) void ld_attn_kernel(AttnParams p) {
 
 }  // namespace
 
-int ld_attn_p16_launch(const AttnParams& p, hipStream_t st);     // ld_attn_p16.hip
-int ld_attn_q64_launch(const AttnParams& p, hipStream_t st);     // ld_attn_q64.hip
-int ld_attn_q64_launch_any(const AttnParams& p, hipStream_t st, const int* win);   // ld_attn_q64.hip: win = {prefix, group, frames}
-#ifdef LD_VARIANTS   // measured alternatives, only in the variants build (build.sh: LD_BUILD_VARIANTS=1)
-int ld_attn_pipe2_launch(const AttnParams& p, hipStream_t st);   // ld_attn_pipe.hip
-int ld_attn_q128_launch(const AttnParams& p, hipStream_t st);    // ld_attn_q128.hip
-#endif
+// ---- what the calling thread's last launch ran: written by attn_run alone ----
+static thread_local AttnRan g_attn_ran = {"", nullptr, 0};
 
 // name of the kernel the calling thread's last ld_attn_fwd_bf16 launched (bench.py labels its roofline object with it)
-static thread_local const char* g_attn_last_kernel = "";
-void ld_attn_set_last_kernel(const char* name) { g_attn_last_kernel = name; }
-LD_API const char* ld_attn_last_kernel(void) { return g_attn_last_kernel; }
-
-int ld_attn_q64_exact_launch(const AttnParams& p, hipStream_t st);   // ld_attn_q64_exact.hip
-
-// Where the calling thread's last launch counts the query blocks that left the fast pass's window (ld_attn_last_fallbacks):
-// kind 0 = the kernel has no such window (running-max or two-pass softmax: nothing to count), 1 = counted at `src` (device address,
-// valid until the next launch on that stream), 2 = a max-free fast pass that keeps no count (static dispatch, 32-row tile).
-static thread_local const unsigned* g_attn_fb_src = nullptr;
-static thread_local int g_attn_fb_kind = 0;
-void ld_attn_set_fallback_source(const unsigned* src, int kind) { g_attn_fb_src = src; g_attn_fb_kind = kind; }
+LD_API const char* ld_attn_last_kernel(void) { return g_attn_ran.name; }
 
 LD_API int ld_attn_last_fallbacks(int32_t* out, void* stream) {
   LD_REQUIRE(out, "ld_attn_last_fallbacks: null pointer");
   hipStream_t st = (hipStream_t)stream;
   hipError_t e;
-  if (g_attn_fb_kind == 1) e = hipMemcpyAsync(out, g_attn_fb_src, 4, hipMemcpyDeviceToDevice, st);
-  else e = hipMemsetAsync(out, g_attn_fb_kind == 2 ? 0xFF : 0, 4, st);
+  if (g_attn_ran.fb_kind == 1) e = hipMemcpyAsync(out, g_attn_ran.fb_src, 4, hipMemcpyDeviceToDevice, st);
+  else e = hipMemsetAsync(out, g_attn_ran.fb_kind == 2 ? 0xFF : 0, 4, st);
   if (e != hipSuccess) return ld_set_error(LD_ERR_LAUNCH, "ld_attn_last_fallbacks: %s", hipGetErrorString(e));
   return LD_OK;
 }
 
-static int attn_fwd_impl(const void* Q, const void* K, const void* Vt, void* O,
-                         int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t Npad,
-                         int64_t o_batch_stride, int64_t o_row_stride, float softmax_scale,
-                         const int32_t* fid_q, const int32_t* fid_k,
-                         const int32_t* kt_min, const int32_t* kt_max, void* stream, bool exact) {
-  LD_REQUIRE(Q && K && Vt && O, "ld_attn_fwd_bf16: null pointer");
-  LD_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0, "ld_attn_fwd_bf16: empty problem");
-  LD_REQUIRE(Npad % QB == 0 && Npad >= Nq && Npad >= Nk, "ld_attn_fwd_bf16: Npad=%ld must be a multiple of %d and >= Nq,Nk", (long)Npad, QB);
-  LD_REQUIRE((fid_q == nullptr) == (fid_k == nullptr), "ld_attn_fwd_bf16: fid_q and fid_k go together");
-  LD_REQUIRE(!fid_k || (kt_min && kt_max), "ld_attn_fwd_bf16: masked attention needs kt_min/kt_max");
-  LD_REQUIRE(o_row_stride % 4 == 0 && ((uintptr_t)O & 7) == 0, "ld_attn_fwd_bf16: output alignment");
+// ---- the plan: which kernel a problem gets.  Shapes and knobs only, never the HIP runtime (ld_attn_route runs it dry). ----
+enum { ATTN_PLAIN = 0, ATTN_Q64 = 1, ATTN_Q64_EXACT = 2, ATTN_Q64_WIN = 3, ATTN_P16 = 4, ATTN_Q128 = 5, ATTN_PIPE2 = 6 };   // (ld_attn_route, landiff_hip.h)
+enum AttnForm { FORM_DEFAULT = 0, FORM_EXACT = 1, FORM_WINDOW = 2 };       // ld_attn_fwd_bf16 / _exact / _window
+
+struct AttnPlan {
+  int route = ATTN_PLAIN;               // < 0: an error code, message set, nothing to launch
+  int safe = 0, msum = 1, nw = 4, npre = 44, variant = 0;
+  bool want_dyn = false;
+  int win[3] = {0, 0, 0};               // ATTN_Q64_WIN: {prefix, group, frames}
+};
+
+static int attn_window_too_short(int64_t nkt) {
+  return ld_set_error(LD_ERR_UNSUPPORTED, "ld_attn_fwd_bf16_window: %ld key tiles; the pipelined kernel needs at least %d", (long)nkt,
+                      ATTN_PIPELINED_MIN_TILES);
+}
+
+// The LD_ATTN_* knobs, all read here and through ld_knob (once per process, or per call under LD_TUNING=1: ld_common.h):
+//   LD_ATTN_VARIANT  0  0 = the pipelined 16x16x32 kernels below for every unmasked problem of >= ATTN_PIPELINED_MIN_TILES key tiles,
+//                       else the plain kernel; 9 = the plain kernel everywhere; 1 / 4 = the plain kernel with row sums on the matrix
+//                       pipe / in its lean-register 4-waves form; 8 = the round-1 pipelined 32x32x16 kernel of ld_attn_pipe.hip for
+//                       tile counts 4 m + 2 (variants build only: the shipped library runs the plain kernel)
+//   LD_ATTN_Q64      1  0 = the 32-query-row wave tile of ld_attn_p16.hip instead of the 64-row one of ld_attn_q64.hip
+//   LD_ATTN_Q128     0  (variants build only) 1 = the 128-row, one-wave-per-SIMD tile of ld_attn_q128.hip for problems with enough
+//                       query rows to fill the chip with its 512-row workgroups; 2 = for every pipelined problem
+//   LD_ATTN_SAFE     0  1 = the pipelined kernels run their running-max pass (testing, A/B timing)
+//   LD_ATTN_DYN      1  0 = q64: the hardware's round-robin dispatch of one workgroup per query block, not the dynamic form (which
+//                       the launcher takes for grids of at least four rounds of the chip's slots when the stream allows it)
+//   LD_ATTN_MSUM     1  0 = p16: the row sums by v_add_f32, not on the matrix pipe (A/B timing)
+//   LD_ATTN_NW       4  8 = p16 / pipe2: 8-wave workgroups (halve the K/V traffic per CU, measure the same: 4.44 vs 4.46 ms)
+//   LD_ATTN_NPRE    44  q128: 36 | 52 the other exp2 splits, 1036 | 1040 with the packs under the PV phase (A/B timing)
+// The exact form is decided before LD_ATTN_VARIANT / LD_ATTN_Q64, and the window form goes to the q64 window kernels whatever
+// they say: there is no other kernel for either.
+static AttnPlan attn_plan(const AttnParams& p, AttnForm form, const int* win) {
+  static int k_var = LD_KNOB_UNSET, k_q64 = LD_KNOB_UNSET, k_safe = LD_KNOB_UNSET, k_dyn = LD_KNOB_UNSET, k_msum = LD_KNOB_UNSET,
+             k_nw = LD_KNOB_UNSET;
+  AttnPlan pl;
+  pl.variant = ld_knob("LD_ATTN_VARIANT", 0, &k_var);
+  pl.safe = ld_knob("LD_ATTN_SAFE", 0, &k_safe);
+  pl.want_dyn = ld_knob("LD_ATTN_DYN", 1, &k_dyn) > 0 && !pl.safe;
+  pl.msum = ld_knob("LD_ATTN_MSUM", 1, &k_msum);
+  pl.nw = ld_knob("LD_ATTN_NW", 4, &k_nw) == 8 ? 8 : 4;      // (anything but 8 is 4)
+  const bool q64 = ld_knob("LD_ATTN_Q64", 1, &k_q64) != 0;
+  const int64_t nkt = ((int64_t)p.Nk + KT - 1) / KT;
+  const bool pipelined = !p.fid_k && nkt >= ATTN_PIPELINED_MIN_TILES;
+  auto to = [&](int route) { pl.route = route; return pl; };
+  if (form == FORM_WINDOW) {
+    for (int i = 0; i < 3; ++i) pl.win[i] = win ? win[i] : 0;
+    return to(nkt < ATTN_PIPELINED_MIN_TILES ? attn_window_too_short(nkt) : ATTN_Q64_WIN);
+  }
+  const bool exact = form == FORM_EXACT;
+#ifdef LD_VARIANTS
+  static int k_q128 = LD_KNOB_UNSET, k_npre = LD_KNOB_UNSET;
+  const int q128 = ld_knob("LD_ATTN_Q128", 0, &k_q128);
+  pl.npre = ld_knob("LD_ATTN_NPRE", 44, &k_npre);
+  if (pl.variant == 0 && !exact && pipelined && (q128 == 2 || (q128 == 1 && (int64_t)p.B * p.H * ((p.Npad + 511) / 512) >= 512)))
+    return to(ATTN_Q128);
+#endif
+  // exact form: the two-pass kernel where the pipelined tile applies; every other shape takes the plain kernel, whose online
+  // softmax is exact for any logit range already
+  if (exact && pipelined) return to(ATTN_Q64_EXACT);
+  if (pl.variant == 0 && pipelined && q64 && !exact) return to(ATTN_Q64);
+  if (pl.variant == 0 && pipelined && !exact) return to(ATTN_P16);        // any tile count
+#ifdef LD_VARIANTS
+  if (pl.variant == 8 && !exact && pipelined && (nkt - 2) % 4 == 0) return to(ATTN_PIPE2);   // (the round-1 kernel: tile counts 4 m + 2)
+#endif
+  return to(ATTN_PLAIN);       // by pl.variant: ld_attn_kernel<false,3> | <true,2> (1) | <false,4> (4)
+}
+
+static int attn_plain_launch(const AttnParams& p, hipStream_t st, int variant, AttnRan* ran) {
+  auto launch = [&](void (*kernel)(AttnParams), const char* name) {
+    *ran = {name, nullptr, 0};                   // a running-max kernel: no window to leave
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((int64_t)p.B * p.H * (p.Npad / QB))), dim3(256), 2 * STAGE_BYTES + 64, st, p);
+    return ld_check_launch("ld_attn_fwd_bf16");
+  };
+  if (variant == 1) return launch(ld_attn_kernel<true, 2>, "ld_attn_kernel<true,2>");
+  if (variant == 4) return launch(ld_attn_kernel<false, 4>, "ld_attn_kernel<false,4>");
+  return launch(ld_attn_kernel<false, LD_ATTN_PLAIN_WPS>, "ld_attn_kernel<false," LD_STR(LD_ATTN_PLAIN_WPS) ">");
+}
+
+// Executes a plan: one launcher call, and the one place that records what ran (a launcher that fails before its launch reports
+// nothing, and the record stays what it was).
+static int attn_run(const AttnPlan& pl, const AttnParams& p, hipStream_t st) {
+  if (pl.route < 0) return pl.route;
+  AttnRan ran = {nullptr, nullptr, 0};
+  int rc;
+  switch (pl.route) {
+    case ATTN_Q64: rc = ld_attn_q64_launch(p, st, nullptr, pl.safe, pl.want_dyn, &ran); break;
+    case ATTN_Q64_WIN: rc = ld_attn_q64_launch(p, st, pl.win, pl.safe, pl.want_dyn, &ran); break;
+    case ATTN_Q64_EXACT: rc = ld_attn_q64_exact_launch(p, st, &ran); break;
+    case ATTN_P16: rc = ld_attn_p16_launch(p, st, pl.safe, pl.msum, pl.nw, &ran); break;
+#ifdef LD_VARIANTS
+    case ATTN_Q128: rc = ld_attn_q128_launch(p, st, pl.safe, pl.npre, &ran); break;
+    case ATTN_PIPE2: rc = ld_attn_pipe2_launch(p, st, pl.safe, pl.nw, &ran); break;
+#endif
+    default: rc = attn_plain_launch(p, st, pl.variant, &ran); break;
+  }
+  if (ran.name) g_attn_ran = ran;
+  return rc;
+}
+
+// the shape rules (`who` names the entry point in the messages): pure, so that ld_attn_route answers with the launch's own messages
+static int attn_check_shape(const char* who, AttnForm form, int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t Npad) {
+  LD_REQUIRE(B > 0 && H > 0 && Nq > 0 && Nk > 0, "%s: empty problem", who);
+  LD_REQUIRE(Npad % QB == 0 && Npad >= Nq && Npad >= Nk, "%s: Npad=%ld must be a multiple of %d and >= %s", who, (long)Npad, QB,
+             form == FORM_WINDOW ? "N" : "Nq,Nk");
+  if (form == FORM_WINDOW) LD_REQUIRE(B * H * ((Npad + 255) / 256) < (1LL << 31), "%s: grid too large", who);
+  return LD_OK;
+}
+
+// What the three entry points share: pointers, shapes, mask tables and alignment checked (in this order: the first failure names
+// itself), the parameter block filled, the plan made and run.
+static int attn_fwd(const char* who, AttnForm form, const int* win, const void* Q, const void* K, const void* Vt, void* O,
+                    int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t Npad, int64_t o_batch_stride, int64_t o_row_stride,
+                    float softmax_scale, const int32_t* fid_q, const int32_t* fid_k, const int32_t* kt_min, const int32_t* kt_max, void* stream) {
+  LD_REQUIRE(Q && K && Vt && O, "%s: null pointer", who);
+  if (int rc = attn_check_shape(who, form, B, H, Nq, Nk, Npad)) return rc;
+  LD_REQUIRE((fid_q == nullptr) == (fid_k == nullptr), "%s: fid_q and fid_k go together", who);
+  LD_REQUIRE(!fid_k || (kt_min && kt_max), "%s: masked attention needs kt_min/kt_max", who);
+  LD_REQUIRE(o_row_stride % 4 == 0 && ((uintptr_t)O & 7) == 0, "%s: output alignment", who);
   AttnParams p{};
   p.Q = (const bf16_t*)Q; p.K = (const bf16_t*)K; p.Vt = (const bf16_t*)Vt; p.O = (bf16_t*)O;
   p.B = (int)B; p.H = (int)H; p.Nq = (int)Nq; p.Nk = (int)Nk; p.Npad = (int)Npad;
   p.o_bs = o_batch_stride; p.o_rs = o_row_stride;
   p.c = softmax_scale * 1.4426950408889634f;
   p.fid_q = fid_q; p.fid_k = fid_k; p.kt_min = kt_min; p.kt_max = kt_max;
-  const int nqb = (int)(Npad / QB);
-  dim3 grid((unsigned)(B * H * nqb)), block(256);
-  static int var = -1;
-  if (var < 0) {
-    // tuning knob: 0 = default (pipelined 16x16x32 kernels of ld_attn_q64.hip / ld_attn_p16.hip for every unmasked problem of >= 6 key tiles, else the plain kernel),
-    // 8 = the pipelined 32x32x16 kernel of ld_attn_pipe.hip (round-1 default; variants build only), 9 = plain kernel everywhere,
-    // 1 / 4 = plain kernel with row sums on the matrix pipe / lean-register 4-waves form
-    const char* e = getenv("LD_ATTN_VARIANT");
-    var = e ? atoi(e) : 0;
-  }
-  hipStream_t st = (hipStream_t)stream;
-  ld_attn_set_fallback_source(nullptr, 0);          // (the pipelined launchers below say otherwise)
-  const size_t s1 = 2 * STAGE_BYTES + 64;
-  const int64_t nkt = (Nk + KT - 1) / KT;
-  // LD_ATTN_Q64=0 (tuning knob): the 32-query-row wave tile of ld_attn_p16.hip instead of the 64-row one of ld_attn_q64.hip
-  static const int q64 = getenv("LD_ATTN_Q64") ? atoi(getenv("LD_ATTN_Q64")) : 1;
-#ifdef LD_VARIANTS
-  // LD_ATTN_Q128 (variants build only): 1 = the 128-query-row, one-wave-per-SIMD tile of ld_attn_q128.hip (512 rows per workgroup:
-  // only for problems with enough query rows to fill the chip with such workgroups); 2 = every unmasked problem of >= 6 key tiles.
-  // Like every knob it is read once, or per call under LD_TUNING=1 (ld_common.h) so that one process can time both tiles.
-  static int k_q128 = LD_KNOB_UNSET;
-  const int q128 = ld_knob("LD_ATTN_Q128", 0, &k_q128);
-  if (var == 0 && !exact && !fid_k && nkt >= 6 && (q128 == 2 || (q128 == 1 && B * H * ((Npad + 511) / 512) >= 512)))
-    return ld_attn_q128_launch(p, st);
-#endif
-  // exact form: the two-pass kernel where the pipelined tile applies; every other shape takes the plain kernel below, whose online
-  // softmax is exact for any logit range already
-  if (exact && !fid_k && nkt >= 6) return ld_attn_q64_exact_launch(p, st);
-  if (var == 0 && !fid_k && nkt >= 6 && q64 && !exact) return ld_attn_q64_launch(p, st);
-  if (var == 0 && !fid_k && nkt >= 6 && !exact) return ld_attn_p16_launch(p, st);        // any tile count
-#ifdef LD_VARIANTS
-  if (var == 8 && !exact && !fid_k && nkt >= 6 && (nkt - 2) % 4 == 0) return ld_attn_pipe2_launch(p, st);   // (the round-1 kernel: tile counts 4 m + 2)
-#endif
-  if (var == 1) {
-    g_attn_last_kernel = "ld_attn_kernel<1,true,false,true,2>";
-    hipLaunchKernelGGL((ld_attn_kernel<1, true, false, true, 2>), grid, block, s1, st, p);
-  } else if (var == 4) {
-    g_attn_last_kernel = "ld_attn_kernel<1,true,false,false,4>";
-    hipLaunchKernelGGL((ld_attn_kernel<1, true, false, false, 4>), grid, block, s1, st, p);
-  } else {
-    g_attn_last_kernel = "ld_attn_kernel<1,true,false,false," LD_STR(LD_ATTN_PLAIN_WPS) ">";
-    hipLaunchKernelGGL((ld_attn_kernel<1, true, false, false, LD_ATTN_PLAIN_WPS>), grid, block, s1, st, p);
-  }
-  return ld_check_launch("ld_attn_fwd_bf16");
+  return attn_run(attn_plan(p, form, win), p, (hipStream_t)stream);
 }
 
 LD_API int ld_attn_fwd_bf16(const void* Q, const void* K, const void* Vt, void* O,
@@ -449,15 +479,15 @@ LD_API int ld_attn_fwd_bf16(const void* Q, const void* K, const void* Vt, void* 
                             int64_t o_batch_stride, int64_t o_row_stride, float softmax_scale,
                             const int32_t* fid_q, const int32_t* fid_k,
                             const int32_t* kt_min, const int32_t* kt_max, void* stream) {
-  return attn_fwd_impl(Q, K, Vt, O, B, H, Nq, Nk, Npad, o_batch_stride, o_row_stride, softmax_scale, fid_q, fid_k, kt_min, kt_max, stream, false);
+  return attn_fwd("ld_attn_fwd_bf16", FORM_DEFAULT, nullptr, Q, K, Vt, O, B, H, Nq, Nk, Npad, o_batch_stride, o_row_stride, softmax_scale, fid_q, fid_k, kt_min, kt_max, stream);
 }
 
 LD_API int ld_attn_fwd_bf16_exact(const void* Q, const void* K, const void* Vt, void* O,
                                   int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t Npad,
                                   int64_t o_batch_stride, int64_t o_row_stride, float softmax_scale,
                                   const int32_t* fid_q, const int32_t* fid_k,
-                                  const int32_t* kt_min, const int32_t* kt_max, void* stream) {
-  return attn_fwd_impl(Q, K, Vt, O, B, H, Nq, Nk, Npad, o_batch_stride, o_row_stride, softmax_scale, fid_q, fid_k, kt_min, kt_max, stream, true);
+                                  const int32_t* kt_min, const int32_t* kt_max, void* stream) {      // (one operation with ld_attn_fwd_bf16: its messages carry that name)
+  return attn_fwd("ld_attn_fwd_bf16", FORM_EXACT, nullptr, Q, K, Vt, O, B, H, Nq, Nk, Npad, o_batch_stride, o_row_stride, softmax_scale, fid_q, fid_k, kt_min, kt_max, stream);
 }
 
 // ---- frame-window attention: every 256-row query block walks the prefix tiles and the tiles of the frames within `window` of its
@@ -491,26 +521,35 @@ LD_API int ld_attn_fwd_bf16_window(const void* Q, const void* K, const void* Vt,
   // the window's own rules first (pure host arithmetic: a caller may probe a shape without a device)
   if (int rc = attn_window_args("ld_attn_fwd_bf16_window", N, prefix, &group, &window)) return rc;
   const int64_t n = (N + KT - 1) / KT, pt = (prefix + KT - 1) / KT;
-  if (n < 6) return ld_set_error(LD_ERR_UNSUPPORTED, "ld_attn_fwd_bf16_window: %ld key tiles; the pipelined kernel needs at least 6", (long)n);
+  if (n < ATTN_PIPELINED_MIN_TILES) return attn_window_too_short(n);
   for (int64_t b = 0; b < (N + 255) / 256; ++b) {
     int lo, hi, ne;
     attn_window_block((int)N, (int)prefix, (int)group, (int)window, (int)b, &lo, &hi, &ne);
-    if (ne < 6)
+    if (ne < ATTN_PIPELINED_MIN_TILES)
       return ld_set_error(LD_ERR_UNSUPPORTED, "ld_attn_fwd_bf16_window: query block %ld would walk %d key tiles (prefix %ld, group %ld, window %ld); "
-                          "the pipelined kernel needs at least 6", (long)b, ne, (long)prefix, (long)group, (long)window);
+                          "the pipelined kernel needs at least %d", (long)b, ne, (long)prefix, (long)group, (long)window, ATTN_PIPELINED_MIN_TILES);
     if (!(lo >= pt && lo <= hi && hi <= n))     // (cannot happen: the rule keeps every list inside [0, n))
       return ld_set_error(LD_ERR_INVALID, "ld_attn_fwd_bf16_window: block %ld: tile range [%d, %d) outside [%ld, %ld]", (long)b, lo, hi, (long)pt, (long)n);
   }
-  LD_REQUIRE(Q && K && Vt && O, "ld_attn_fwd_bf16_window: null pointer");
-  LD_REQUIRE(B > 0 && H > 0, "ld_attn_fwd_bf16_window: empty problem");
-  LD_REQUIRE(Npad % QB == 0 && Npad >= N, "ld_attn_fwd_bf16_window: Npad=%ld must be a multiple of %d and >= N", (long)Npad, QB);
-  LD_REQUIRE(o_row_stride % 4 == 0 && ((uintptr_t)O & 7) == 0, "ld_attn_fwd_bf16_window: output alignment");
-  LD_REQUIRE(B * H * ((Npad + 255) / 256) < (1LL << 31), "ld_attn_fwd_bf16_window: grid too large");
-  AttnParams p{};
-  p.Q = (const bf16_t*)Q; p.K = (const bf16_t*)K; p.Vt = (const bf16_t*)Vt; p.O = (bf16_t*)O;
-  p.B = (int)B; p.H = (int)H; p.Nq = (int)N; p.Nk = (int)N; p.Npad = (int)Npad;
-  p.o_bs = o_batch_stride; p.o_rs = o_row_stride;
-  p.c = softmax_scale * 1.4426950408889634f;
   const int win[3] = {(int)prefix, (int)group, (int)window};
-  return ld_attn_q64_launch_any(p, (hipStream_t)stream, win);
+  return attn_fwd("ld_attn_fwd_bf16_window", FORM_WINDOW, win, Q, K, Vt, O, B, H, N, N, Npad, o_batch_stride, o_row_stride, softmax_scale,
+                  nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+// The plan run dry: the route code of the kernel family a launch of these shapes would take (landiff_hip.h), or the launch's own
+// refusal.  No HIP call.
+LD_API int ld_attn_route(int64_t B, int64_t H, int64_t Nq, int64_t Nk, int64_t Npad, int32_t masked, int32_t form) {
+  LD_REQUIRE(form >= FORM_DEFAULT && form <= FORM_WINDOW, "ld_attn_route: form %d is not 0 (default), 1 (exact) or 2 (window)", (int)form);
+  const char* who = form == FORM_WINDOW ? "ld_attn_fwd_bf16_window" : "ld_attn_fwd_bf16";
+  if (form == FORM_WINDOW) {
+    LD_REQUIRE(!masked && Nq == Nk, "ld_attn_route: there is no masked or rectangular (Nq=%ld, Nk=%ld) window form", (long)Nq, (long)Nk);
+    int64_t one_frame = Nk > 0 ? Nk : 1, every = 0;         // (the sequence alone: the window's own numbers are ld_attn_window_plan's)
+    if (int rc = attn_window_args(who, Nk, 0, &one_frame, &every)) return rc;
+  }
+  if (int rc = attn_check_shape(who, (AttnForm)form, B, H, Nq, Nk, Npad)) return rc;
+  static const int32_t some_mask = 0;       // (the plan only asks whether there is a mask)
+  AttnParams p{};
+  p.B = (int)B; p.H = (int)H; p.Nq = (int)Nq; p.Nk = (int)Nk; p.Npad = (int)Npad;
+  if (masked) p.fid_q = p.fid_k = &some_mask;
+  return attn_plan(p, (AttnForm)form, nullptr).route;
 }

@@ -482,23 +482,13 @@ __global__ __launch_bounds__(256, 2) void ld_attn_p16a_w4_kernel(AttnParams p, i
 
 }  // namespace
 
-void ld_attn_set_last_kernel(const char* name);   // ld_attn.hip
-void ld_attn_set_fallback_source(const unsigned* src, int kind);   // ld_attn.hip
-
-// LD_ATTN_SAFE=1 forces the running-max pass (testing); LD_ATTN_MSUM=0 takes the row sums by v_add_f32 (A/B timing).
-int ld_attn_p16_launch(const AttnParams& p, hipStream_t st) {
+// msum = 0: the row sums by v_add_f32 (4-wave workgroups only); nw = 8: 8-wave workgroups.  fb_kind 2: a fast pass with a window, no count kept.
+int ld_attn_p16_launch(const AttnParams& p, hipStream_t st, int safe, int msum, int nw, AttnRan* ran) {
   constexpr int SMEM = 8 * KTILE_BYTES + 64;
-  static int safe = -1, msum = 1, nw = 4;
-  if (safe < 0) {
-    const char* e = getenv("LD_ATTN_SAFE"); safe = e ? atoi(e) : 0;
-    const char* m = getenv("LD_ATTN_MSUM"); if (m) msum = atoi(m);
-    const char* w = getenv("LD_ATTN_NW"); if (w && atoi(w) == 8) nw = 8;
-  }
   static thread_local LdSmemCache c4{}, c4a{}, c8{};
-  ld_attn_set_fallback_source(nullptr, safe ? 0 : 2);       // a fast pass with a window, no count kept
   if (nw == 8 && msum) {
     if (int rc = ld_ensure_dyn_smem((const void*)ld_attn_p16_w8_kernel, SMEM, &c8)) return rc;
-    ld_attn_set_last_kernel(safe ? "ld_attn_p16_w8_kernel[safe pass forced]" : "ld_attn_p16_w8_kernel");
+    *ran = {safe ? "ld_attn_p16_w8_kernel[safe pass forced]" : "ld_attn_p16_w8_kernel", nullptr, safe ? 0 : 2};
     hipLaunchKernelGGL(ld_attn_p16_w8_kernel, dim3((unsigned)((long)p.B * p.H * ((p.Npad + 255) / 256))), dim3(512), SMEM, st, p, safe);
     return ld_check_launch("ld_attn_fwd_bf16(p16 w8)");
   }
@@ -506,10 +496,10 @@ int ld_attn_p16_launch(const AttnParams& p, hipStream_t st) {
                     : ld_ensure_dyn_smem((const void*)ld_attn_p16a_w4_kernel, SMEM, &c4a)) return rc;
   dim3 grid((unsigned)((long)p.B * p.H * ((p.Npad + 127) / 128)));
   if (msum) {
-    ld_attn_set_last_kernel(safe ? "ld_attn_p16_w4_kernel[safe pass forced]" : "ld_attn_p16_w4_kernel");
+    *ran = {safe ? "ld_attn_p16_w4_kernel[safe pass forced]" : "ld_attn_p16_w4_kernel", nullptr, safe ? 0 : 2};
     hipLaunchKernelGGL(ld_attn_p16_w4_kernel, grid, dim3(256), SMEM, st, p, safe);
   } else {
-    ld_attn_set_last_kernel(safe ? "ld_attn_p16a_w4_kernel[safe pass forced]" : "ld_attn_p16a_w4_kernel");
+    *ran = {safe ? "ld_attn_p16a_w4_kernel[safe pass forced]" : "ld_attn_p16a_w4_kernel", nullptr, safe ? 0 : 2};
     hipLaunchKernelGGL(ld_attn_p16a_w4_kernel, grid, dim3(256), SMEM, st, p, safe);
   }
   return ld_check_launch("ld_attn_fwd_bf16(p16)");

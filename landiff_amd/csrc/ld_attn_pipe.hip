@@ -344,25 +344,16 @@ __global__ __launch_bounds__(512, 2) void ld_attn_pipe2_w8_kernel(AttnParams p, 
 
 }  // namespace
 
-void ld_attn_set_last_kernel(const char* name);   // ld_attn.hip
-void ld_attn_set_fallback_source(const unsigned* src, int kind);   // ld_attn.hip
-
-// LD_ATTN_SAFE=1 forces the running-max pass (testing / A-B timing); LD_ATTN_NW=4|8 picks the workgroup size.
-int ld_attn_pipe2_launch(const AttnParams& p, hipStream_t st) {
+// nw = 4 | 8: the workgroup size in waves
+int ld_attn_pipe2_launch(const AttnParams& p, hipStream_t st, int safe, int nw, AttnRan* ran) {
   constexpr int SMEM = 8 * KTILE_BYTES + 64;
-  static int safe = -1, nw = 4;       // 8-wave workgroups halve the K/V traffic per CU but measure the same (4.44 vs 4.46 ms)
-  if (safe < 0) {
-    const char* e = getenv("LD_ATTN_SAFE"); safe = e ? atoi(e) : 0;
-    const char* w = getenv("LD_ATTN_NW"); if (w && atoi(w) == 8) nw = 8;
-  }
   static thread_local LdSmemCache c4{}, c8{};
   if (int rc = nw == 4 ? ld_ensure_dyn_smem((const void*)ld_attn_pipe2_w4_kernel, SMEM, &c4)
                        : ld_ensure_dyn_smem((const void*)ld_attn_pipe2_w8_kernel, SMEM, &c8)) return rc;
   const int qbw = nw * 32;
   dim3 grid((unsigned)((long)p.B * p.H * ((p.Npad + qbw - 1) / qbw)));
-  ld_attn_set_fallback_source(nullptr, safe ? 0 : 2);
-  ld_attn_set_last_kernel(nw == 4 ? (safe ? "ld_attn_pipe2_w4_kernel[safe pass forced]" : "ld_attn_pipe2_w4_kernel")
-                                  : (safe ? "ld_attn_pipe2_w8_kernel[safe pass forced]" : "ld_attn_pipe2_w8_kernel"));
+  *ran = {nw == 4 ? (safe ? "ld_attn_pipe2_w4_kernel[safe pass forced]" : "ld_attn_pipe2_w4_kernel")
+                  : (safe ? "ld_attn_pipe2_w8_kernel[safe pass forced]" : "ld_attn_pipe2_w8_kernel"), nullptr, safe ? 0 : 2};
   if (nw == 4) hipLaunchKernelGGL(ld_attn_pipe2_w4_kernel, grid, dim3(256), SMEM, st, p, safe);
   else hipLaunchKernelGGL(ld_attn_pipe2_w8_kernel, grid, dim3(512), SMEM, st, p, safe);
   return ld_check_launch("ld_attn_fwd_bf16(pipe2)");

@@ -502,16 +502,9 @@ LD_Q128_KERNEL(ld_attn_q128_s1n40_kernel, 40, 1)       // (LD_ATTN_NPRE=1040)
 
 }  // namespace
 
-void ld_attn_set_last_kernel(const char* name);   // ld_attn.hip
-void ld_attn_set_fallback_source(const unsigned* src, int kind);   // ld_attn.hip
-
-// LD_ATTN_SAFE=1 forces the running-max pass (testing); LD_ATTN_NPRE=36|52 picks the other exp2 splits (A/B timing).
-int ld_attn_q128_launch(const AttnParams& p, hipStream_t st) {
+// npre: 44 = the shipped exp2 split; 36 | 52 | 1036 | 1040 the other instantiations above; anything else runs the shipped one
+int ld_attn_q128_launch(const AttnParams& p, hipStream_t st, int safe, int npre, AttnRan* ran) {
   constexpr int SMEM = 8 * KTILE_BYTES + 64;
-  static int safe = -1;
-  if (safe < 0) { const char* e = getenv("LD_ATTN_SAFE"); safe = e ? atoi(e) : 0; }
-  static int k_npre = LD_KNOB_UNSET;
-  const int npre = ld_knob("LD_ATTN_NPRE", 44, &k_npre);
   static thread_local LdSmemCache c44{}, c36{}, c52{}, cs1{}, cs2{};
   dim3 grid((unsigned)((long)p.B * p.H * ((p.Npad + Q128_ROWS - 1) / Q128_ROWS)));
   if (npre != 44) {
@@ -522,15 +515,13 @@ int ld_attn_q128_launch(const AttnParams& p, hipStream_t st) {
     else if (npre == 1040) { k = ld_attn_q128_s1n40_kernel; c = &cs2; name = "ld_attn_q128_s1n40_kernel"; }
     if (k) {
       if (int rc = ld_ensure_dyn_smem((const void*)k, SMEM, c)) return rc;
-      ld_attn_set_last_kernel(name);
-      ld_attn_set_fallback_source(nullptr, safe ? 0 : 2);
+      *ran = {name, nullptr, safe ? 0 : 2};
       hipLaunchKernelGGL(k, grid, dim3(256), SMEM, st, p, safe);
       return ld_check_launch("ld_attn_fwd_bf16(q128)");
     }
   }
   if (int rc = ld_ensure_dyn_smem((const void*)ld_attn_q128_kernel, SMEM, &c44)) return rc;
-  ld_attn_set_last_kernel(safe ? "ld_attn_q128_kernel[safe pass forced]" : "ld_attn_q128_kernel");
-  ld_attn_set_fallback_source(nullptr, safe ? 0 : 2);
+  *ran = {safe ? "ld_attn_q128_kernel[safe pass forced]" : "ld_attn_q128_kernel", nullptr, safe ? 0 : 2};
   hipLaunchKernelGGL(ld_attn_q128_kernel, grid, dim3(256), SMEM, st, p, safe);
   return ld_check_launch("ld_attn_fwd_bf16(q128)");
 }

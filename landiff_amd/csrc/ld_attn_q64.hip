@@ -194,25 +194,17 @@ int q64_device_info(int* dev_out, unsigned** base_out, int* slots_out) {
 
 }  // namespace
 
-void ld_attn_set_last_kernel(const char* name);   // ld_attn.hip
-void ld_attn_set_fallback_source(const unsigned* src, int kind);   // ld_attn.hip
-int ld_attn_q64_launch_any(const AttnParams& p, hipStream_t st, const int* win);
-
-// LD_ATTN_SAFE=1 forces the running-max pass (testing).  LD_ATTN_DYN=0: the hardware's round-robin dispatch of one workgroup per
-// query block instead of the dynamic form (the default for grids of at least four rounds of the chip's slots).
-int ld_attn_q64_launch(const AttnParams& p, hipStream_t st) { return ld_attn_q64_launch_any(p, st, nullptr); }
-
-// win: null = the dense kernels; else {prefix, group, frames} of the frame-window form (validated by ld_attn_fwd_bf16_window)
-int ld_attn_q64_launch_any(const AttnParams& p, hipStream_t st, const int* win) {
+// win: null = the dense kernels; else {prefix, group, frames} of the frame-window form (validated by ld_attn_fwd_bf16_window).
+// want_dyn (the plan: LD_ATTN_DYN and no forced safe pass): the dynamic form where it can be had -- a grid of at least four rounds of
+// the chip's slots, a stream that is not being captured and a counter set for it -- else the hardware's round-robin dispatch.
+int ld_attn_q64_launch(const AttnParams& p, hipStream_t st, const int* win, int safe, bool want_dyn, AttnRan* ran) {
   constexpr int SMEM = 8 * KTILE_BYTES + 64;
-  static int k_safe = LD_KNOB_UNSET, k_dyn = LD_KNOB_UNSET;
-  const int safe = ld_knob("LD_ATTN_SAFE", 0, &k_safe);
   static thread_local LdSmemCache cache{};
   static thread_local LdSmemCache cache_w{};
   if (int rc = win ? ld_ensure_dyn_smem((const void*)ld_attn_q64_win_kernel, SMEM, &cache_w)
                    : ld_ensure_dyn_smem((const void*)ld_attn_q64_kernel, SMEM, &cache)) return rc;
   const int total = (int)((long)p.B * p.H * ((p.Npad + Q64_ROWS - 1) / Q64_ROWS));
-  if (ld_knob("LD_ATTN_DYN", 1, &k_dyn) > 0 && !safe) {
+  if (want_dyn) {
     int dev = -1, slots = 0; unsigned* base = nullptr;
     if (int rc = q64_device_info(&dev, &base, &slots)) return rc;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
@@ -224,25 +216,23 @@ int ld_attn_q64_launch_any(const AttnParams& p, hipStream_t st, const int* win) 
                          : ld_ensure_dyn_smem((const void*)ld_attn_q64_dyn_kernel, SMEM, &cache_d)) return rc;
         hipError_t e = hipMemsetAsync(base + set * 16, 0, 64, st);
         if (e != hipSuccess) return ld_set_error(LD_ERR_LAUNCH, "ld_attn_fwd_bf16(q64 dynamic): zeroing counter set %d: %s", set, hipGetErrorString(e));
-        ld_attn_set_fallback_source(base + set * 16 + 8, 1);
         if (win) {
-          ld_attn_set_last_kernel("ld_attn_q64_win_dyn_kernel");
+          *ran = {"ld_attn_q64_win_dyn_kernel", base + set * 16 + 8, 1};
           hipLaunchKernelGGL(ld_attn_q64_win_dyn_kernel, dim3((unsigned)slots), dim3(256), SMEM, st, p, safe, total, set, win[0], win[1], win[2]);
           return ld_check_launch("ld_attn_fwd_bf16_window(q64 dynamic)");
         }
-        ld_attn_set_last_kernel("ld_attn_q64_dyn_kernel");
+        *ran = {"ld_attn_q64_dyn_kernel", base + set * 16 + 8, 1};
         hipLaunchKernelGGL(ld_attn_q64_dyn_kernel, dim3((unsigned)slots), dim3(256), SMEM, st, p, safe, total, set);
         return ld_check_launch("ld_attn_fwd_bf16(q64 dynamic)");
       }
     }
   }
-  ld_attn_set_fallback_source(nullptr, safe ? 0 : 2);
   if (win) {
-    ld_attn_set_last_kernel(safe ? "ld_attn_q64_win_kernel[safe pass forced]" : "ld_attn_q64_win_kernel");
+    *ran = {safe ? "ld_attn_q64_win_kernel[safe pass forced]" : "ld_attn_q64_win_kernel", nullptr, safe ? 0 : 2};
     hipLaunchKernelGGL(ld_attn_q64_win_kernel, dim3((unsigned)total), dim3(256), SMEM, st, p, safe, win[0], win[1], win[2]);
     return ld_check_launch("ld_attn_fwd_bf16_window(q64)");
   }
-  ld_attn_set_last_kernel(safe ? "ld_attn_q64_kernel[safe pass forced]" : "ld_attn_q64_kernel");
+  *ran = {safe ? "ld_attn_q64_kernel[safe pass forced]" : "ld_attn_q64_kernel", nullptr, safe ? 0 : 2};
   hipLaunchKernelGGL(ld_attn_q64_kernel, dim3((unsigned)total), dim3(256), SMEM, st, p, safe);
   return ld_check_launch("ld_attn_fwd_bf16(q64)");
 }

@@ -19,14 +19,12 @@ __global__ __launch_bounds__(256, 2) void ld_attn_q64_exact_kernel(AttnParams p)
 
 }  // namespace
 
-void ld_attn_set_last_kernel(const char* name);   // ld_attn.hip
-
-int ld_attn_q64_exact_launch(const AttnParams& p, hipStream_t st) {
+int ld_attn_q64_exact_launch(const AttnParams& p, hipStream_t st, AttnRan* ran) {
   constexpr int SMEM = 8 * KTILE_BYTES + 64;
   static thread_local LdSmemCache cache{};
   if (int rc = ld_ensure_dyn_smem((const void*)ld_attn_q64_exact_kernel, SMEM, &cache)) return rc;
   const int total = (int)((long)p.B * p.H * ((p.Npad + Q64_ROWS - 1) / Q64_ROWS));
-  ld_attn_set_last_kernel("ld_attn_q64_exact_kernel");
+  *ran = {"ld_attn_q64_exact_kernel", nullptr, 0};          // a two-pass softmax: no window to leave
   hipLaunchKernelGGL(ld_attn_q64_exact_kernel, dim3((unsigned)total), dim3(256), SMEM, st, p);
   return ld_check_launch("ld_attn_fwd_bf16_exact(q64)");
 }

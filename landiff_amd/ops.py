@@ -186,7 +186,20 @@ def conv_cl(x_padded: torch.Tensor, w: torch.Tensor, T: int, H: int, W: int,
 
 
 ATTN_KEY_TILE = 64                 # keys per tile of the attention kernels (kt_min / kt_max granularity)
-ATTN_PIPELINED_MIN_TILES = 6       # unmasked problems of at least this many key tiles take the pipelined kernels
+ATTN_PIPELINED_MIN_TILES = 6       # unmasked problems of at least this many key tiles take the pipelined kernels (the library's
+                                   # constant of that name: tests/test_attn_route_host.py finds it through attn_route)
+ATTN_FORMS = {"default": 0, "exact": 1, "window": 2}
+
+
+def attn_route(B: int, H: int, Nq: int, Nk: int, Npad: int, masked: bool = False, form: str = "default") -> int:
+    """ld_attn_route: the kernel family an attn_fwd (form "default" / "exact") or attn_fwd_window ("window") launch of these shapes
+    would run under the current LD_ATTN_* knobs -- 0 plain, 1 q64, 2 q64 exact, 3 q64 window, 4 p16, 5 q128, 6 pipe2 -- or
+    LandiffHipError with the launch's own refusal.  Host only: nothing is launched, no GPU needed."""
+    lib = _lib.load()
+    rc = lib.ld_attn_route(B, H, Nq, Nk, Npad, int(bool(masked)), ATTN_FORMS[form])
+    if rc < 0:
+        check(rc, "ld_attn_route")
+    return rc
 
 
 def attn_mask_tables(fid_q, fid_k, Npad: int, device=None):

@@ -95,6 +95,48 @@ def _last_kernel():
     return (_lib.load().ld_attn_last_kernel() or b"").decode()
 
 
+# ---- what ran is what the plan said: after a real launch, ld_attn_last_kernel names a kernel of the family ld_attn_route named ----
+ROUTE_KERNELS = {0: "ld_attn_kernel", 1: "ld_attn_q64_kernel", 2: "ld_attn_q64_exact_kernel", 4: "ld_attn_p16_w4_kernel"}
+
+
+def test_attn_launch_runs_the_kernel_family_the_route_names(cuda, monkeypatch):
+    """B = H = 1: the grids are far below four rounds of the chip, so the q64 launches are static.  Also: ld_attn_last_fallbacks still
+    answers 0 for the plain kernel (no window), -1 for the static q64 launch (a window, no count kept), 0 for the exact form."""
+    from landiff_amd import ops
+    for k in ("LD_ATTN_VARIANT", "LD_ATTN_Q64", "LD_ATTN_Q128", "LD_ATTN_SAFE", "LD_ATTN_DYN", "LD_ATTN_MSUM", "LD_ATTN_NW"):
+        monkeypatch.delenv(k, raising=False)
+    cnt = torch.full((1,), -7, device=cuda, dtype=torch.int32)
+
+    def launch(N, route, name, fallbacks, exact=False, masked=False):
+        Npad = (N + 127) // 128 * 128
+        q, k, vt = _qkv(cuda, 1, 1, N, seed=N)
+        kw = {}
+        if masked:
+            kw = dict(zip(("fid_q", "fid_k", "kt_min", "kt_max"), ops.attn_mask_tables(np.arange(N) // 100, np.arange(N) // 100, Npad, cuda)))
+        assert ops.attn_route(1, 1, N, N, Npad, masked=masked, form="exact" if exact else "default") == route
+        out = torch.zeros(1, N, 64, device=cuda, dtype=torch.bfloat16)
+        ops.attn_fwd(q, k, vt, out, N, N, 0.125, exact=exact, **kw)
+        got = _last_kernel()
+        assert got.startswith(ROUTE_KERNELS[route]) and (got == name or (name == "ld_attn_kernel" and got[len(name)] == "<")), got
+        cnt.fill_(-7)
+        ops.attn_last_fallbacks(cnt)
+        assert int(cnt.item()) == fallbacks, (got, int(cnt.item()))
+        s = (q[0, 0, :N].float() @ k[0, 0, :N].float().T) * 0.125
+        if masked:
+            f = torch.arange(N, device=cuda) // 100
+            s = s.masked_fill(f[None, :] > f[:, None], float("-inf"))
+        assert (out[0].float() - torch.softmax(s, 1) @ vt[0, 0, :, :N].float().T).abs().max().item() < 2e-2
+
+    launch(384, 1, "ld_attn_q64_kernel", -1)
+    launch(384, 2, "ld_attn_q64_exact_kernel", 0, exact=True)
+    launch(320, 0, "ld_attn_kernel", 0)
+    launch(384, 0, "ld_attn_kernel", 0, masked=True)
+    monkeypatch.setenv("LD_ATTN_Q64", "0")
+    launch(384, 4, "ld_attn_p16_w4_kernel", -1)
+    monkeypatch.setenv("LD_ATTN_SAFE", "1")
+    launch(384, 4, "ld_attn_p16_w4_kernel[safe pass forced]", 0)          # the running-max pass: nothing to fall back from
+
+
 # ---- the dynamic form of the 64-row kernel (ld_attn_q64_dyn_kernel: one workgroup per slot pulls query blocks, XCD by XCD) ----
 def _qkv(cuda, B, H, N, seed):
     g = torch.Generator(device=cuda).manual_seed(seed)

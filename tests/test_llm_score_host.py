@@ -97,7 +97,7 @@ def test_abi_15_exports_both_entry_points():
     from landiff_amd import _lib
     lib = _lib.load()
     hdr = open(os.path.join(ROOT, "include", "landiff_hip.h")).read()
-    assert lib.ld_version() == _lib.ABI_VERSION == int(re.search(r"#define LD_ABI_VERSION (\d+)", hdr).group(1)) == 15
+    assert lib.ld_version() == _lib.ABI_VERSION == int(re.search(r"#define LD_ABI_VERSION (\d+)", hdr).group(1)) >= 15      # (they came with 15)
     for name in ("ld_llm_token_logprobs", "ld_llm_head_f32"):
         assert hasattr(lib, name) and name in _lib.SIGNATURES and re.search(rf"\bint {name}\(", hdr)
 

@@ -74,6 +74,43 @@ def test_attn_q128_equals_q64_bit_for_bit_in_process(cuda, monkeypatch):
     assert torch.equal(outs[0], outs[1])
 
 
+# ---- the routes that only this build has, asked of the plan run dry (ld_attn_route; the shipped routes: tests/test_attn_route_host.py).
+# The rule, restated independently of the plan's code: LD_ATTN_Q128 first (default form, LD_ATTN_VARIANT=0, unmasked, >= 6 key tiles:
+# 2 = always, 1 = when B * H * ceil(Npad / 512) >= 512), then exact, q64 / p16, then LD_ATTN_VARIANT=8 for tile counts 4 m + 2. ----
+def _route(monkeypatch, B, H, N, masked=False, form="default", **knobs):
+    from landiff_amd import ops
+    for k in ("LD_ATTN_VARIANT", "LD_ATTN_Q64", "LD_ATTN_Q128"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in knobs.items():
+        monkeypatch.setenv(k, str(v))
+    return ops.attn_route(B, H, N, N, (N + 127) // 128 * 128, masked=masked, form=form)
+
+
+def test_attn_route_q128(monkeypatch):
+    assert _route(monkeypatch, 1, 1, 384) == 1
+    assert _route(monkeypatch, 1, 1, 384, LD_ATTN_Q128=2) == 5 and _route(monkeypatch, 2, 30, 17776, LD_ATTN_Q128=2) == 5
+    assert _route(monkeypatch, 1, 1, 320, LD_ATTN_Q128=2) == 0 and _route(monkeypatch, 1, 1, 384, masked=True, LD_ATTN_Q128=2) == 0
+    assert _route(monkeypatch, 1, 1, 384, form="exact", LD_ATTN_Q128=2) == 2 and _route(monkeypatch, 1, 1, 384, form="window", LD_ATTN_Q128=2) == 3
+    assert _route(monkeypatch, 1, 1, 384, LD_ATTN_Q128=2, LD_ATTN_Q64=0) == 5          # decided before the wave tile of the default kernels
+    assert _route(monkeypatch, 1, 1, 384, LD_ATTN_Q128=2, LD_ATTN_VARIANT=9) == 0
+    # 1: only problems that fill the chip with 512-row workgroups -- B * H * ceil(Npad / 512) >= 512
+    assert _route(monkeypatch, 2, 30, 17776, LD_ATTN_Q128=1) == 5                      # 60 * 35 = 2100
+    assert _route(monkeypatch, 1, 1, 384, LD_ATTN_Q128=1) == 1
+    assert _route(monkeypatch, 16, 32, 512, LD_ATTN_Q128=1) == 5 and _route(monkeypatch, 7, 73, 512, LD_ATTN_Q128=1) == 1      # 512, 511
+    assert _route(monkeypatch, 8, 32, 513, LD_ATTN_Q128=1) == 5 and _route(monkeypatch, 8, 32, 512, LD_ATTN_Q128=1) == 1       # Npad 640: 2 each
+    assert _route(monkeypatch, 16, 32, 512, LD_ATTN_Q128=1, LD_ATTN_Q64=0) == 5 and _route(monkeypatch, 7, 73, 512, LD_ATTN_Q128=1, LD_ATTN_Q64=0) == 4
+
+
+def test_attn_route_pipe2(monkeypatch):
+    for n in range(1, 24):                                                              # key tiles
+        want = 6 if n >= 6 and (n - 2) % 4 == 0 else 0
+        assert _route(monkeypatch, 1, 2, 64 * n, LD_ATTN_VARIANT=8) == want, n
+        assert _route(monkeypatch, 1, 2, 64 * n - 37, LD_ATTN_VARIANT=8) == want, n     # ragged last tile
+    assert _route(monkeypatch, 1, 2, 384, masked=True, LD_ATTN_VARIANT=8) == 0
+    assert _route(monkeypatch, 1, 2, 384, form="exact", LD_ATTN_VARIANT=8) == 2 and _route(monkeypatch, 1, 2, 384, form="window", LD_ATTN_VARIANT=8) == 3
+    assert _route(monkeypatch, 1, 2, 384, LD_ATTN_VARIANT=8, LD_ATTN_Q128=2) == 6      # the 128-row tile needs LD_ATTN_VARIANT=0
+
+
 def test_llm_chained_and_fused_blocks_equal_per_operation_chain_tiny(cuda, setup):
     """The two other forms of a decode step's blocks -- dependent launches on two streams (ld_llm_decode_blocks_chained) and one
     persistent launch with grid barriers (ld_llm_decode_forward_fused) -- against the per-operation chain on the tiny config: ids,
