@@ -33,7 +33,8 @@ extern "C" {
  * ld_llm_sample_advance_pairs were added.  15: ld_llm_token_logprobs and ld_llm_head_f32 were added;
  * ld_gemv_wide, ld_llm_decode_forward_wide and ld_llm_sample_advance_wide joined later, and so did ld_absdiff_sums,
  * ld_residual_sub, ld_residual_add, ld_attn_fwd_bf16_window, ld_attn_window_plan, ld_unpatchify_cfg_keep, ld_unpatchify_cond, ld_latent_pin and ld_mask_to_latent (additions do not change
- * the number: no existing signature moved).  16: ld_attn_route was added. */
+ * the number: no existing signature moved).  16: ld_attn_route was added; ld_resize_u8 and ld_resize_mask_u8 joined later
+ * (additions again). */
 #define LD_ABI_VERSION 16
 
 int ld_version(void);
@@ -638,6 +639,33 @@ int ld_latent_pin(float* x, const float* known, const float* noise, const uint8_
  * mapping), rows 8i .. 8i+7, columns 8j .. 8j+7.  LD_ERR_INVALID unless F % 4 == 1, Hp % 8 == 0, Wp % 8 == 0 and mask_px is
  * 8-byte aligned. */
 int ld_mask_to_latent(const uint8_t* mask_px, uint8_t* out, int64_t F, int64_t Hp, int64_t Wp, void* stream);
+
+/* ---- the conform stage (ld_conform.hip; landiff_amd/conform.py) ----
+ * Antialiased separable resampling of uint8 channels-last frames, with a crop box and a frame gather fused in (what torchvision's
+ * resize does for the reference, theia_extractor.py:88-90).  src [Fs][Hs][Ws][C], C 1 or 3; dst [n_out][Ho][Wo][C]; output frame k
+ * is made from source frame frame_idx[k] (int32 on the device; repeats and any order allowed; null: frame k, n_out <= Fs) -- the
+ * caller checks its range, an index outside [0, Fs) is clamped.  Only the box rows y0 .. y0+hc-1, columns x0 .. x0+wc-1 are read.
+ * The filter arrives as tables, built by the caller in float64 and rounded to fp32 (landiff_amd/conform.py axis_table), per axis
+ * over the box, n_in the box's size along it:  scale = n_in / n_out; half = 1 (filter 0, bilinear: f(x) = 1 - |x|, |x| < 1) or 2
+ * (filter 1, bicubic, Keys a = -0.5: f(x) = ((a+2)|x| - (a+3))x^2 + 1, |x| < 1; a(((|x| - 5)|x| + 8)|x| - 4), 1 <= |x| < 2);
+ * support = half * scale and inv = 1 / scale when scale >= 1, else half and 1;  c = scale (i + 0.5), lo = max(0, int(c - support
+ * + 0.5)), hi = min(n_in, int(c + support + 0.5));  tap j in [lo, hi) weighs f((j - c + 0.5) inv), divided by the taps' sum
+ * (PyTorch's antialias weights).  win [n_out][2] int32 = (lo, hi - lo), w [n_out][tmax] f32 = the weights of output i in
+ * w[i][0 .. cnt), tmax >= every cnt: any tap count.  A window is clamped into the box and to tmax taps whatever the table holds.
+ * value = sum_y w_y (sum_x w_x src): fp32 fma chains, nothing rounded in between, then clamp(round-half-even(v), 0, 255) once.
+ * `filter` must be the tables' filter: it sizes the tiles.  LD_ERR_INVALID: null pointer, C not 1 or 3, empty shape, a box that
+ * leaves the source, n_out > Fs without frame_idx, unknown filter. */
+int ld_resize_u8(const uint8_t* src, uint8_t* dst, const int32_t* frame_idx, const int32_t* win_y, const float* w_y,
+                 int64_t tmax_y, const int32_t* win_x, const float* w_x, int64_t tmax_x, int64_t Fs, int64_t Hs, int64_t Ws,
+                 int64_t C, int64_t n_out, int64_t Ho, int64_t Wo, int64_t y0, int64_t x0, int64_t hc, int64_t wc,
+                 int32_t filter, void* stream);
+
+/* The same geometry over a keep-mask, C = 1, no arithmetic: dst = 1 if every source byte in the window [lo_y, hi_y) x [lo_x, hi_x)
+ * of the filter's tables is non-zero, else 0 -- decided by the window's bounds, not by whether a weight happens to be 0; the rule
+ * of ld_mask_to_latent one level up (a pixel is kept only if everything it was made from is kept). */
+int ld_resize_mask_u8(const uint8_t* src, uint8_t* dst, const int32_t* frame_idx, const int32_t* win_y, const int32_t* win_x,
+                      int64_t Fs, int64_t Hs, int64_t Ws, int64_t n_out, int64_t Ho, int64_t Wo, int64_t y0, int64_t x0,
+                      int64_t hc, int64_t wc, int32_t filter, void* stream);
 
 /* timestep_embedding (sgm/modules/diffusionmodules/util.py:207-233): t [B] f32 -> [B][dim] bf16 (cos || sin). */
 int ld_timestep_embedding(const float* t, void* out, int64_t B, int64_t dim, float max_period, void* stream);

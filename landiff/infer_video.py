@@ -53,7 +53,7 @@ def parse_args(argv=None):
     parser.add_argument("--edit_video", type=str, default=None,
                         help="Edit this clip instead of generating from scratch (LanDiffPipeline.edit_video): a uint8 [4T-3, H, W, 3] "
                              ".npy or an mp4 when imageio can read it -- exactly one chunk at the model's frame size (49 frames of "
-                             "480 x 720), never resized.  Writes the edited clip and <save_file_name>_edit.json.")
+                             "480 x 720), never resized unless --clip_fit says how.  Writes the edited clip and <save_file_name>_edit.json.")
     parser.add_argument("--edit_strength", type=float, default=0.6, metavar="S",
                         help="With --edit_video: the share of the sampler's steps that run, in (0, 1].  1.0 regenerates from pure "
                              "noise; smaller values start later, from the re-noised clip, and stay closer to it.")
@@ -67,6 +67,20 @@ def parse_args(argv=None):
     parser.add_argument("--edit_clean_known", action="store_true",
                         help="With --edit_video and --edit_mask: pin the kept cells to the clean clip latent at every step instead "
                              "of its re-noised version.")
+    parser.add_argument("--clip_fit", choices=("exact", "cover", "stretch"), default="exact",
+                        help="How the input of --extend_video, --edit_video (with its --edit_mask) or --first_frame is brought to the "
+                             "model's frame (the conform stage, on the GPU).  exact: it must already be that size (the default: "
+                             "nothing is resized).  cover: the largest centred box of the frame's aspect ratio, resampled.  "
+                             "stretch: the whole picture, resampled.  Writes <save_file_name>_conform.json.")
+    parser.add_argument("--clip_fps", type=str, default=None, metavar="F",
+                        help="With --clip_fit cover / stretch: the input clip's frame rate (a number or a ratio such as 30000/1001); "
+                             "the model's frames are then picked at 8 fps from it.  Without it frames are taken one to one.  (Not "
+                             "read from the container.)")
+    parser.add_argument("--clip_start", type=float, default=None, metavar="S",
+                        help="With --clip_fps: take the frames from S seconds into the clip on (--edit_video) instead of its "
+                             "first ones; --extend_video always continues the clip's end.")
+    parser.add_argument("--clip_filter", choices=("bilinear", "bicubic"), default=None,
+                        help="With --clip_fit cover / stretch: the antialiased resampling filter (default bilinear).")
     parser.add_argument("--dit_cache", type=str, default=None, metavar="THRESH",
                         help="DiT step cache (off by default): a sampler step whose first-block input moved by less than THRESH "
                              "(accumulated relative L1, a float >= 0) since the last computed step reuses that step's residual across "
@@ -130,6 +144,24 @@ def parse_args(argv=None):
             args.edit_tokens = "from_frames" if args.theia_ckpt else "prompt"
     if args.num_samples > 1 and args.extend_video:
         parser.error("--num_samples applies to generation from a prompt, not to --extend_video")
+    args.conform = None
+    if args.clip_fit == "exact":
+        if args.clip_fps is not None or args.clip_start is not None or args.clip_filter is not None:
+            parser.error("--clip_fps / --clip_start / --clip_filter go with --clip_fit cover or stretch")
+    else:
+        if not (args.extend_video or args.edit_video or args.first_frame):
+            parser.error("--clip_fit fits the input of --extend_video, --edit_video or --first_frame: give one of them")
+        if args.clip_start is not None and (args.clip_fps is None or not args.edit_video):
+            parser.error("--clip_start goes with --clip_fps and --edit_video (--extend_video continues the clip's end)")
+        if args.clip_fps is not None and not (args.extend_video or args.edit_video):
+            parser.error("--clip_fps is the frame rate of the --extend_video / --edit_video clip")
+        from landiff_amd.conform import ConformConfig
+        try:
+            args.conform = ConformConfig(fit=args.clip_fit, src_fps=args.clip_fps,
+                                         window="last" if args.extend_video or args.clip_fps is None or args.clip_start is None else "first",
+                                         start_s=args.clip_start or 0.0, filter=args.clip_filter or "bilinear")
+        except (ValueError, ZeroDivisionError) as e:
+            parser.error(f"--clip_fps / --clip_start: {e}")
     if args.num_samples > 1 and not all(args.seed + i for i in range(args.num_samples)):
         parser.error("--num_samples needs non-zero seeds (--seed .. --seed + N - 1)")
     if args.keep is not None:
@@ -175,6 +207,13 @@ def first_frame_tokens(args) -> torch.Tensor:
     img = load_image(args.first_frame)
     dev = torch.device(f"cuda:{torch.cuda.current_device()}")
     theia = build_theia_tokenizer(args, dev)
+    if getattr(args, "conform", None) is not None:
+        from landiff.diffusion.dif_infer import DEFAULT_INFER_CFG, DEFAULT_MODEL_CFG, _cfg_path
+        from landiff_amd.config import load_diffusion_config
+        from landiff_amd.conform import conform_image, image_plan
+        d = load_diffusion_config(_cfg_path(DEFAULT_MODEL_CFG), _cfg_path(DEFAULT_INFER_CFG)).dit
+        _write_conform_json(args, image_plan(tuple(img.shape), 8 * d.latent_h, 8 * d.latent_w, args.conform).as_dict())
+        img = conform_image(img, 8 * d.latent_h, 8 * d.latent_w, args.conform, dev)
     tokens = theia.tokenize_image(img.to(dev)).cpu()
     del theia
     torch.cuda.empty_cache()
@@ -258,6 +297,11 @@ def _dit_options(args) -> dict:
     return kw
 
 
+def _conform_options(args) -> dict:
+    """--clip_fit cover / stretch as the conform= keyword of extend_video / edit_video, present only when the flag was given."""
+    return {} if getattr(args, "conform", None) is None else {"conform": args.conform}
+
+
 def _write_dit_cache_report(args, stem, report):
     """--dit_cache: <stem>_dit_cache.json, what the step cache did in the run that produced <stem>.mp4."""
     if getattr(args, "dit_cache", None) is None:
@@ -276,6 +320,18 @@ def _write_dit_guidance_report(args, stem, report):
     path = Path(f"{stem}_dit_guidance.json")
     path.parent.mkdir(parents=True, exist_ok=True)
     write_report_json(str(path), report)
+
+
+def _write_conform_json(args, last_conform):
+    """--clip_fit cover / stretch: <save_file_name>_conform.json, what the conform stage did (box, scales, frame indices, fit, filter,
+    src_fps)."""
+    if getattr(args, "conform", None) is None or last_conform is None:
+        return
+    import json
+    path = Path(f"{args.save_file_name}_conform.json")
+    path.parent.mkdir(parents=True, exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(last_conform, f, indent=1, allow_nan=False)
 
 
 def infer_diffusion_samples(args, tokens, kept=None):
@@ -354,7 +410,7 @@ def extend_diffusion(args):
     generate_stream runs its later chunks (sliding semantic windows of one multi-segment AR decode, the prefix latents pinned,
     the decode continued against the VAE caches); --extend_tokens forces the decode's first segment to the clip's own tokens, and
     so does --theia_ckpt without --extend_tokens, with the tokens computed from the clip's frames.
-    Writes the clip followed by the new frames."""
+    Writes the clip followed by the new frames; with --clip_fit cover / stretch the conformed window followed by the new frames."""
     clip = load_clip(args.extend_video)
     pipe, inp = build_continuation(args)
     if args.extend_tokens:
@@ -362,7 +418,10 @@ def extend_diffusion(args):
     else:
         clip_tokens = "from_frames" if args.theia_ckpt else None
     new = pipe.extend_video(inp, args.extend_chunks, frames=clip, clip_tokens=clip_tokens,
-                            prefix_frames=args.extend_prefix_frames)
+                            prefix_frames=args.extend_prefix_frames, **_conform_options(args))
+    if getattr(args, "conform", None) is not None:
+        clip = pipe.last_conform_frames.cpu()
+        _write_conform_json(args, pipe.last_conform)
     _write_dit_cache_report(args, args.save_file_name, pipe.dit_cache_reports)        # one list per appended chunk
     _write_dit_guidance_report(args, args.save_file_name, pipe.dit_guidance_reports)
     frames = torch.cat([clip, new.cpu()], dim=0)
@@ -394,7 +453,8 @@ def edit_diffusion(args):
     elif args.edit_tokens != "prompt":
         kw["tokens"] = torch.from_numpy(np.load(args.edit_tokens)).reshape(-1)
     frames = pipe.edit_video(inp, frames=clip, strength=args.edit_strength, keep_mask=mask,
-                             known_noise=not args.edit_clean_known, **kw).cpu()
+                             known_noise=not args.edit_clean_known, **kw, **_conform_options(args)).cpu()
+    _write_conform_json(args, pipe.last_conform)
     _write_dit_cache_report(args, args.save_file_name, pipe.dit_cache_report() if getattr(args, "dit_cache", None) is not None else None)
     _write_dit_guidance_report(args, args.save_file_name,
                                pipe.dit_guidance_report() if getattr(args, "dit_guidance", None) is not None else None)

@@ -117,6 +117,8 @@ SIGNATURES: dict[str, list] = {
     "ld_axpbypcz": [P, P, c_float, P, c_float, P, c_float, I64, P],
     "ld_latent_pin": [P, P, P, P, c_float, c_float, I64, I64, I64, I64, P],
     "ld_mask_to_latent": [P, P, I64, I64, I64, P],
+    "ld_resize_u8": [P, P, P, P, P, I64, P, P, I64] + [I64] * 11 + [I32, P],
+    "ld_resize_mask_u8": [P, P, P, P, P] + [I64] * 10 + [I32, P],
     "ld_timestep_embedding": [P, P, I64, I64, c_float, P],
     "ld_absdiff_sums": [P, P, I64, P, P, I32, P],
     "ld_residual_sub": [P, P, P, I64, P, P, P, P],

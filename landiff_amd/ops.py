@@ -799,6 +799,77 @@ def mask_to_latent(mask_px, out=None):
     return out
 
 
+def _resize_geometry(name, src, dims, out_hw, frame_idx, box, filter):
+    """The shared argument checks of resize_u8 / resize_mask_u8 -> (Fs, Hs, Ws, n_out, Ho, Wo, box, device frame_idx, filter id)."""
+    from .conform import FILTERS
+    if src.dim() != dims or not src.is_contiguous():
+        raise ValueError(f"{name}: the source must be a contiguous {dims}-d tensor, got {tuple(src.shape)}")
+    Fs, Hs, Ws = src.shape[:3]
+    Ho, Wo = (int(v) for v in out_hw)
+    if min(Fs, Hs, Ws, Ho, Wo) < 1:
+        raise ValueError(f"{name}: empty shape (source {tuple(src.shape)}, target {Ho} x {Wo})")
+    if filter not in FILTERS:
+        raise ValueError(f"{name}: filter must be one of {tuple(FILTERS)}, got {filter!r}")
+    box = (0, 0, Hs, Ws) if box is None else tuple(int(v) for v in box)
+    y0, x0, hc, wc = box
+    if y0 < 0 or x0 < 0 or hc < 1 or wc < 1 or y0 + hc > Hs or x0 + wc > Ws:
+        raise ValueError(f"{name}: the crop box {box} leaves the {Hs} x {Ws} source")
+    idx = None
+    n_out = Fs
+    if frame_idx is not None:
+        host = [int(v) for v in (frame_idx.tolist() if hasattr(frame_idx, "tolist") else frame_idx)]
+        if not host or min(host) < 0 or max(host) >= Fs:
+            raise ValueError(f"{name}: frame_idx must be a non-empty list of indices in [0, {Fs}), got {host[:8]}{'...' if len(host) > 8 else ''}")
+        n_out = len(host)
+        if host != list(range(Fs)):                 # (the identity needs no table)
+            idx = torch.tensor(host, dtype=torch.int32).to(src.device)
+    return Fs, Hs, Ws, n_out, Ho, Wo, box, idx, FILTERS[filter]
+
+
+def _axis_tables(n_in, n_out, filter, device, weights=True):
+    from .conform import axis_table
+    win, w = axis_table(n_in, n_out, filter)
+    return torch.from_numpy(win).to(device), (torch.from_numpy(w).to(device) if weights else None)
+
+
+def resize_u8(src, out_hw, *, frame_idx=None, box=None, filter="bilinear", out=None):
+    """Antialiased resampling of uint8 channels-last frames [Fs, Hs, Ws, C] (C 1 or 3) -> uint8 [n_out, Ho, Wo, C]: output frame k
+    is made from the crop box (y0, x0, h, w) of source frame frame_idx[k] (a host list; None: every frame in order).  PyTorch's
+    antialias weights (conform.axis_table), fp32 accumulation, one clamp(round-half-even) at the end; only the box is read."""
+    if src.dtype != torch.uint8:
+        raise TypeError(f"resize_u8: the source must be uint8, got {src.dtype}")
+    if src.dim() == 4 and src.shape[3] not in (1, 3):
+        raise ValueError(f"resize_u8: C must be 1 or 3, got {tuple(src.shape)}")
+    Fs, Hs, Ws, n_out, Ho, Wo, box, idx, fid = _resize_geometry("resize_u8", src, 4, out_hw, frame_idx, box, filter)
+    C = src.shape[3]
+    if out is None:
+        out = torch.empty(n_out, Ho, Wo, C, dtype=torch.uint8, device=src.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (n_out, Ho, Wo, C) or not out.is_contiguous():
+        raise ValueError(f"resize_u8: out must be contiguous uint8 [{n_out}, {Ho}, {Wo}, {C}], got {out.dtype} {tuple(out.shape)}")
+    win_y, w_y = _axis_tables(box[2], Ho, filter, src.device)
+    win_x, w_x = _axis_tables(box[3], Wo, filter, src.device)
+    check(_lib.load().ld_resize_u8(_ptr(src), _ptr(out), _ptr(idx), _ptr(win_y), _ptr(w_y), w_y.shape[1], _ptr(win_x), _ptr(w_x),
+                                   w_x.shape[1], Fs, Hs, Ws, C, n_out, Ho, Wo, *box, fid, _stream()), "ld_resize_u8")
+    return out
+
+
+def resize_mask_u8(mask, out_hw, *, frame_idx=None, box=None, filter="bilinear", out=None):
+    """A keep-mask [Fs, Hs, Ws] (uint8 / bool, non-zero = keep) through resize_u8's geometry -> uint8 [n_out, Ho, Wo], 1 where every
+    source pixel in the output pixel's tap window [lo_y, hi_y) x [lo_x, hi_x) of `filter` is non-zero, else 0."""
+    if mask.dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f"resize_mask_u8: the mask must be uint8 or bool, got {mask.dtype}")
+    Fs, Hs, Ws, n_out, Ho, Wo, box, idx, fid = _resize_geometry("resize_mask_u8", mask, 3, out_hw, frame_idx, box, filter)
+    if out is None:
+        out = torch.empty(n_out, Ho, Wo, dtype=torch.uint8, device=mask.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (n_out, Ho, Wo) or not out.is_contiguous():
+        raise ValueError(f"resize_mask_u8: out must be contiguous uint8 [{n_out}, {Ho}, {Wo}], got {out.dtype} {tuple(out.shape)}")
+    win_y, _ = _axis_tables(box[2], Ho, filter, mask.device, weights=False)
+    win_x, _ = _axis_tables(box[3], Wo, filter, mask.device, weights=False)
+    check(_lib.load().ld_resize_mask_u8(_ptr(mask), _ptr(out), _ptr(idx), _ptr(win_y), _ptr(win_x), Fs, Hs, Ws, n_out, Ho, Wo, *box,
+                                        fid, _stream()), "ld_resize_mask_u8")
+    return out
+
+
 def timestep_embedding(t, out, max_period=10000.0):
     B, dim = out.shape
     check(_lib.load().ld_timestep_embedding(_ptr(t), _ptr(out), B, dim, float(max_period), _stream()),

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib, ops
 from .config import AttnWindowConfig, PipelineConfig
+from .conform import ConformConfig, conform_clip, conform_mask, conform_plan
 from .detokenizer import Detokenizer
 from .dit import ControlDiTRunner
 from .dit_cache import as_config
@@ -29,6 +30,9 @@ from .vae_encoder import VAEEncoder
 # latent frames of the previous chunk a streamed chunk pins as its prefix: the shipped sampler's "fixed_frames: 7 # 49 frames,
 # 13 latent, prefix_length=7" (cogvideox_2b_control_theia_interpolate_video_vq.yaml :213,231)
 STREAM_PREFIX_FRAMES = 7
+# frames per second of the model's clips (sampling_fps of the shipped config; infer_video writes its videos at it): where the
+# conform stage puts output frame k of a clip whose own rate is given, k / MODEL_FPS seconds
+MODEL_FPS = 8
 
 
 @dataclass
@@ -91,6 +95,28 @@ class LanDiffPipeline:
         self.timings = {}
         self.last_candidates = None       # generate_samples(keep=k): every candidate's ids and scores
         self.last_edit = None             # edit_video: what the last call ran (strength, start_step, steps_run, ...)
+        self.last_conform = None          # extend_video / edit_video(conform=...): ConformPlan.as_dict() of the last conformed clip
+        self.last_conform_frames = None   # ... and that clip at the model's frame, uint8 on the device (None: nothing was conformed)
+
+    def _conform(self, frames, conform, keep_mask=None):
+        """The conform stage of extend_video / edit_video: `frames` of any size / frame rate -> the 4T-3 frames of
+        8h x 8w the rest of the call takes, and a pixel keep_mask in the source clip's geometry with them; timed as "conform"."""
+        d = self.cfg.dit
+        if frames is None:
+            raise ValueError("conform= fits a clip given as frames=; a clip latent is already at the model's size")
+        if frames.dim() != 4 or frames.dtype != torch.uint8 or frames.shape[-1] != 3:
+            raise ValueError(f"clip frames must be uint8 [F, H, W, 3], got {frames.dtype} {tuple(frames.shape)}")
+        t0 = time.perf_counter()
+        plan = conform_plan(tuple(frames.shape), 4 * d.latent_frames - 3, 8 * d.latent_h, 8 * d.latent_w, conform)
+        if keep_mask is not None and tuple(keep_mask.shape) == tuple(frames.shape[:3]):
+            if keep_mask.dtype != torch.bool:
+                raise ValueError(f"keep_mask must be bool, got {keep_mask.dtype} {tuple(keep_mask.shape)}")
+            keep_mask = conform_mask(keep_mask, plan, self.dev)
+        frames = conform_clip(frames, plan, self.dev)
+        self.last_conform = plan.as_dict()
+        self.last_conform_frames = frames
+        self._t("conform", t0)
+        return frames, keep_mask
 
     def _t(self, name, t0):
         torch.cuda.current_stream(self.dev).synchronize()      # (the stage's own stream: an overlapped AR decode keeps running)
@@ -425,7 +451,7 @@ class LanDiffPipeline:
     def extend_video(self, inp: PromptInputs, n_chunks: int, *, frames: torch.Tensor | None = None,
                      clip_latent: torch.Tensor | None = None, clip_tokens: torch.Tensor | None = None,
                      tokens: torch.Tensor | None = None, prefix_frames: int = STREAM_PREFIX_FRAMES, want_float: bool = False, noises=None,
-                     latents_out: list | None = None):
+                     latents_out: list | None = None, conform: ConformConfig | None = None):
         """Continues a given clip: the clip is chunk 0 of a generate_stream run, and chunks 1..n_chunks are produced exactly as
         generate_stream(inp, n_chunks + 1, prefix_frames, ...) produces its chunks 1.. (seed inp.seed + k, semantic window
         [k new, k new + T), prefix = the last `prefix_frames` latents of the previous chunk, decode against the VAE caches).
@@ -443,7 +469,11 @@ class LanDiffPipeline:
         then come from the prompt, not from the clip.
 
         `noises[k-1]` is chunk k's initial noise.  Returns the NEW frames only, uint8 [n_chunks * 4 new, H, W, 3] (new =
-        T - prefix_frames), plus the fp32 video [3, frames, H, W] when want_float.  latents_out receives every new chunk's latent."""
+        T - prefix_frames), plus the fp32 video [3, frames, H, W] when want_float.  latents_out receives every new chunk's latent.
+
+        conform (a conform.ConformConfig with fit "cover" / "stretch"): `frames` may have any size and frame rate -- they go through
+        the conform stage first (timed as "conform"; what it did is self.last_conform, its output self.last_conform_frames) and
+        everything after sees the 4T-3 frames of 8h x 8w it made.  None or fit="exact": nothing is resized, as above."""
         d, lc = self.cfg.dit, self.cfg.llm
         T, new, n_seg = self.stream_plan(n_chunks + 1, prefix_frames)
         per_seg = self.cfg.tok.num_latent_tokens
@@ -453,6 +483,8 @@ class LanDiffPipeline:
             raise ValueError("extend_video takes the clip as exactly one of frames and clip_latent")
         if tokens is not None and clip_tokens is not None:
             raise ValueError("extend_video: tokens already holds every segment; clip_tokens goes with a decode from the prompt")
+        if conform is not None and conform.fit != "exact":
+            frames, _ = self._conform(frames, conform)
         if isinstance(clip_tokens, str):
             if clip_tokens != "from_frames":
                 raise ValueError(f"extend_video: clip_tokens must be a tensor or 'from_frames', got {clip_tokens!r}")
@@ -503,7 +535,8 @@ class LanDiffPipeline:
     def edit_video(self, inp: PromptInputs, *, frames: torch.Tensor | None = None, clip_latent: torch.Tensor | None = None,
                    strength: float = 1.0, keep_mask: torch.Tensor | None = None, tokens: torch.Tensor | None = None,
                    clip_tokens: str | None = None, known_noise: bool = True, composite: bool = True,
-                   noise: torch.Tensor | None = None, want_float: bool = False, latents_out: list | None = None):
+                   noise: torch.Tensor | None = None, want_float: bool = False, latents_out: list | None = None,
+                   conform: ConformConfig | None = None):
         """Changes a given clip, training-free: an SDEdit start (`strength` < 1: the sampler begins at step start =
         edit_start_step(num_steps, strength) from alpha[start] * clip latent + sigma[start] * noise and runs the remaining steps) and /
         or masked inpainting (`keep_mask`: the marked cells are held on the clip's own trajectory, the rest is generated) -- the
@@ -528,7 +561,12 @@ class LanDiffPipeline:
         generation, and the composite covers the frames it returns).  latents_out receives the sampled latent (fp32 values of the bf16 result);
         self.last_edit says what ran: strength, start_step, steps_run, alpha_start, sigma_start, kept_cells, total_cells,
         tokens_source.  With dit_cache / dit_guidance the reports have steps_run rows whose index begins at start_step;
-        attn_window's dense_steps counts executed steps."""
+        attn_window's dense_steps counts executed steps.
+
+        conform (a conform.ConformConfig with fit "cover" / "stretch"): `frames` of any size and frame rate, and a bool keep_mask
+        [F, Hs, Ws] in that clip's own geometry, go through the conform stage first (timed as "conform"; self.last_conform,
+        self.last_conform_frames): the call then equals edit_video(frames=conform_clip(frames, plan), keep_mask=conform_mask(
+        keep_mask, plan)) bit for bit, and the composite uses the conformed clip.  None or fit="exact": nothing is resized."""
         d = self.cfg.dit
         T, S = d.latent_frames, len(self.sampler.plan)
         shape = (1, T, d.in_channels, d.latent_h, d.latent_w)
@@ -543,6 +581,8 @@ class LanDiffPipeline:
         if clip_tokens == "from_frames" and (frames is None or self.theia is None):
             raise ValueError("edit_video(clip_tokens='from_frames') needs frames= and a pipeline built with theia=")
         start = edit_start_step(S, strength)
+        if conform is not None and conform.fit != "exact":
+            frames, keep_mask = self._conform(frames, conform, keep_mask)
         if frames is not None:
             frames = edit_clip(frames, self.cfg)
             if self.encoder is None:
