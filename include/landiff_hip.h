@@ -34,8 +34,8 @@ extern "C" {
  * ld_gemv_wide, ld_llm_decode_forward_wide and ld_llm_sample_advance_wide joined later, and so did ld_absdiff_sums,
  * ld_residual_sub, ld_residual_add, ld_attn_fwd_bf16_window, ld_attn_window_plan, ld_unpatchify_cfg_keep, ld_unpatchify_cond, ld_latent_pin and ld_mask_to_latent (additions do not change
  * the number: no existing signature moved).  16: ld_attn_route was added; ld_resize_u8 and ld_resize_mask_u8 joined later
- * (additions again). */
-#define LD_ABI_VERSION 16
+ * (additions again).  17: ld_clip_diff_u8 and ld_clip_ssim_u8 were added. */
+#define LD_ABI_VERSION 17
 
 int ld_version(void);
 const char* ld_last_error(void);
@@ -666,6 +666,33 @@ int ld_resize_u8(const uint8_t* src, uint8_t* dst, const int32_t* frame_idx, con
 int ld_resize_mask_u8(const uint8_t* src, uint8_t* dst, const int32_t* frame_idx, const int32_t* win_y, const int32_t* win_x,
                       int64_t Fs, int64_t Hs, int64_t Ws, int64_t n_out, int64_t Ho, int64_t Wo, int64_t y0, int64_t x0,
                       int64_t hc, int64_t wc, int32_t filter, void* stream);
+
+/* ---- clip comparison (ld_metrics.hip; landiff_amd/metrics.py) ----
+ * Two uint8 channels-last clips a, b [F][H][W][C], C 1 or 3 (the pipeline's output layout), and an optional keep-mask [F][H][W] u8
+ * (non-zero = counted; null: every pixel).  a and b may alias and need no alignment.  A frame holds fewer than 2^31 bytes.
+ *
+ * ld_clip_diff_u8: out int64 [F][C][5] = the number of counted pixels n, sum (a-b)^2, sum |a-b|, max |a-b| (0 when n is 0) and
+ * the number of counted pixels with a != b, per frame and channel: exact (64-bit sums; integer atomics).  Any H, W >= 1. */
+int ld_clip_diff_u8(const uint8_t* a, const uint8_t* b, const uint8_t* mask, int64_t* out, int64_t F, int64_t H, int64_t W,
+                    int64_t C, void* stream);
+
+/* ld_clip_ssim_u8: out double [F][C][2] = (sum of the SSIM map's counted values, their count) per frame and channel; the mean
+ * is the caller's division.  Pixel values are floats in [0, 255], L = 255, C1 = (0.01 L)^2, C2 = (0.03 L)^2.  `window`
+ * [LD_SSIM_TAPS] f32: the separable window's weights, an 11-tap Gaussian of sigma 1.5 normalised to sum 1, built by the caller in
+ * float64 and rounded once.  Valid region only: the map is (H-10) x (W-10), position (y, x) weighs pixels y .. y+10, x .. x+10;
+ * H or W < 11 is LD_ERR_INVALID.  With E the windowed mean: mu_x = E[x], var_x = E[x^2] - mu_x^2, cov = E[xy] - mu_x mu_y (biased),
+ * ssim = (2 mu_x mu_y + C1)(2 cov + C2) / ((mu_x^2 + mu_y^2 + C1)(var_x + var_y + C2)).  With a mask a position counts when its
+ * centre pixel (y+5, x+5) is kept; the window still reads every pixel under it.
+ * Arithmetic: fp32, every product and sum rounded on its own (no fma), taps added in ascending order, rows first then columns; the
+ * moments are taken of x - 128 and y - 128 (exact, and the variances do not change).  Symmetric in (a, b); exactly 1 where a == b.
+ * Map values are added in double: a tile of LD_SSIM_TILE_H x (LD_SSIM_TILE_ELEMS / C) positions by a fixed tree, a frame's tiles
+ * in a fixed order, through `workspace` (>= F * tiles_y * tiles_x * C * 2 doubles, checked against workspace_doubles) -- no
+ * floating-point atomics: the result is bit-repeatable and a frame's figures do not depend on the other frames of the call. */
+#define LD_SSIM_TAPS 11
+#define LD_SSIM_TILE_H 32
+#define LD_SSIM_TILE_ELEMS 48
+int ld_clip_ssim_u8(const uint8_t* a, const uint8_t* b, const uint8_t* mask, const float* window, double* out, double* workspace,
+                    int64_t workspace_doubles, int64_t F, int64_t H, int64_t W, int64_t C, void* stream);
 
 /* timestep_embedding (sgm/modules/diffusionmodules/util.py:207-233): t [B] f32 -> [B][dim] bf16 (cos || sin). */
 int ld_timestep_embedding(const float* t, void* out, int64_t B, int64_t dim, float max_period, void* stream);

@@ -7,7 +7,7 @@ import torch
 from landiff.diffusion.dif_infer import CogModelInferWrapper, VideoTask
 from landiff.llm.llm_cfg import build_llm
 from landiff.llm.llm_infer import ArModelInferWrapper, ARSampleCfg, CodeTask
-from landiff.utils import save_video_tensor
+from landiff.utils import cthw_to_numpy_images, save_video_tensor
 from landiff_amd.pipeline import STREAM_PREFIX_FRAMES
 
 
@@ -103,6 +103,14 @@ def parse_args(argv=None):
     parser.add_argument("--dit_cfg_cos", type=float, default=None, metavar="C",
                         help="CFG branch skipping: once the two branches' outputs reach a cosine of C (-1 < C <= 1) every later step "
                              "of the video evaluates the cond branch alone.  The effect on quality is not measured.")
+    parser.add_argument("--save_frames", action="store_true",
+                        help="Also write the exact uint8 frames of every video as <name>.frames.npy next to it (an mp4 is lossy: "
+                             "this file is what --compare_to takes).")
+    parser.add_argument("--compare_to", type=str, default=None, metavar="REF.npy",
+                        help="Compare every video written with the uint8 [F, H, W, 3] frames in this file (a --save_frames output "
+                             "of another run), on the GPU: PSNR, SSIM and exact difference counts per frame and for the clip, plus "
+                             "the frame-to-frame profile of both clips, to <name>_metrics.json.  The shapes must be equal; nothing "
+                             "is resized.")
     args = parser.parse_args(argv)
     args.dit_guidance = None
     if args.dit_cfg_tol is not None or args.dit_cfg_refresh is not None or args.dit_cfg_cos is not None:
@@ -334,6 +342,35 @@ def _write_conform_json(args, last_conform):
         json.dump(last_conform, f, indent=1, allow_nan=False)
 
 
+def _save_video(args, video, path: str, fps: int = 8):
+    """Every video this module writes goes through here: save_video_tensor, then --save_frames (<name>.frames.npy, the exact uint8
+    frames) and --compare_to (<name>_metrics.json: landiff_amd.metrics.compare_clips of the frames against the reference file's, and
+    temporal_profile of both clips).  Without the two flags it is save_video_tensor alone."""
+    save_video_tensor(video, path, fps=fps)
+    ref_path = getattr(args, "compare_to", None)
+    if not (getattr(args, "save_frames", False) or ref_path):
+        return
+    frames = video.cpu() if video.dtype == torch.uint8 else torch.from_numpy(cthw_to_numpy_images(video))
+    stem = Path(path).with_suffix("")
+    stem.parent.mkdir(parents=True, exist_ok=True)
+    if getattr(args, "save_frames", False):
+        np.save(f"{stem}.frames.npy", frames.numpy())
+    if ref_path:
+        from landiff_amd.metrics import compare_clips, temporal_profile, write_metrics_json
+        ref = load_clip(ref_path)
+        if tuple(ref.shape) != tuple(frames.shape):
+            raise ValueError(f"--compare_to {ref_path}: the reference is {tuple(ref.shape)}, the video written to {path} is "
+                             f"{tuple(frames.shape)}; the shapes must be equal (nothing is resized)")
+        dev = torch.device(f"cuda:{torch.cuda.current_device()}")
+        out_d, ref_d = frames.to(dev), ref.to(dev)
+        row = compare_clips(out_d, ref_d).as_dict()
+        row["reference"] = ref_path
+        row["temporal"] = {"video": temporal_profile(out_d) if frames.shape[0] > 1 else None,
+                           "reference": temporal_profile(ref_d) if frames.shape[0] > 1 else None}
+        write_metrics_json(f"{stem}_metrics.json", row)
+        print(f"compared with {ref_path}: {stem}_metrics.json")
+
+
 def infer_diffusion_samples(args, tokens, kept=None):
     """kept (--keep): the candidate indices to run, in rank order; None: every candidate."""
     model = _diffusion_model(args)
@@ -343,7 +380,7 @@ def infer_diffusion_samples(args, tokens, kept=None):
         task = model(VideoTask(save_file_name=f"{stem}.mp4", prompt=args.prompt, seed=seed, fps=8, semantic_token=row))
         _write_dit_cache_report(args, stem, model.dit_cache_report() if args.dit_cache is not None else None)
         _write_dit_guidance_report(args, stem, model.dit_guidance_report() if getattr(args, "dit_guidance", None) is not None else None)
-        save_video_tensor(task.result, task.save_file_name, fps=task.fps)
+        _save_video(args, task.result, task.save_file_name, fps=task.fps)
         print(f"save video to {task.save_file_name}")
 
 
@@ -355,7 +392,7 @@ def infer_diffusion(args, semantic_token):
     _write_dit_cache_report(args, args.save_file_name, model.dit_cache_report() if args.dit_cache is not None else None)
     _write_dit_guidance_report(args, args.save_file_name,
                                model.dit_guidance_report() if getattr(args, "dit_guidance", None) is not None else None)
-    save_video_tensor(task.result, task.save_file_name, fps=task.fps)
+    _save_video(args, task.result, task.save_file_name, fps=task.fps)
     print(f"save video to {task.save_file_name}")
 
 
@@ -426,7 +463,7 @@ def extend_diffusion(args):
     _write_dit_guidance_report(args, args.save_file_name, pipe.dit_guidance_reports)
     frames = torch.cat([clip, new.cpu()], dim=0)
     path = f"{args.save_file_name}.mp4"
-    save_video_tensor(frames, path, fps=8)
+    _save_video(args, frames, path, fps=8)
     print(f"save video to {path} ({frames.shape[0]} frames, {new.shape[0]} new)")
     return frames
 
@@ -461,7 +498,7 @@ def edit_diffusion(args):
     path = Path(f"{args.save_file_name}_edit.json")
     path.parent.mkdir(parents=True, exist_ok=True)
     write_edit_json(str(path), pipe.last_edit)
-    save_video_tensor(frames, f"{args.save_file_name}.mp4", fps=8)
+    _save_video(args, frames, f"{args.save_file_name}.mp4", fps=8)
     e = pipe.last_edit
     print(f"save video to {args.save_file_name}.mp4 (steps {e['start_step']}..{e['start_step'] + e['steps_run'] - 1}, "
           f"{e['kept_cells']} of {e['total_cells']} latent cells kept, tokens: {e['tokens_source']})")

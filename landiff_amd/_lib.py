@@ -44,7 +44,7 @@ class LlmLayer(Structure):
 
 
 _lib = None
-ABI_VERSION = 16         # LD_ABI_VERSION of include/landiff_hip.h that SIGNATURES below were written against
+ABI_VERSION = 17         # LD_ABI_VERSION of include/landiff_hip.h that SIGNATURES below were written against
 
 I64 = c_int64
 I32 = c_int32
@@ -119,6 +119,8 @@ SIGNATURES: dict[str, list] = {
     "ld_mask_to_latent": [P, P, I64, I64, I64, P],
     "ld_resize_u8": [P, P, P, P, P, I64, P, P, I64] + [I64] * 11 + [I32, P],
     "ld_resize_mask_u8": [P, P, P, P, P] + [I64] * 10 + [I32, P],
+    "ld_clip_diff_u8": [P, P, P, P, I64, I64, I64, I64, P],
+    "ld_clip_ssim_u8": [P, P, P, P, P, P, I64, I64, I64, I64, I64, P],
     "ld_timestep_embedding": [P, P, I64, I64, c_float, P],
     "ld_absdiff_sums": [P, P, I64, P, P, I32, P],
     "ld_residual_sub": [P, P, P, I64, P, P, P, P],

@@ -870,6 +870,70 @@ def resize_mask_u8(mask, out_hw, *, frame_idx=None, box=None, filter="bilinear",
     return out
 
 
+SSIM_TAPS, SSIM_SIGMA = 11, 1.5                      # LD_SSIM_TAPS of include/landiff_hip.h
+SSIM_TILE_H, SSIM_TILE_ELEMS = 32, 48               # LD_SSIM_TILE_H / LD_SSIM_TILE_ELEMS: they size the workspace, which the library checks
+
+
+def ssim_window() -> np.ndarray:
+    """The 11-tap Gaussian of sigma 1.5, normalised to sum 1 in float64 and rounded to fp32 once: the table ld_clip_ssim_u8 takes."""
+    x = np.arange(SSIM_TAPS, dtype=np.float64) - (SSIM_TAPS - 1) / 2
+    g = np.exp(-(x * x) / (2.0 * SSIM_SIGMA * SSIM_SIGMA))
+    return (g / g.sum()).astype(np.float32)
+
+
+_SSIM_WINDOWS: dict = {}
+
+
+def _clip_pair(name, a, b, mask):
+    """The shared argument checks of clip_diff_u8 / clip_ssim_u8 -> (a, b, mask as uint8 or None), contiguous."""
+    for t in (a, b):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise ValueError(f"{name}: the clips must be uint8 tensors, got {getattr(t, 'dtype', type(t))}")
+    if a.dim() != 4 or a.shape[3] not in (1, 3) or min(a.shape) < 1:
+        raise ValueError(f"{name}: a clip must be a non-empty [F, H, W, C] with C 1 or 3, got {tuple(a.shape)}")
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"{name}: the clips must have one shape, got {tuple(a.shape)} and {tuple(b.shape)} (nothing is resized)")
+    if a.device != b.device:
+        raise ValueError(f"{name}: the clips must be on one device, got {a.device} and {b.device}")
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.bool:
+            raise ValueError(f"{name}: the mask must be a bool tensor, got {getattr(mask, 'dtype', type(mask))}")
+        if tuple(mask.shape) != tuple(a.shape[:3]):
+            raise ValueError(f"{name}: the mask must be {tuple(a.shape[:3])} for clips {tuple(a.shape)}, got {tuple(mask.shape)}")
+        if mask.device != a.device:
+            raise ValueError(f"{name}: the mask must be on the clips' device {a.device}, got {mask.device}")
+        mask = mask.contiguous().view(torch.uint8)
+    return a.contiguous(), b.contiguous(), mask
+
+
+def clip_diff_u8(a, b, mask=None):
+    """Exact integer statistics of two uint8 clips [F, H, W, C] (C 1 or 3) -> int64 [F, C, 5]: the number of counted pixels, sum
+    (a-b)^2, sum |a-b|, max |a-b| and the number of pixels with a != b, per frame and channel, over the pixels the bool mask
+    [F, H, W] keeps (None: all).  Runs on the current stream; does not synchronise."""
+    a, b, mask = _clip_pair("clip_diff_u8", a, b, mask)
+    F, H, W, C = a.shape
+    out = torch.empty(F, C, 5, dtype=torch.int64, device=a.device)
+    check(_lib.load().ld_clip_diff_u8(_ptr(a), _ptr(b), _ptr(mask), _ptr(out), F, H, W, C, _stream()), "ld_clip_diff_u8")
+    return out
+
+
+def clip_ssim_u8(a, b, mask=None):
+    """SSIM of two uint8 clips [F, H, W, C] (C 1 or 3; H, W >= 11) -> float64 [F, C, 2]: the sum of the SSIM map's values and their
+    count per frame and channel (11-tap Gaussian window of sigma 1.5, valid region, L = 255: DESIGN 8.10), over the map positions
+    whose centre pixel the bool mask [F, H, W] keeps (None: all).  Runs on the current stream; does not synchronise."""
+    a, b, mask = _clip_pair("clip_ssim_u8", a, b, mask)
+    F, H, W, C = a.shape
+    tiles = -(-max(H - SSIM_TAPS + 1, 1) // SSIM_TILE_H) * -(-max(W - SSIM_TAPS + 1, 1) // (SSIM_TILE_ELEMS // C))
+    win = _SSIM_WINDOWS.get(a.device)
+    if win is None:                                 # uploaded once per device: a call then copies nothing from the host
+        win = _SSIM_WINDOWS[a.device] = torch.from_numpy(ssim_window()).to(a.device)
+    ws = torch.empty(F * tiles * C * 2, dtype=torch.float64, device=a.device)
+    out = torch.empty(F, C, 2, dtype=torch.float64, device=a.device)
+    check(_lib.load().ld_clip_ssim_u8(_ptr(a), _ptr(b), _ptr(mask), _ptr(win), _ptr(out), _ptr(ws), ws.numel(), F, H, W, C, _stream()),
+          "ld_clip_ssim_u8")
+    return out
+
+
 def timestep_embedding(t, out, max_period=10000.0):
     B, dim = out.shape
     check(_lib.load().ld_timestep_embedding(_ptr(t), _ptr(out), B, dim, float(max_period), _stream()),

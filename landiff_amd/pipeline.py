@@ -97,6 +97,7 @@ class LanDiffPipeline:
         self.last_edit = None             # edit_video: what the last call ran (strength, start_step, steps_run, ...)
         self.last_conform = None          # extend_video / edit_video(conform=...): ConformPlan.as_dict() of the last conformed clip
         self.last_conform_frames = None   # ... and that clip at the model's frame, uint8 on the device (None: nothing was conformed)
+        self.last_metrics = None          # compare: the ClipMetrics of the last comparison
 
     def _conform(self, frames, conform, keep_mask=None):
         """The conform stage of extend_video / edit_video: `frames` of any size / frame rate -> the 4T-3 frames of
@@ -117,6 +118,18 @@ class LanDiffPipeline:
         self.last_conform_frames = frames
         self._t("conform", t0)
         return frames, keep_mask
+
+    def compare(self, frames, reference, mask=None):
+        """PSNR, SSIM and exact difference counts of two uint8 clips [F, H, W, C] of one shape (landiff_amd.metrics.compare_clips,
+        DESIGN 8.10), e.g. what this pipeline returned with and without an opt-in switch; `mask` [F, H, W] bool keeps pixels.  The
+        tensors may live anywhere and are moved to the pipeline's device.  Timed as "metrics"; the result is also self.last_metrics."""
+        from .metrics import compare_clips
+        t0 = time.perf_counter()
+        to = lambda t: t.to(self.dev) if isinstance(t, torch.Tensor) else t
+        with torch.cuda.device(self.dev):
+            self.last_metrics = compare_clips(to(frames), to(reference), to(mask))
+        self._t("metrics", t0)
+        return self.last_metrics
 
     def _t(self, name, t0):
         torch.cuda.current_stream(self.dev).synchronize()      # (the stage's own stream: an overlapped AR decode keeps running)
