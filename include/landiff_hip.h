@@ -34,7 +34,7 @@ extern "C" {
  * ld_gemv_wide, ld_llm_decode_forward_wide and ld_llm_sample_advance_wide joined later, and so did ld_absdiff_sums,
  * ld_residual_sub, ld_residual_add, ld_attn_fwd_bf16_window, ld_attn_window_plan, ld_unpatchify_cfg_keep, ld_unpatchify_cond, ld_latent_pin and ld_mask_to_latent (additions do not change
  * the number: no existing signature moved).  16: ld_attn_route was added; ld_resize_u8 and ld_resize_mask_u8 joined later
- * (additions again).  17: ld_clip_diff_u8 and ld_clip_ssim_u8 were added. */
+ * (additions again).  17: ld_clip_diff_u8 and ld_clip_ssim_u8 were added; ld_retime_u8 joined later (an addition). */
 #define LD_ABI_VERSION 17
 
 int ld_version(void);
@@ -666,6 +666,22 @@ int ld_resize_u8(const uint8_t* src, uint8_t* dst, const int32_t* frame_idx, con
 int ld_resize_mask_u8(const uint8_t* src, uint8_t* dst, const int32_t* frame_idx, const int32_t* win_y, const int32_t* win_x,
                       int64_t Fs, int64_t Hs, int64_t Ws, int64_t n_out, int64_t Ho, int64_t Wo, int64_t y0, int64_t x0,
                       int64_t hc, int64_t wc, int32_t filter, void* stream);
+
+/* ---- the retime stage (ld_retime.hip; landiff_amd/retime.py) ----
+ * src u8 [F][H][W][C] -> dst u8 [n_out][H][W][C], C 1 or 3: output frame k lies at source position src_idx[k] + phase_p[k] / q
+ * (device int32 tables of n_out entries, 0 <= phase_p < q, src_idx + (phase_p > 0) <= F - 1: the caller checks them).  Phase 0
+ * copies src[src_idx[k]].  Otherwise, between A = src[i] and B = src[i + 1], every 8 x 8 output block is matched over the
+ * 16 x 16 luma window centred on it (Y = (77 R + 150 G + 29 B + 128) >> 8, or the channel itself; every coordinate clamped to the
+ * frame): for d = (dy, dx) in [-search, search]^2, per component a = -rhu(p d, q), b = d + a with rhu(n, m) =
+ * floor((2 n + m) / (2 m)); SAD(d) = sum |Y_A[y + a] - Y_B[y + b]|; the chosen d minimises (SAD + penalty (|dy| + |dx|),
+ * |dy| + |dx|, dy, dx); a chosen SAD above max_sad * 256 makes the block use d = (0, 0); then out = rhu((q - p) A[y + a] +
+ * p B[y + b], q) per pixel and channel.  Integer arithmetic only; two runs give the same bits.  mv (may be null): int16
+ * [n_out][ceil(H/8)][ceil(W/8)][2] = (dy, dx) after the fallback; sad (may be null): int32 [n_out][ceil(H/8)][ceil(W/8)] = the
+ * chosen candidate's SAD; both zero for phase-0 frames.  One launch; all element offsets are 64-bit.  LD_ERR_INVALID: null src,
+ * dst, src_idx or phase_p, C not 1 or 3, a size < 1, search outside 0..32, penalty or max_sad outside 0..255, q outside 1..65535. */
+int ld_retime_u8(const uint8_t* src, uint8_t* dst, const int32_t* src_idx, const int32_t* phase_p, int32_t q, int16_t* mv,
+                 int32_t* sad, int64_t F, int64_t n_out, int64_t H, int64_t W, int64_t C, int32_t search, int32_t penalty,
+                 int32_t max_sad, void* stream);
 
 /* ---- clip comparison (ld_metrics.hip; landiff_amd/metrics.py) ----
  * Two uint8 channels-last clips a, b [F][H][W][C], C 1 or 3 (the pipeline's output layout), and an optional keep-mask [F][H][W] u8

@@ -111,7 +111,27 @@ def parse_args(argv=None):
                              "of another run), on the GPU: PSNR, SSIM and exact difference counts per frame and for the clip, plus "
                              "the frame-to-frame profile of both clips, to <name>_metrics.json.  The shapes must be equal; nothing "
                              "is resized.")
+    parser.add_argument("--out_fps", type=int, default=None, metavar="N",
+                        help="Write every video at N frames per second (an integer >= 1) instead of the model's 8: the frames go "
+                             "through the retime stage on the GPU (in-between frames by block matching and motion-compensated "
+                             "blending in integer arithmetic; landiff_amd/retime.py).  Writes <name>_retime.json (the plan and the "
+                             "clip's motion profile).  --save_frames / --compare_to keep using the model's own 8 fps frames.  What "
+                             "block-matched interpolation looks like on a trained checkpoint's output is not measured.")
+    parser.add_argument("--out_search", type=int, default=None, metavar="R",
+                        help="With --out_fps: the block search range in pixels per axis, 0..32 (default 8, untuned; 0: a cross-fade).")
     args = parser.parse_args(argv)
+    args.retime = None
+    if args.out_fps is None:
+        if args.out_search is not None:
+            parser.error("--out_search goes with --out_fps")
+    else:
+        if args.out_fps < 1:
+            parser.error(f"--out_fps takes an integer >= 1, got {args.out_fps}")
+        from landiff_amd.retime import RetimeConfig
+        try:
+            args.retime = RetimeConfig(out_fps=args.out_fps, **({} if args.out_search is None else {"search": args.out_search}))
+        except ValueError as e:
+            parser.error(f"--out_search: {e}")
     args.dit_guidance = None
     if args.dit_cfg_tol is not None or args.dit_cfg_refresh is not None or args.dit_cfg_cos is not None:
         from landiff_amd.dit_guidance import REFUSE_STEP_CACHE, GuidanceSkipConfig
@@ -342,11 +362,34 @@ def _write_conform_json(args, last_conform):
         json.dump(last_conform, f, indent=1, allow_nan=False)
 
 
+def _save_retimed(video, path: str, fps: int, retime):
+    """--out_fps: the clip's frames at `fps` -> the retime stage on the current device -> save_video_tensor at the new rate, and
+    <name>_retime.json: the plan (source frame and phase of every frame written) and the motion profile of the model's frames."""
+    import json
+    from landiff_amd.retime import motion_profile, retime_clip, retime_plan
+    dev = torch.device(f"cuda:{torch.cuda.current_device()}")
+    frames = (video if video.dtype == torch.uint8 else torch.from_numpy(cthw_to_numpy_images(video))).to(dev).contiguous()
+    plan = retime_plan(frames.shape[0], retime, src_fps=fps)
+    save_video_tensor(retime_clip(frames, plan), path, fps=int(plan.out_fps))
+    report = {"plan": plan.as_dict(),
+              "motion": motion_profile(frames, retime.search, retime.penalty, retime.max_sad).as_dict() if frames.shape[0] > 1 else None}
+    stem = Path(path).with_suffix("")
+    with open(f"{stem}_retime.json", "w") as f:
+        json.dump(report, f, indent=1, allow_nan=False)
+    print(f"retimed {frames.shape[0]} frames at {fps} fps to {plan.n_out} at {int(plan.out_fps)} fps: {stem}_retime.json")
+
+
 def _save_video(args, video, path: str, fps: int = 8):
     """Every video this module writes goes through here: save_video_tensor, then --save_frames (<name>.frames.npy, the exact uint8
     frames) and --compare_to (<name>_metrics.json: landiff_amd.metrics.compare_clips of the frames against the reference file's, and
-    temporal_profile of both clips).  Without the two flags it is save_video_tensor alone."""
-    save_video_tensor(video, path, fps=fps)
+    temporal_profile of both clips).  Without the two flags it is save_video_tensor alone.  --out_fps N: what is written is the
+    clip retimed to N fps on the current device (landiff_amd.retime), with <name>_retime.json beside it; the two flags keep using the
+    model's own frames, and <name>.frames.npy is written after the video so that it holds them whatever the writer left there."""
+    retime = getattr(args, "retime", None)
+    if retime is None:
+        save_video_tensor(video, path, fps=fps)
+    else:
+        _save_retimed(video, path, fps, retime)
     ref_path = getattr(args, "compare_to", None)
     if not (getattr(args, "save_frames", False) or ref_path):
         return

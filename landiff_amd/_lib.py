@@ -119,6 +119,7 @@ SIGNATURES: dict[str, list] = {
     "ld_mask_to_latent": [P, P, I64, I64, I64, P],
     "ld_resize_u8": [P, P, P, P, P, I64, P, P, I64] + [I64] * 11 + [I32, P],
     "ld_resize_mask_u8": [P, P, P, P, P] + [I64] * 10 + [I32, P],
+    "ld_retime_u8": [P, P, P, P, I32, P, P, I64, I64, I64, I64, I64, I32, I32, I32, P],
     "ld_clip_diff_u8": [P, P, P, P, I64, I64, I64, I64, P],
     "ld_clip_ssim_u8": [P, P, P, P, P, P, I64, I64, I64, I64, I64, P],
     "ld_timestep_embedding": [P, P, I64, I64, c_float, P],

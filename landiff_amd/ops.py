@@ -870,6 +870,41 @@ def resize_mask_u8(mask, out_hw, *, frame_idx=None, box=None, filter="bilinear",
     return out
 
 
+def retime_u8(frames, src_idx, phase_p, q, search, penalty, max_sad, want_motion=False):
+    """uint8 channels-last frames [F, H, W, C] (C 1 or 3) -> uint8 [n_out, H, W, C]: output frame k lies at source position
+    src_idx[k] + phase_p[k] / q (host lists).  Phase 0 copies; every other frame is block-matched and motion-compensated between
+    its two neighbours in integer arithmetic (landiff_amd.retime states the parameters).  want_motion: also the
+    motion field int16 [n_out, ceil(H/8), ceil(W/8), 2] = (dy, dx) and the SAD int32 [n_out, ceil(H/8), ceil(W/8)].  One launch on the
+    current stream; does not synchronise."""
+    from .retime import MAX_Q, check_search
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
+        raise TypeError(f"retime_u8: the frames must be a uint8 tensor, got {getattr(frames, 'dtype', type(frames))}")
+    if frames.dim() != 4 or not frames.is_contiguous() or min(frames.shape) < 1 or frames.shape[3] not in (1, 3):
+        raise ValueError(f"retime_u8: the frames must be a non-empty contiguous [F, H, W, C] with C 1 or 3, got {tuple(frames.shape)}")
+    F, H, W, C = frames.shape
+    check_search(search, penalty, max_sad, "retime_u8")
+    if isinstance(q, bool) or int(q) != q or not 1 <= q <= MAX_Q:
+        raise ValueError(f"retime_u8: q must be an integer in 1..{MAX_Q}, got {q!r}")
+    idx = [int(v) for v in (src_idx.tolist() if hasattr(src_idx, "tolist") else src_idx)]
+    ph = [int(v) for v in (phase_p.tolist() if hasattr(phase_p, "tolist") else phase_p)]
+    if not idx or len(idx) != len(ph):
+        raise ValueError(f"retime_u8: src_idx and phase_p must be non-empty lists of one length, got {len(idx)} and {len(ph)}")
+    for k, (i, p) in enumerate(zip(idx, ph)):
+        if not 0 <= p < q:
+            raise ValueError(f"retime_u8: phase_p[{k}] = {p} is not in [0, {q})")
+        if i < 0 or i + (p > 0) > F - 1:
+            raise ValueError(f"retime_u8: output frame {k} at source position {i} + {p}/{q} leaves the clip's {F} frames")
+    n_out = len(idx)
+    tab = torch.tensor([idx, ph], dtype=torch.int32).to(frames.device)
+    out = torch.empty(n_out, H, W, C, dtype=torch.uint8, device=frames.device)
+    nby, nbx = -(-H // 8), -(-W // 8)
+    mv = torch.empty(n_out, nby, nbx, 2, dtype=torch.int16, device=frames.device) if want_motion else None
+    sad = torch.empty(n_out, nby, nbx, dtype=torch.int32, device=frames.device) if want_motion else None
+    check(_lib.load().ld_retime_u8(_ptr(frames), _ptr(out), _ptr(tab[0]), _ptr(tab[1]), int(q), _ptr(mv), _ptr(sad), F, n_out, H, W, C,
+                                   int(search), int(penalty), int(max_sad), _stream()), "ld_retime_u8")
+    return (out, mv, sad) if want_motion else out
+
+
 SSIM_TAPS, SSIM_SIGMA = 11, 1.5                      # LD_SSIM_TAPS of include/landiff_hip.h
 SSIM_TILE_H, SSIM_TILE_ELEMS = 32, 48               # LD_SSIM_TILE_H / LD_SSIM_TILE_ELEMS: they size the workspace, which the library checks
 

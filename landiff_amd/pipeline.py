@@ -98,6 +98,7 @@ class LanDiffPipeline:
         self.last_conform = None          # extend_video / edit_video(conform=...): ConformPlan.as_dict() of the last conformed clip
         self.last_conform_frames = None   # ... and that clip at the model's frame, uint8 on the device (None: nothing was conformed)
         self.last_metrics = None          # compare: the ClipMetrics of the last comparison
+        self.last_retime = None           # retime: RetimePlan.as_dict() of the last retimed clip
 
     def _conform(self, frames, conform, keep_mask=None):
         """The conform stage of extend_video / edit_video: `frames` of any size / frame rate -> the 4T-3 frames of
@@ -130,6 +131,22 @@ class LanDiffPipeline:
             self.last_metrics = compare_clips(to(frames), to(reference), to(mask))
         self._t("metrics", t0)
         return self.last_metrics
+
+    def retime(self, frames, cfg):
+        """uint8 frames [F, H, W, C] at the model's MODEL_FPS -> uint8 frames at cfg.out_fps on the pipeline's device (cfg: a
+        retime.RetimeConfig or a ready RetimePlan; landiff_amd.retime.retime_clip).  A function of the frames alone: it
+        takes what __call__, generate_stream, extend_video or edit_video returned.  Timed as "retime"; the plan is self.last_retime."""
+        from .retime import _as_plan, retime_clip
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.dtype != torch.uint8:
+            raise ValueError(f"retime: frames must be uint8 [F, H, W, C], got {getattr(frames, 'dtype', type(frames))} "
+                             f"{tuple(getattr(frames, 'shape', ()))}")
+        t0 = time.perf_counter()
+        plan = _as_plan(frames, cfg)
+        with torch.cuda.device(self.dev):
+            out = retime_clip(frames.to(self.dev).contiguous(), plan)
+        self.last_retime = plan.as_dict()
+        self._t("retime", t0)
+        return out
 
     def _t(self, name, t0):
         torch.cuda.current_stream(self.dev).synchronize()      # (the stage's own stream: an overlapped AR decode keeps running)
