@@ -553,7 +553,7 @@ int ld_llm_token_logprobs(const float* cond, int64_t cond_stride, const float* u
 int ld_llm_head_f32(const float* A, int64_t lda, const float* W, int64_t ldw, float* C, int64_t ldc, int64_t M, int64_t N,
                     int64_t K, void* stream);
 
-/* ---- normalisation kernels (ld_norm.hip) ---- */
+/* ---- normalisation kernels (ld_norm_layer.hip, ld_norm_qkv.hip, ld_norm_group.hip) ---- */
 
 /* LayerNorm over D (fp32 statistics) with optional AdaLN modulate `x*(1+scale)+shift` (bf16 ops) whose vectors are
  * picked per row: batch = row / rows_per_batch, region = text if (row % rows_per_batch) < text_len else image;
@@ -563,7 +563,7 @@ int ld_llm_head_f32(const float* A, int64_t lda, const float* W, int64_t ldw, fl
  * D % 8 == 0 and 0 < D <= 4096 (LD_ERR_INVALID otherwise).  NOT checked -- the rows are read and written in 16-byte pieces: x, out,
  * w, b and every modulation vector 16-byte aligned, hence ldx, ldo multiples of 8 elements for bf16 and 4 for f32, and mod_bstride and
  * the four offsets multiples of 8.  Columns [D, ldo) of out and rows >= `rows` are not written.
- * With mod, bf16 x and out, affine weights and D <= 2048 a two-rows-per-wave kernel runs (LD_LN_FAST=0, read once per process: never);
+ * With mod, bf16 x and out, affine weights and D <= 2048 a two-rows-per-wave kernel runs (LD_LN_FAST=0, a knob like every other -- read once per process, per call under LD_TUNING=1: never);
  * it stores the same bf16 values as the general kernel. */
 int ld_layernorm(const void* x, int64_t ldx, int32_t x_f32, const void* w, const void* b, void* out, int64_t ldo,
                  int32_t out_f32, int64_t rows, int64_t D, float eps, const void* mod, int64_t mod_bstride,

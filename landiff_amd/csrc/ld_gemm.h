@@ -3,6 +3,7 @@
 // family, which tiles); ld_gemm_2stage.hip, ld_gemm_8p.hip, ld_gemm_fp8.hip and ld_gemm_variants.hip hold the kernels and their launchers.
 #pragma once
 #include "ld_common.h"
+#include "ld_mx.h"
 #include <type_traits>
 
 namespace ldgemm {
@@ -167,7 +168,7 @@ struct NoHook { __device__ __forceinline__ void operator()() const {} };
 // of 4 rows per 32-row block -- as two 4-channel quads (sum, sum of squares), and after every second row block the 8 lanes that
 // hold the same columns meet in a fixed butterfly and lane 0..7 store the 64-row patch's four numbers.  Each (64-row unit, quad)
 // is written exactly once per launch, by a fixed sequence of fp32 additions: deterministic; ld_gn_stats_from_partials_kernel
-// (ld_norm.hip) sums the units in double in index order.  Replaces the separate read of the whole activation by
+// (ld_norm_group.hip) sums the units in double in index order.  Replaces the separate read of the whole activation by
 // ld_gn_stats_kernel for the VAE's GroupNorms, all of which normalise a convolution's output (cp_enc_dec.py:546-569, 745-782).
 template <int MI, int EPI, typename StageFn, typename Hook = NoHook, bool GN = false>
 __device__ __forceinline__ void gemm_epilogue_core(const GemmParams& p, StageFn&& stage_block, float* cw, int lane,
@@ -281,7 +282,7 @@ __device__ __forceinline__ void gemm_epilogue_core(const GemmParams& p, StageFn&
         }
         if constexpr (EPI == EPI_GELU_MX) {
           // the bf16 activation, quantised where it is produced: a 32-column MX block is the 8 columns of four adjacent
-          // lanes of the same row (lane bits 0-1); scale = smallest power of two >= amax / 448 (ld_quant_mxfp8_kernel)
+          // lanes of the same row (lane bits 0-1)
           float amax = 0.f;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {       // round to bf16 pairwise (one cvt_pk + two unpacks per pair)
@@ -289,23 +290,11 @@ __device__ __forceinline__ void gemm_epilogue_core(const GemmParams& p, StageFn&
             v[2 * e] = bf_lo(pk); v[2 * e + 1] = bf_hi(pk);
             amax = fmaxf(amax, fmaxf(fabsf(v[2 * e]), fabsf(v[2 * e + 1])));
           }
-          amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-          amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-          const uint32_t tb = __float_as_uint(amax * (1.0f / 448.0f));
-          int sb = (int)((tb >> 23) & 0xffu) + ((tb & 0x7fffffu) != 0u ? 1 : 0);
-          sb = amax > 0.f ? (sb < 1 ? 1 : (sb > 254 ? 254 : sb)) : 0;
-          const float inv = __uint_as_float((uint32_t)(254 - sb) << 23);      // exact power of two: |v| * inv <= 448, no clamp
+          float inv;
+          const int sb = mx_scale_byte(mx_block_amax(amax), inv);
           if (gm < p.M && col_ok) {
-            u32x2_t o;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-              unsigned w = 0;
-              w = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * h] * inv, v[4 * h + 1] * inv, w, false);
-              w = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * h + 2] * inv, v[4 * h + 3] * inv, w, true);
-              o[h] = w;
-            }
-            *(u32x2_t*)((unsigned char*)p.out + (long)gm * p.ldo + gn0) = o;
-            if ((lane & 3) == 0) p.mx_out[(((long)(gn0 >> 7)) * p.ld_mx_out + gm) * 4 + ((gn0 >> 5) & 3)] = (unsigned char)sb;
+            *(u32x2_t*)((unsigned char*)p.out + (long)gm * p.ldo + gn0) = mx_pack8(v, inv);
+            if ((lane & 3) == 0) p.mx_out[mx_scale_index(gm, gn0, p.ld_mx_out)] = (unsigned char)sb;
           }
         } else if (gm < p.M && col_ok) {
           u32x4_t ow;

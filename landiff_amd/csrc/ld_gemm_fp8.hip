@@ -287,9 +287,8 @@ int launch_f8(GemmParams p, hipStream_t stream) {
   return launch_2stage_f8(p, false, stream);
 }
 
-// MXFP8 quantiser (OCP Microscaling v1.0 container: e4m3 elements + one E8M0 scale per 32 consecutive K elements, byte =
-// exponent + 127), scale = smallest power of two >= amax / 448, elements = e4m3 cast of x / scale.  One wave per row; a block is the four
-// 8-element chunks of four adjacent lanes.
+// MXFP8 quantiser: elements = e4m3 cast of x / scale, one scale per 32 consecutive K elements by the block rule of ld_mx.h.
+// One wave per row; a block is the four 8-element chunks of four adjacent lanes.
 __global__ __launch_bounds__(256) void ld_quant_mxfp8_kernel(const bf16_t* x, long ldx, unsigned char* q, long ldq,
                                                              unsigned char* sc, long lds, int rows, int K) {
   const int lane = threadIdx.x & 63;
@@ -303,25 +302,11 @@ __global__ __launch_bounds__(256) void ld_quant_mxfp8_kernel(const bf16_t* x, lo
     float amax = 0.f;
 #pragma unroll
     for (int e = 0; e < 4; ++e) { f[2 * e] = bf_lo(v[e]); f[2 * e + 1] = bf_hi(v[e]); amax = fmaxf(amax, fmaxf(fabsf(f[2 * e]), fabsf(f[2 * e + 1]))); }
-    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-    amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-    // E8M0 byte sb: the smallest power of two 2^(sb - 127) >= amax / 448, so that no element saturates (the floor rule of
-    // the MX paper, 2^(floor(log2 amax) - 8), clips block maxima in [448, 512) x scale and measured 20-45 % more error)
-    const uint32_t tb = __float_as_uint(amax * (1.0f / 448.0f));
-    int sb = (int)((tb >> 23) & 0xffu) + ((tb & 0x7fffffu) != 0u ? 1 : 0);
-    sb = amax > 0.f ? (sb < 1 ? 1 : (sb > 254 ? 254 : sb)) : 0;
-    const float inv = __uint_as_float((uint32_t)(254 - sb) << 23);     // 2^(127 - sb)
+    float inv;
+    const int sb = mx_scale_byte(mx_block_amax(amax), inv);
     if (c < nchunk) {
-      u32x2_t o;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        unsigned w = 0;
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * h] * inv, f[4 * h + 1] * inv, w, false);       // |f| * inv <= 448 by construction
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(f[4 * h + 2] * inv, f[4 * h + 3] * inv, w, true);
-        o[h] = w;
-      }
-      *(u32x2_t*)(q + (long)r * ldq + c * 8) = o;
-      if ((c & 3) == 0) sc[((long)(c >> 4) * lds + r) * 4 + ((c >> 2) & 3)] = (unsigned char)sb;   // [K/128][lds rows][4]
+      *(u32x2_t*)(q + (long)r * ldq + c * 8) = mx_pack8(f, inv);
+      if ((c & 3) == 0) sc[mx_scale_index(r, c * 8, lds)] = (unsigned char)sb;
     }
   }
 }

@@ -714,7 +714,7 @@ def groupnorm_stats(x, stats, F, P, C, G):
     check(lib.ld_groupnorm_stats(_ptr(x), _ptr(stats), _ptr(ws), F, P, C, G, _stream()), "ld_groupnorm_stats")
 
 
-GN_FOLD_BLOCKS = 256      # ld_norm.hip: LD_GN_FOLD_BLOCKS
+GN_FOLD_BLOCKS = 256      # ld_norm_group.hip: LD_GN_FOLD_BLOCKS
 
 
 def groupnorm_stats_from_conv(part, stats, P, C, G):

@@ -1,4 +1,4 @@
-"""References and checkers for the direct tests of the layout (ld_elem.hip), norm-form / head-split (ld_norm.hip) and T5 (ld_t5.hip)
+"""References and checkers for the direct tests of the layout (ld_elem.hip), norm-form / head-split (ld_norm_*.hip) and T5 (ld_t5.hip)
 kernels: tests/test_gpu_elem_kernels.py, test_gpu_norm_forms.py, test_gpu_t5_kernels.py; tests/test_kernel_ref_host.py runs every
 checker here on the CPU against a correct restatement (must pass) and against deliberately wrong outputs (must fail).
 
@@ -275,7 +275,7 @@ def latent_to_cl_ref(x, T, C, H, W, Cpad, mul, src_tchw):
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# ld_norm.hip
+# ld_norm_layer.hip, ld_norm_qkv.hip, ld_norm_group.hip
 # ------------------------------------------------------------------------------------------------------------------------------
 def ln_inputs(rows, D, seed, x_f32=False):
     """tests/test_gpu_llm_kernels.py::_ln_inputs: a non-zero mean (E[x^2] - mean^2 would lose its digits); bf16 weights."""

@@ -253,6 +253,99 @@ def test_fused_mxfp8_producers(cuda):
     assert torch.equal(hs1, hs2) and torch.equal(hq1, hq2)
 
 
+# ---- ld_layernorm_mxfp8 by kernel: one row per wave (no mod, no weights, or LD_LN_FAST=0) and two rows per wave ----
+LNMX_ROWS, LNMX_FILL, LNMX_EPS = 9, 0xA5, 1e-5     # an odd row count: three waves of the third workgroup idle, one row pair half empty
+
+
+def _lnmx_raw(x, w, b, qbuf, ldq, sbuf, lds, rows, D, **mod):
+    """The C entry itself (ops.layernorm_mxfp8 fixes lds = rows and asserts the shapes the refusals are about)."""
+    from landiff_amd import _lib, ops
+    m = dict(dict(mod=None, mod_bstride=0, shift_img=0, scale_img=0, shift_txt=0, scale_txt=0, rows_per_batch=0, text_len=0), **mod)
+    _lib.check(_lib.load().ld_layernorm_mxfp8(ops._ptr(x), x.stride(0), ops._ptr(w), ops._ptr(b), ops._ptr(qbuf), ldq, ops._ptr(sbuf), lds,
+                                              rows, D, LNMX_EPS, ops._ptr(m["mod"]), m["mod_bstride"], m["shift_img"], m["scale_img"],
+                                              m["shift_txt"], m["scale_txt"], m["rows_per_batch"], m["text_len"], ops._stream()),
+               "ld_layernorm_mxfp8")
+
+
+def _lnmx_both(cuda, x, w, b, lds_extra=0, **mod):
+    """(fused, two-pass): q inside a pre-filled [rows + 2][D + 8] buffer (ldq = D + 8) and scales [D/128][rows + lds_extra][4], both
+    returned WHOLE, beside the same buffers holding ops.layernorm -> bf16 -> ops.quantize_mxfp8 and the fill everywhere else."""
+    from landiff_amd import ops
+    rows, D = x.shape
+    x, w, b = (None if t is None else t.to(cuda) for t in (x, w, b))
+    mod = {k: v.to(cuda) if torch.is_tensor(v) else v for k, v in mod.items()}
+    ln = ops.layernorm(x, w, b, torch.empty(rows, D, device=cuda, dtype=BF), LNMX_EPS, **mod)
+    q2, s2 = ops.quantize_mxfp8(ln)
+    fill = lambda *shape: torch.full(shape, LNMX_FILL, device=cuda, dtype=torch.uint8)
+    qb, sb, wq, ws = fill(rows + 2, D + 8), fill(D // 128, rows + lds_extra, 4), fill(rows + 2, D + 8), fill(D // 128, rows + lds_extra, 4)
+    wq[:rows, :D] = q2
+    ws[:, :rows] = s2
+    if lds_extra:
+        _lnmx_raw(x, w, b, qb, D + 8, sb, rows + lds_extra, rows, D, **mod)
+    else:
+        ops.layernorm_mxfp8(x, w, b, qb[:rows, :D], sb, LNMX_EPS, **mod)
+    torch.cuda.synchronize()
+    return (qb.cpu(), sb.cpu()), (wq.cpu(), ws.cpu())
+
+
+def _lnmx_inputs(D, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.randn(LNMX_ROWS, D, generator=g) * torch.logspace(-2, 2, D)[None, :] + 0.5).to(BF)      # block maxima over many binades
+    return x, (1 + 0.1 * torch.randn(D, generator=g)).to(BF), (0.1 * torch.randn(D, generator=g)).to(BF)
+
+
+@pytest.mark.parametrize("affine", [True, False], ids=["affine", "noweights"])
+@pytest.mark.parametrize("D", [128, 1024, 1920, 2048])
+def test_layernorm_mxfp8_one_row_kernel(cuda, D, affine):
+    """Without `mod` ld_layernorm_mxfp8 runs one row per wave: the same codes and scale bytes as ld_layernorm to bf16 followed by
+    ld_quantize_mxfp8, and nothing else of q's buffer written.  D gives 1, 2, 4 and 4 chunks per lane; at 1920 lanes 48-63 hold no fourth
+    chunk and still take part in the block-maximum shuffles."""
+    x, w, b = _lnmx_inputs(D, D + affine)
+    (q, s), (wq, ws) = _lnmx_both(cuda, x, w if affine else None, b if affine else None)
+    assert torch.equal(s, ws)
+    assert torch.equal(q, wq)
+
+
+def test_layernorm_mxfp8_scale_stride(cuda):
+    """lds = rows + 3 through the C entry: scale bytes of K-tile t at [t][row], rows >= `rows` of every tile left alone."""
+    x, w, b = _lnmx_inputs(1920, 5)
+    (q, s), (wq, ws) = _lnmx_both(cuda, x, w, b, lds_extra=3)
+    assert torch.equal(s, ws)
+    assert torch.equal(q, wq)
+
+
+@pytest.mark.parametrize("D", [128, 1920])
+def test_layernorm_mxfp8_modulate_one_and_two_rows_per_wave(cuda, monkeypatch, D):
+    """With `mod` (the 9-row case of test_gpu_norm_forms.py: batch and text / image boundaries inside row pairs): two rows per wave
+    by default, one row per wave under LD_LN_FAST=0 -- equal to each other and to the two-pass form."""
+    from test_gpu_norm_forms import MOD_RPB, MOD_TEXT, _mod_case
+    x, w, b, ada, offs, _, _ = _mod_case(D, 7 * D)
+    mod = dict(mod=ada, mod_bstride=ada.shape[1], rows_per_batch=MOD_RPB, text_len=MOD_TEXT, **offs)
+    two, want = _lnmx_both(cuda, x, w, b, **mod)
+    monkeypatch.setenv("LD_LN_FAST", "0")
+    one, want1 = _lnmx_both(cuda, x, w, b, **mod)
+    for got, ref in ((two, want), (one, want1), (one, two)):
+        assert torch.equal(got[1], ref[1])
+        assert torch.equal(got[0], ref[0])
+
+
+@pytest.mark.parametrize("what", ["D_64", "D_2176", "ldq_not_8k", "lds_below_rows", "w_without_b"])
+def test_layernorm_mxfp8_refusals(cuda, what):
+    from landiff_amd._lib import LandiffHipError
+    D = {"D_64": 64, "D_2176": 2176}.get(what, 256)
+    rows = 4
+    x = torch.ones(rows, D, dtype=BF, device=cuda)
+    w = torch.ones(D, dtype=BF, device=cuda)
+    ldq = D + (4 if what == "ldq_not_8k" else 8)
+    lds = rows - 1 if what == "lds_below_rows" else rows
+    qb = torch.full((rows, D + 8), LNMX_FILL, device=cuda, dtype=torch.uint8)
+    sb = torch.full((D // 128 + 1, rows, 4), LNMX_FILL, device=cuda, dtype=torch.uint8)
+    with pytest.raises(LandiffHipError):
+        _lnmx_raw(x, w, None if what == "w_without_b" else w, qb, ldq, sb, lds, rows, D)
+    torch.cuda.synchronize()
+    assert bool((qb == LNMX_FILL).all()) and bool((sb == LNMX_FILL).all())
+
+
 def test_streaming_with_mxfp8_linears_tiny(cuda):
     """BASELINE configs[4] in miniature: the chunked long-video driver (one multi-segment AR decode overlapped with the chunk
     loop, latent prefix pinned per later chunk, VAE conv caches resident in HBM) with the DiT's four large linears on MXFP8

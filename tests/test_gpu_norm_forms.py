@@ -1,10 +1,11 @@
-"""The forms of ld_norm.hip that no direct test reached: the general LayerNorm kernel (fp32 in / out, no weights, D above 2048, with
-modulation where the two-rows-per-wave kernel does not take the call), that kernel against the two-rows-per-wave one, ld_qkv_split in
-its three modes, the GroupNorm statistics at 2 / 4 / 8 / 64 channels per group and both GroupNorm-apply kernels -- each against a plain
+"""The forms of ld_norm_layer.hip, ld_norm_qkv.hip and ld_norm_group.hip that no direct test reached: the general LayerNorm kernel
+(fp32 in / out, no weights, D above 2048, with modulation where the two-rows-per-wave kernel does not take the call), that kernel
+against the two-rows-per-wave one, ld_qkv_split in its three modes, the GroupNorm statistics at 2 / 4 / 8 / 64 channels per group and both GroupNorm-apply kernels -- each against a plain
 float64 reference (tests/kernel_ref.py) through landiff_amd.ops, outputs inside NaN sentinels.
 
-The kernel choice is made through the arguments (LD_LN_FAST and LD_GN_ROWS are read once per process): fp32 in or out, no weights or
-D > 2048 reach the general LayerNorm kernel; a channel count with 256 % (C / 8) != 0 reaches the flat GroupNorm kernel.
+The kernel choice is made through the arguments: fp32 in or out, no weights or D > 2048 reach the general LayerNorm kernel; a channel
+count with 256 % (C / 8) != 0 reaches the flat GroupNorm kernel.  LD_LN_FAST=0 and LD_GN_ROWS=0 choose the same kernels for any
+arguments; they are knobs like every other (re-read per call under LD_TUNING=1, conftest), and one test uses the first.
 
 Classes (kernel_ref's docstring): B for LayerNorm without modulation, QK-LayerNorm and RoPE; C for LayerNorm + modulate and GroupNorm +
 SpatialNorm + swish; A for the plain split, V in every mode and all padding.
@@ -116,10 +117,11 @@ def test_layernorm_modulate_on_the_general_kernel(cuda, D, out_f32):
 
 
 @pytest.mark.parametrize("D", [128, 768, 1920])
-def test_layernorm_mod_kernel_equals_general_kernel(cuda, D):
+def test_layernorm_mod_kernel_equals_general_kernel(cuda, monkeypatch, D):
     """The two-rows-per-wave kernel (bf16 out) against the general kernel (the same call with fp32 output, which stores the
-    bf16-rounded values): "the same operations at the same roundings" (ld_norm.hip) -- bit equality, over an odd row count with region and
-    batch boundaries inside row pairs.  The two-rows-per-wave kernel is also held to the class-C chain on its own."""
+    bf16-rounded values, and the same bf16-out call under LD_LN_FAST=0): "the same operations at the same roundings"
+    (ld_norm_layer.hip) -- bit equality, over an odd row count with region and batch boundaries inside row pairs.  The
+    two-rows-per-wave kernel is also held to the class-C chain on its own."""
     x, w, b, ada, offs, shift, scale = _mod_case(D, 3 * D)
     ref, bound = kr.ln_modulate_ref(x, w, b, LN_EPS, shift, scale)
     fast = _mod_run(cuda, x, w, b, ada, offs, BF)
@@ -129,6 +131,8 @@ def test_layernorm_mod_kernel_equals_general_kernel(cuda, D):
     print(f"two-rows-per-wave vs general kernel, D={D}: {int(differ.sum())} of {differ.numel()} elements differ, largest difference "
           f"{(fast.float() - general).abs().max().item():.3e}")
     kr.check_bits(fast.float(), general, f"two-rows-per-wave kernel vs general kernel, D={D}")
+    monkeypatch.setenv("LD_LN_FAST", "0")
+    kr.check_bits(_mod_run(cuda, x, w, b, ada, offs, BF), fast, f"general kernel, bf16 out (LD_LN_FAST=0) vs two-rows-per-wave kernel, D={D}")
 
 
 # ---- head split ---------------------------------------------------------------------------------------------------------------

@@ -25,5 +25,8 @@ for name, N, K in (("qkv", 5760, 1920), ("proj", 1920, 1920), ("fc1", 7680, 1920
     m8, ms = ops.quantize_mxfp8(a); v8, vs = ops.quantize_mxfp8(w)
     tm = t(lambda: ops.gemm_mxfp8(m8, ms, v8, vs, out=out, bias=bias))
     tmq = t(lambda: ops.quantize_mxfp8(a, m8, ms))
+    # bias + GELU with MXFP8 output (the DiT's fc1 form: the next GEMM's operand is quantised in the epilogue)
+    o8 = torch.empty(M, N, device=dev, dtype=torch.uint8); os8 = torch.empty(N // 128, M, 4, device=dev, dtype=torch.uint8)
+    tmo = t(lambda: ops.gemm_mxfp8(m8, ms, v8, vs, out=o8, out_scales=os8, bias=bias, act="gelu_tanh"))
     print(f"{name:5s} M={M} N={N} K={K}: bf16 {t16*1e3:7.1f} us ({fl/t16/1e9:6.0f} TF)   fp8 row {t8*1e3:7.1f} us ({fl/t8/1e9:6.0f} TF) + quantise {tq*1e3:6.1f} us"
-          f"   MXFP8 {tm*1e3:7.1f} us ({fl/tm/1e9:6.0f} TF) + quantise {tmq*1e3:6.1f} us")
+          f"   MXFP8 {tm*1e3:7.1f} us ({fl/tm/1e9:6.0f} TF) + quantise {tmq*1e3:6.1f} us   MXFP8, GELU -> MXFP8 out {tmo*1e3:7.1f} us")
