@@ -2,7 +2,9 @@
 // problem gets, every LD_ATTN_* knob), the executor and the entry points.  The pipelined kernels and their launchers:
 // ld_attn_q64.hip (64-row wave tile: dense, frame-window and dynamic forms; shared body ld_attn_q64_body.h), ld_attn_q64_exact.hip
 // (two-pass exact softmax), ld_attn_p16.hip (32-row wave tile) and, in the variants build only, ld_attn_pipe.hip (round-1 pipeline)
-// and ld_attn_q128.hip (128-row tile).  A launcher takes its knob values as arguments -- it reads no environment -- and reports
+// and ld_attn_q128.hip (128-row tile).  What the pipelined kernels share on the device -- LDS layout, the ring's LDS-DMA plan,
+// fragment offsets, key indices, the window test and vote, the DMA drain, the O epilogue -- is stated once in ld_attn_dev.h; their
+// launchers share attn_launch below.  A launcher takes its knob values as arguments -- it reads no environment -- and reports
 // what it launched through an AttnRan; attn_run (ld_attn.hip) is the one writer of what ld_attn_last_kernel / _fallbacks answer.
 #pragma once
 #include "ld_common.h"
@@ -83,10 +85,23 @@ inline void attn_window_clamp(int64_t N, int64_t P, int64_t* G, int64_t* w) {
   if (*w > frames) *w = frames;
 }
 
-__device__ __forceinline__ void glds16(const bf16_t* g, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(
-      (const __attribute__((address_space(1))) void*)g,
-      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+// What a launch without a fallback count reports.  name / name_safe: the kernel and the kernel "[safe pass forced]" (ATTN_KNAMES
+// writes the pair, so the suffix rule stands here alone); a forced safe pass has no window to leave (fb_kind 0), a fast pass of a
+// static launch has one and keeps no count (fb_kind 2).
+#define ATTN_KNAMES(kernel) #kernel, #kernel "[safe pass forced]"
+inline AttnRan attn_ran_static(const char* name, const char* name_safe, int safe) {
+  return AttnRan{safe ? name_safe : name, nullptr, safe ? 0 : 2};
+}
+
+// The launch of a pipelined kernel: its dynamic shared memory (cache: the kernel's own `static thread_local` LdSmemCache), what it
+// reports, the launch.  *ran is written only once nothing before the launch can fail any more.
+template <class Kernel, class... Args>
+int attn_launch(Kernel kernel, LdSmemCache* cache, size_t smem, dim3 grid, dim3 block, hipStream_t st, AttnRan* ran, const AttnRan& what_ran,
+                const char* what, Args... args) {
+  if (int rc = ld_ensure_dyn_smem((const void*)kernel, smem, cache)) return rc;
+  *ran = what_ran;
+  hipLaunchKernelGGL(kernel, grid, block, smem, st, args...);
+  return ld_check_launch(what);
 }
 
 __device__ __forceinline__ float lane32_max(float x) {
@@ -97,14 +112,6 @@ __device__ __forceinline__ float lane32_max(float x) {
 __device__ __forceinline__ float lane32_sum(float x) {
   auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// v_max3_f32 by hand: plain fmaxf on MFMA outputs makes hipcc insert a canonicalising v_max per operand.  CAUTION: an asm statement
-// gets no hazard padding -- when the operands are MFMA results the caller provides the MFMA -> VALU wait states (ld_attn.hip)
-__device__ __forceinline__ float max3f(float a, float b, float c) {
-  float r;
-  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-  return r;
 }
 
 __device__ __forceinline__ int swap23(int i) {

@@ -34,6 +34,20 @@
 
 namespace {
 
+__device__ __forceinline__ void glds16(const bf16_t* g, char* lds_wave_base) {
+  __builtin_amdgcn_global_load_lds(
+      (const __attribute__((address_space(1))) void*)g,
+      (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+}
+
+// v_max3_f32 by hand: plain fmaxf on MFMA outputs makes hipcc insert a canonicalising v_max per operand.  CAUTION: an asm statement
+// gets no hazard padding -- when the operands are MFMA results the caller provides the MFMA -> VALU wait states (below)
+__device__ __forceinline__ float max3f(float a, float b, float c) {
+  float r;
+  asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+
 template <bool MFMASUM, int WPS>   // WPS = waves/SIMD of the register budget
 __global__ __launch_bounds__(256, WPS) void ld_attn_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];   // 2 stages of one key tile (K 8 KB + V^T 8 KB) + 64 B

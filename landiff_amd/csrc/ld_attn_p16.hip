@@ -25,6 +25,7 @@
 // chunk kg*4 + (l >> 4): the usual f = (row >> 1) & 7 is conflict-free for the four 16-lane groups of a ds_read_b128.  The
 // permuted K rows are not, with that f; f_K(row) = bit 1 | bits 4:3 << 1 is (each 16-lane group then covers all 16 slots).
 #include "ld_attn.h"
+#include "ld_attn_dev.h"
 
 namespace {
 
@@ -34,8 +35,6 @@ namespace {
 #ifndef LD_ATTN_ABLATE
 #define LD_ATTN_ABLATE 0
 #endif
-
-__device__ __forceinline__ int swz_k(int r) { return ((r >> 1) & 1) | (((r >> 3) & 3) << 1); }
 
 // MSUM: softmax denominators from the matrix pipe -- l[qb] += ones(16 x 32) . P[kg][qb], 4 more MFMAs per tile (+12.5 %)
 // instead of 32 v_add_f32: the kernel's cycle count follows its VALU-class issue count (SQ counters, profiles/
@@ -47,45 +46,25 @@ __device__ __forceinline__ int swz_k(int r) { return ((r >> 1) & 1) | (((r >> 3)
 // even with the matrix pipe 83 % busy.)
 template <int NW, bool MSUM>     // NW: waves per workgroup (32 query rows each)
 __device__ __forceinline__ void attn_p16_body(const AttnParams& p, int force_safe, char* smem) {   // smem: K slots 0..3 | V^T slots 0..3 | NW flag words
-  constexpr int VBASE = 4 * KTILE_BYTES;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l16 = lane & 15, h4 = lane >> 4;
-  constexpr int QBW = NW * 32;                    // query rows per workgroup
-  constexpr int NPW = 16 / NW;                    // LDS-DMA pieces per wave and tile (K: 8 pieces, V^T: 8 pieces)
-  const int nqb = (p.Npad + QBW - 1) / QBW;
   const int n = (p.Nk + KT - 1) / KT;             // >= 6 (launcher)
 
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = bid / nqb, qblk = bid - bh * nqb;
-  const int b = bh / p.H, h = bh - b * p.H;
-  const bf16_t* Qb = p.Q + (long)bh * p.Npad * D;
-  const bf16_t* Kb = p.K + (long)bh * p.Npad * D;
-  const bf16_t* Vb = p.Vt + (long)bh * D * p.Npad;
-  const int q0 = qblk * QBW + wave * 32;
-  if (qblk * QBW >= p.Nq) return;
+  const AttnBlock blk = attn_block(p, xcd_remap(blockIdx.x, gridDim.x), NW * 32, 32, wave);
+  const int q0 = blk.q0;
+  if (blk.past) return;
 
-  // Q^T fragments (B operand): rows q0 + qb*16 + l16, d = ks*32 + h4*8 .. + 8, pre-multiplied by scale * log2(e)
-  bf16x8_t qf[2][2];
-#pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    const int q = q0 + qb * 16 + l16;
-    const bf16_t* qrow = Qb + (long)(q < p.Npad ? q : p.Npad - 1) * D + h4 * 8;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const u32x4_t raw = *(const u32x4_t*)(qrow + ks * 32);
-      u32x4_t sc;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) sc[e] = pack_bf16x2(bf_lo(raw[e]) * p.c, bf_hi(raw[e]) * p.c);
-      qf[qb][ks] = __builtin_bit_cast(bf16x8_t, sc);
-    }
-  }
+  bf16x8_t qf[2][2];                               // Q^T fragments [qb][ks]
+  attn_load_qt<2>(p, blk.Qb, q0, l16, h4, [&](int qb, int ks, const u32x4_t& w) { qf[qb][ks] = __builtin_bit_cast(bf16x8_t, w); });
 
-  // LDS-DMA: the first half of the waves brings K tiles (rows = keys), the second half V^T tiles (rows = d)
+  // LDS-DMA: the first half of the waves brings K tiles (rows = keys), the second half V^T tiles (rows = d).  The plan of AttnDma
+  // (ld_attn_dev.h) restated in place: set up by any function -- struct, references or values -- ld_attn_p16_w4_kernel spills 52 more bytes.
+  constexpr int NPW = 16 / NW;                    // LDS-DMA pieces per wave and tile (K: 8 pieces, V^T: 8 pieces)
   const bool kwave = wave < NW / 2;
   const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(kwave ? Kb : Vb), 0, 0x7fffffff, 0x00020000);   // raw buffer, wave-uniform
+      __builtin_amdgcn_make_buffer_rsrc((void*)(kwave ? blk.Kb : blk.Vb), 0, 0x7fffffff, 0x00020000);   // raw buffer, wave-uniform
   const int tstride = kwave ? KT * D * 2 : KT * 2;               // bytes per tile step in the source
   const int rstride = kwave ? D : p.Npad;
   uint32_t goff[NPW];
@@ -94,9 +73,9 @@ __device__ __forceinline__ void attn_p16_body(const AttnParams& p, int force_saf
   for (int i = 0; i < NPW; ++i) {
     const int piece = (wave % (NW / 2)) * NPW + i;
     const int r = piece * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ (kwave ? swz_k(r) : ((r >> 1) & 7));
+    const int chunk = (lane & 7) ^ (kwave ? attn_swz_k(r) : attn_swz_v(r));
     goff[i] = (uint32_t)(r * rstride + chunk * 8) * 2u;
-    ldsoff[i] = (kwave ? 0 : VBASE) + piece * 1024;
+    ldsoff[i] = (kwave ? 0 : ATTN_VBASE) + piece * 1024;
   }
   auto dma_piece = [&](int i, int slot, int t) {
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(smem + slot * KTILE_BYTES + ldsoff[i]),
@@ -107,17 +86,8 @@ __device__ __forceinline__ void attn_p16_body(const AttnParams& p, int force_saf
     for (int i = 0; i < NPW; ++i) dma_piece(i, slot, t);
   };
 
-  // fragment read offsets: K block kb = 2*kg + b, k-step ks: kofs[ks] + kg*4096 + b*512;  V^T block db, key group kg: vofs[kg] + db*2048
-  int kofs[2], vofs[2];
-  {
-    const int key = 8 * (l16 >> 2) + (l16 & 3);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int c = ks * 4 + h4;
-      kofs[ks] = key * 128 + ((c ^ swz_k(key)) << 4);
-      vofs[ks] = VBASE + l16 * 128 + ((c ^ ((l16 >> 1) & 7)) << 4);
-    }
-  }
+  int kofs[2], vofs[2];                            // fragment read offsets (K block kb = 2*kg + b)
+  attn_frag_offsets(l16, h4, 0, ATTN_VBASE, kofs, vofs);
 
   f32x4_t o[4][2];
   using T = std::true_type; using F = std::false_type;
@@ -128,7 +98,7 @@ __device__ __forceinline__ void attn_p16_body(const AttnParams& p, int force_saf
   auto mask_tail = [&](f32x4_t (&s)[4][2], int t) {
 #pragma unroll
     for (int kb = 0; kb < 4; ++kb) {
-      const int key0 = t * KT + (kb >> 1) * 32 + h4 * 8 + (kb & 1) * 4;
+      const int key0 = attn_key0(2 * t + (kb >> 1), kb & 1, h4);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         if (key0 + r >= p.Nk) { s[kb][0][r] = NEG_BIG; s[kb][1][r] = NEG_BIG; }
@@ -428,42 +398,12 @@ __device__ __forceinline__ void attn_p16_body(const AttnParams& p, int force_saf
   bool redo = force_safe != 0;
   if (!redo) {
     fast_pass();
-    // 2^-80 <= l <= 2^110 (NaN fails): see the header comment of ld_attn_pipe.hip
-    bool bad = false;
-#pragma unroll
-    for (int qb = 0; qb < 2; ++qb)
-      bad = bad || (!(ltot[qb] >= 8.2718061e-25f && ltot[qb] <= 1.2980742e33f) && (q0 + qb * 16 + l16 < p.Nq));
-    int* flags = (int*)(smem + 8 * KTILE_BYTES);
-    const bool wbad = __any(bad);
-    if (lane == 0) flags[wave] = wbad ? 1 : 0;
-    __syncthreads();
-    redo = false;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) redo = redo || flags[w] != 0;
-    __syncthreads();
+    redo = attn_window_vote<NW, 2>(smem, ltot, q0 + l16, p.Nq, lane, wave);
   }
   if (redo) safe_pass();
-  // Every LDS-DMA of this workgroup has LANDED before the workgroup ends: the loops above run ahead of the tiles they consume;
-  // a wave that ended with buffer_load ... lds in flight would let the data
-  // arrive in LDS that may by then belong to the next workgroup on this CU.  (Round 5: added while hunting the co-residency bug
-  // that turned out to be the packed-fp32 one -- csrc/build.sh -- and kept: it measures at 0 us of a 3.6 ms launch.)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-
+  attn_dma_drain();
 #pragma unroll
-  for (int qb = 0; qb < 2; ++qb) {
-    const int q = q0 + qb * 16 + l16;
-    const float inv = ltot[qb] > 0.f ? 1.0f / ltot[qb] : 0.f;
-    if (q < p.Nq) {
-      bf16_t* orow = p.O + (long)b * p.o_bs + (long)q * p.o_rs + h * D + h4 * 4;
-#pragma unroll
-      for (int db = 0; db < 4; ++db) {
-        u32x2_t w2;
-        w2[0] = pack_bf16x2(o[db][qb][0] * inv, o[db][qb][1] * inv);
-        w2[1] = pack_bf16x2(o[db][qb][2] * inv, o[db][qb][3] * inv);
-        *(u32x2_t*)(orow + db * 16) = w2;
-      }
-    }
-  }
+  for (int qb = 0; qb < 2; ++qb) attn_store_o(p, blk.b, blk.h, q0 + qb * 16 + l16, h4, ltot[qb], o[0][qb], o[1][qb], o[2][qb], o[3][qb]);
 }
 #undef FENCE
 
@@ -484,23 +424,13 @@ __global__ __launch_bounds__(256, 2) void ld_attn_p16a_w4_kernel(AttnParams p, i
 
 // msum = 0: the row sums by v_add_f32 (4-wave workgroups only); nw = 8: 8-wave workgroups.  fb_kind 2: a fast pass with a window, no count kept.
 int ld_attn_p16_launch(const AttnParams& p, hipStream_t st, int safe, int msum, int nw, AttnRan* ran) {
-  constexpr int SMEM = 8 * KTILE_BYTES + 64;
   static thread_local LdSmemCache c4{}, c4a{}, c8{};
-  if (nw == 8 && msum) {
-    if (int rc = ld_ensure_dyn_smem((const void*)ld_attn_p16_w8_kernel, SMEM, &c8)) return rc;
-    *ran = {safe ? "ld_attn_p16_w8_kernel[safe pass forced]" : "ld_attn_p16_w8_kernel", nullptr, safe ? 0 : 2};
-    hipLaunchKernelGGL(ld_attn_p16_w8_kernel, dim3((unsigned)((long)p.B * p.H * ((p.Npad + 255) / 256))), dim3(512), SMEM, st, p, safe);
-    return ld_check_launch("ld_attn_fwd_bf16(p16 w8)");
-  }
-  if (int rc = msum ? ld_ensure_dyn_smem((const void*)ld_attn_p16_w4_kernel, SMEM, &c4)
-                    : ld_ensure_dyn_smem((const void*)ld_attn_p16a_w4_kernel, SMEM, &c4a)) return rc;
+  if (nw == 8 && msum)
+    return attn_launch(ld_attn_p16_w8_kernel, &c8, ATTN_SMEM_BYTES, dim3((unsigned)((long)p.B * p.H * ((p.Npad + 255) / 256))), dim3(512), st, ran,
+                       attn_ran_static(ATTN_KNAMES(ld_attn_p16_w8_kernel), safe), "ld_attn_fwd_bf16(p16 w8)", p, safe);
   dim3 grid((unsigned)((long)p.B * p.H * ((p.Npad + 127) / 128)));
-  if (msum) {
-    *ran = {safe ? "ld_attn_p16_w4_kernel[safe pass forced]" : "ld_attn_p16_w4_kernel", nullptr, safe ? 0 : 2};
-    hipLaunchKernelGGL(ld_attn_p16_w4_kernel, grid, dim3(256), SMEM, st, p, safe);
-  } else {
-    *ran = {safe ? "ld_attn_p16a_w4_kernel[safe pass forced]" : "ld_attn_p16a_w4_kernel", nullptr, safe ? 0 : 2};
-    hipLaunchKernelGGL(ld_attn_p16a_w4_kernel, grid, dim3(256), SMEM, st, p, safe);
-  }
-  return ld_check_launch("ld_attn_fwd_bf16(p16)");
+  if (msum) return attn_launch(ld_attn_p16_w4_kernel, &c4, ATTN_SMEM_BYTES, grid, dim3(256), st, ran,
+                               attn_ran_static(ATTN_KNAMES(ld_attn_p16_w4_kernel), safe), "ld_attn_fwd_bf16(p16)", p, safe);
+  return attn_launch(ld_attn_p16a_w4_kernel, &c4a, ATTN_SMEM_BYTES, grid, dim3(256), st, ran,
+                     attn_ran_static(ATTN_KNAMES(ld_attn_p16a_w4_kernel), safe), "ld_attn_fwd_bf16(p16)", p, safe);
 }

@@ -35,6 +35,7 @@
 // before any wave refills those slots.  The DMA itself is buffer_load ... lds with the tile offset in an SGPR (soffset)
 // and a loop-invariant per-lane voffset: no VALU address arithmetic in the loop.
 #include "ld_attn.h"
+#include "ld_attn_dev.h"
 
 namespace {
 
@@ -42,28 +43,20 @@ namespace {
 
 template <int NW>     // waves per workgroup (32 query rows each): 4 (two workgroups per CU) or 8 (one)
 __device__ __forceinline__ void attn_pipe2_body(const AttnParams& p, int force_safe, char* smem) {   // smem: K slots 0..3 | V^T slots 0..3 | NW flag words
-  constexpr int VBASE = 4 * KTILE_BYTES;
+  constexpr int VBASE = ATTN_VBASE;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int hi = lane >> 5;
-  constexpr int QBW = NW * 32;                    // query rows per workgroup
-  constexpr int NPW = 16 / NW;                    // LDS-DMA pieces per wave and tile (K: 8 pieces, V^T: 8 pieces)
-  const int nqb = (p.Npad + QBW - 1) / QBW;
   const int n = (p.Nk + KT - 1) / KT;             // >= 6 and (n - 2) % 4 == 0 (launcher)
 
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = bid / nqb, qb = bid - bh * nqb;
-  const int b = bh / p.H, h = bh - b * p.H;
-  const bf16_t* Qb = p.Q + (long)bh * p.Npad * D;
-  const bf16_t* Kb = p.K + (long)bh * p.Npad * D;
-  const bf16_t* Vb = p.Vt + (long)bh * D * p.Npad;
-  const int q = qb * QBW + wave * 32 + (lane & 31);
-  if (qb * QBW >= p.Nq) return;
+  const AttnBlock blk = attn_block(p, xcd_remap(blockIdx.x, gridDim.x), NW * 32, 32, wave);
+  const int q = blk.q0 + (lane & 31);
+  if (blk.past) return;
 
   bf16x8_t qf[4];
   {
-    const bf16_t* qrow = Qb + (long)(q < p.Npad ? q : p.Npad - 1) * D + hi * 8;   // rows past Npad (NW = 8) are never stored
+    const bf16_t* qrow = blk.Qb + (long)(q < p.Npad ? q : p.Npad - 1) * D + hi * 8;   // rows past Npad (NW = 8) are never stored
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
       const u32x4_t raw = *(const u32x4_t*)(qrow + kk * 16);
@@ -74,31 +67,12 @@ __device__ __forceinline__ void attn_pipe2_body(const AttnParams& p, int force_s
     }
   }
 
-  // LDS-DMA: the first half of the waves brings K tiles (rows = keys), the second half V^T tiles (rows = d); NPW x 1 KB
-  // pieces per wave and tile
+  // LDS-DMA: the first half of the waves brings K tiles, the second half V^T tiles (the K rows are read in order here: AttnSwzK32)
   const bool kwave = wave < NW / 2;
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(kwave ? Kb : Vb), 0, 0x7fffffff, 0x00020000);   // raw buffer, wave-uniform
-  const int tstride = kwave ? KT * D * 2 : KT * 2;               // bytes per tile step in the source
-  const int rstride = kwave ? D : p.Npad;
-  uint32_t goff[NPW];
-  int ldsoff[NPW];
-#pragma unroll
-  for (int i = 0; i < NPW; ++i) {
-    const int piece = (wave % (NW / 2)) * NPW + i;
-    const int r = piece * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((r >> 1) & 7);
-    goff[i] = (uint32_t)(r * rstride + chunk * 8) * 2u;
-    ldsoff[i] = (kwave ? 0 : VBASE) + piece * 1024;
-  }
-  auto dma_piece = [&](int i, int slot, int t) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(smem + slot * KTILE_BYTES + ldsoff[i]),
-                                             16, goff[i], t * tstride, 0, 0);
-  };
-  auto dma = [&](int slot, int t) {
-#pragma unroll
-    for (int i = 0; i < NPW; ++i) dma_piece(i, slot, t);
-  };
+  const AttnDma<NW, AttnSwzK32> ring(blk.Kb, blk.Vb, p.Npad, wave, lane);
+  constexpr int NPW = decltype(ring)::NPW;
+  auto dma_piece = [&](int i, int slot, int t) { ring.piece(smem, i, slot, t); };
+  auto dma = [&](int slot, int t) { ring.tile(smem, slot, t); };
 
   int kofs[4], vofs[4];
   {
@@ -297,27 +271,16 @@ __device__ __forceinline__ void attn_pipe2_body(const AttnParams& p, int force_s
   bool redo = force_safe != 0;
   if (!redo) {
     ltot = pass(T{});
-    // 2^-80 <= l <= 2^110 (NaN fails): see the header comment
-    const bool bad = !(ltot >= 8.2718061e-25f && ltot <= 1.2980742e33f) && (q < p.Nq);
-    int* flags = (int*)(smem + 8 * KTILE_BYTES);
-    const bool wbad = __any(bad);
-    if (lane == 0) flags[wave] = wbad ? 1 : 0;
-    __syncthreads();
-    redo = false;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) redo = redo || flags[w] != 0;
-    __syncthreads();
+    // 2^-80 <= l <= 2^110 (ATTN_L_MIN / ATTN_L_MAX; NaN fails): see the header comment
+    const float l1[1] = {ltot};
+    redo = attn_window_vote<NW, 1>(smem, l1, q, p.Nq, lane, wave);
   }
   if (redo) ltot = pass(F{});
-  // Every LDS-DMA of this workgroup has LANDED before the workgroup ends: the loops above run ahead of the tiles they consume;
-  // a wave that ended with buffer_load ... lds in flight would let the data
-  // arrive in LDS that may by then belong to the next workgroup on this CU.  (Round 5: added while hunting the co-residency bug
-  // that turned out to be the packed-fp32 one -- csrc/build.sh -- and kept: it measures at 0 us of a 3.6 ms launch.)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  attn_dma_drain();
 
   const float inv = ltot > 0.f ? 1.0f / ltot : 0.f;
   if (q < p.Nq) {
-    bf16_t* orow = p.O + (long)b * p.o_bs + (long)q * p.o_rs + h * D;
+    bf16_t* orow = p.O + (long)blk.b * p.o_bs + (long)q * p.o_rs + blk.h * D;   // (the 32x32 layout: its own epilogue)
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -346,15 +309,11 @@ __global__ __launch_bounds__(512, 2) void ld_attn_pipe2_w8_kernel(AttnParams p, 
 
 // nw = 4 | 8: the workgroup size in waves
 int ld_attn_pipe2_launch(const AttnParams& p, hipStream_t st, int safe, int nw, AttnRan* ran) {
-  constexpr int SMEM = 8 * KTILE_BYTES + 64;
   static thread_local LdSmemCache c4{}, c8{};
-  if (int rc = nw == 4 ? ld_ensure_dyn_smem((const void*)ld_attn_pipe2_w4_kernel, SMEM, &c4)
-                       : ld_ensure_dyn_smem((const void*)ld_attn_pipe2_w8_kernel, SMEM, &c8)) return rc;
   const int qbw = nw * 32;
   dim3 grid((unsigned)((long)p.B * p.H * ((p.Npad + qbw - 1) / qbw)));
-  *ran = {nw == 4 ? (safe ? "ld_attn_pipe2_w4_kernel[safe pass forced]" : "ld_attn_pipe2_w4_kernel")
-                  : (safe ? "ld_attn_pipe2_w8_kernel[safe pass forced]" : "ld_attn_pipe2_w8_kernel"), nullptr, safe ? 0 : 2};
-  if (nw == 4) hipLaunchKernelGGL(ld_attn_pipe2_w4_kernel, grid, dim3(256), SMEM, st, p, safe);
-  else hipLaunchKernelGGL(ld_attn_pipe2_w8_kernel, grid, dim3(512), SMEM, st, p, safe);
-  return ld_check_launch("ld_attn_fwd_bf16(pipe2)");
+  if (nw == 4) return attn_launch(ld_attn_pipe2_w4_kernel, &c4, ATTN_SMEM_BYTES, grid, dim3(256), st, ran,
+                                  attn_ran_static(ATTN_KNAMES(ld_attn_pipe2_w4_kernel), safe), "ld_attn_fwd_bf16(pipe2)", p, safe);
+  return attn_launch(ld_attn_pipe2_w8_kernel, &c8, ATTN_SMEM_BYTES, grid, dim3(512), st, ran,
+                     attn_ran_static(ATTN_KNAMES(ld_attn_pipe2_w8_kernel), safe), "ld_attn_fwd_bf16(pipe2)", p, safe);
 }

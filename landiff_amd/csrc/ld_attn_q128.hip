@@ -36,12 +36,11 @@
 //   phase 2: PV + row sums of half h (40 MFMAs) over exp2 of scores 0..NPRE-1 of half h+1 and the 4 K fragment reads of half h+2
 // LDS ring and barrier cadence unchanged: four K and four V^T slots of 8 KB, one workgroup barrier per two tiles.
 #include "ld_attn.h"
+#include "ld_attn_dev.h"
 
 namespace {
 
 #define FENCE() __builtin_amdgcn_sched_barrier(0)
-
-__device__ __forceinline__ int q128_swz_k(int r) { return ((r >> 1) & 1) | (((r >> 3) & 3) << 1); }
 
 constexpr int Q128_NW = 4;                 // waves per workgroup
 constexpr int Q128_NQB = 8;                // 16-row query blocks per wave
@@ -54,12 +53,6 @@ constexpr int AQ(int qb, int ks) { return 128 + (qb * 2 + ks) * 4; }
 constexpr int AK(int bb, int ks) { return 192 + (bb * 2 + ks) * 4; }
 constexpr int AV(int db) { return 208 + db * 4; }
 constexpr int Q128_AGPRS = 228;
-
-template <int I> using IC = std::integral_constant<int, I>;
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-  if constexpr (I < N) { f(IC<I>{}); static_for<N, I + 1>(f); }
-}
 
 // S^T quad (VGPRs)  = / +=  K fragment (a[K:K+3]) . Q^T fragment (a[Q:Q+3])
 template <int K, int Q> __device__ __forceinline__ void mfma_s_zero(f32x4_t& d) {
@@ -114,81 +107,40 @@ __device__ __forceinline__ void lgkm_wait0() { asm volatile("s_waitcnt lgkmcnt(0
 template <int NPRE, int SCHED>
 __device__ __forceinline__ void attn_q128_body(const AttnParams& p, int force_safe, char* smem) {   // smem: K slots 0..3 | V^T slots 0..3 | flag words
   constexpr int NW = Q128_NW, NQB = Q128_NQB;
-  constexpr int VBASE = 4 * KTILE_BYTES;
+  constexpr int VBASE = ATTN_VBASE;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l16 = lane & 15, h4 = lane >> 4;
-  constexpr int NPW = 16 / NW;                    // LDS-DMA pieces per wave and tile
-  const int nqb = (p.Npad + Q128_ROWS - 1) / Q128_ROWS;
   const int n = (p.Nk + KT - 1) / KT;             // >= 6 (launcher)
   const int NH = 2 * n;                           // halves
 
-  const int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int bh = bid / nqb, qblk = bid - bh * nqb;
-  const int b = bh / p.H, h = bh - b * p.H;
-  const bf16_t* Qb = p.Q + (long)bh * p.Npad * D;
-  const bf16_t* Kb = p.K + (long)bh * p.Npad * D;
-  const bf16_t* Vb = p.Vt + (long)bh * D * p.Npad;
-  const int q0 = qblk * Q128_ROWS + wave * Q128_WROWS;
-  if (qblk * Q128_ROWS >= p.Nq) return;
+  const AttnBlock blk = attn_block(p, xcd_remap(blockIdx.x, gridDim.x), Q128_ROWS, Q128_WROWS, wave);
+  const int q0 = blk.q0;
+  if (blk.past) return;
   // bit 256 (timing builds): shader-clock cycles (s_memtime) and 100 MHz ticks (s_memrealtime) of every workgroup into kt_min
   unsigned long long t_cyc0 = 0, t_real0 = 0;
   if (LD_Q128_ABLATE & 256) { t_cyc0 = __builtin_amdgcn_s_memtime(); t_real0 = __builtin_amdgcn_s_memrealtime(); }
 
-  // Q^T fragments (B operand): rows q0 + qb*16 + l16, d = ks*32 + h4*8 .. + 8, pre-multiplied by scale * log2(e) -> a[128:191]
+  // Q^T fragments -> a[128:191] (the quad is part of the asm text: the indices must be constants)
   static_for<NQB>([&](auto qc) {
-    constexpr int qb = decltype(qc)::value;
-    const int q = q0 + qb * 16 + l16;
-    const bf16_t* qrow = Qb + (long)(q < p.Npad ? q : p.Npad - 1) * D + h4 * 8;
     static_for<2>([&](auto kc) {
-      constexpr int ks = decltype(kc)::value;
-      const u32x4_t raw = *(const u32x4_t*)(qrow + ks * 32);
-      u32x4_t sc;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) sc[e] = pack_bf16x2(bf_lo(raw[e]) * p.c, bf_hi(raw[e]) * p.c);
-      acc_write4<AQ(qb, ks)>(sc);
+      constexpr int qb = decltype(qc)::value, ks = decltype(kc)::value;
+      acc_write4<AQ(qb, ks)>(attn_qt_frag(p, blk.Qb, q0 + qb * 16 + l16, h4, ks));
     });
   });
 
-  // LDS-DMA: waves 0, 1 bring K tiles (rows = keys), waves 2, 3 V^T tiles (rows = d)
+  // LDS-DMA: waves 0, 1 bring K tiles, waves 2, 3 V^T tiles
   const bool kwave = wave < NW / 2;
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(kwave ? Kb : Vb), 0, 0x7fffffff, 0x00020000);   // raw buffer, wave-uniform
-  const int tstride = kwave ? KT * D * 2 : KT * 2;               // bytes per tile step in the source
-  const int rstride = kwave ? D : p.Npad;
-  uint32_t goff[NPW];
-  int ldsoff[NPW];
-#pragma unroll
-  for (int i = 0; i < NPW; ++i) {
-    const int piece = (wave % (NW / 2)) * NPW + i;
-    const int r = piece * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ (kwave ? q128_swz_k(r) : ((r >> 1) & 7));
-    goff[i] = (uint32_t)(r * rstride + chunk * 8) * 2u;
-    ldsoff[i] = (kwave ? 0 : VBASE) + piece * 1024;
-  }
-  auto dma_piece = [&](int i, int slot, int t) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(smem + slot * KTILE_BYTES + ldsoff[i]),
-                                             16, goff[i], t * tstride, 0, 0);
-  };
-  auto dma = [&](int slot, int t) {
-#pragma unroll
-    for (int i = 0; i < NPW; ++i) dma_piece(i, slot, t);
-  };
+  const AttnDma<NW, AttnSwzK16> ring(blk.Kb, blk.Vb, p.Npad, wave, lane);
+  constexpr int NPW = decltype(ring)::NPW;
+  auto dma_piece = [&](int i, int slot, int t) { ring.piece(smem, i, slot, t); };
+  auto dma = [&](int slot, int t) { ring.tile(smem, slot, t); };
 
-  // fragment read addresses (LDS byte addresses): K block 2*kg + b, k-step ks: kaddr[ks] + slot*8K + kg*4096 + b*512;
-  // V^T block db, key group kg: vaddr[kg] + VBASE + slot*8K + db*2048
+  // fragment read addresses (LDS byte addresses; VBASE goes into the V^T reads' offset field)
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
   uint32_t kaddr[2], vaddr[2];
-  {
-    const int key = 8 * (l16 >> 2) + (l16 & 3);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int c = ks * 4 + h4;
-      kaddr[ks] = lds0 + key * 128 + ((c ^ q128_swz_k(key)) << 4);
-      vaddr[ks] = lds0 + l16 * 128 + ((c ^ ((l16 >> 1) & 7)) << 4);
-    }
-  }
+  attn_frag_offsets(l16, h4, lds0, lds0, kaddr, vaddr);
   // fragment loads into the fixed quads: slot / key group are compile-time (they go into the offset field)
   auto KF = [&](auto slot_c, auto kg_c, auto g_c) {              // g = b*2 + ks
     constexpr int slot = decltype(slot_c)::value, kg = decltype(kg_c)::value, g = decltype(g_c)::value;
@@ -212,19 +164,7 @@ __device__ __forceinline__ void attn_q128_body(const AttnParams& p, int force_sa
     static_for<32>([&](auto c) { acc_write4<decltype(c)::value * 4>(z); });
   };
 
-  // keys of half hh (tile hh >> 1, key group hh & 1) past Nk -> -inf-like scores
-  auto mask_half = [&](f32x4_t (&s)[2][NQB], int hh) {
-#pragma unroll
-    for (int bb = 0; bb < 2; ++bb) {
-      const int key0 = (hh >> 1) * KT + (hh & 1) * 32 + h4 * 8 + bb * 4;
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (key0 + r >= p.Nk) {
-#pragma unroll
-          for (int qb = 0; qb < NQB; ++qb) s[bb][qb][r] = NEG_BIG;
-        }
-    }
-  };
+  auto mask_half = [&](f32x4_t (&s)[2][NQB], int hh) { attn_mask_half<NQB>(s, hh, h4, p.Nk); };
 
   // ---------------- fast pass: no running maximum (see ld_attn_pipe.hip for the argument and the window test) ----------------
   float ltot[NQB];
@@ -441,26 +381,10 @@ __device__ __forceinline__ void attn_q128_body(const AttnParams& p, int force_sa
   bool redo = force_safe != 0;
   if (!redo) {
     fast_pass();
-    // 2^-80 <= l <= 2^110 (NaN fails): see the header comment of ld_attn_pipe.hip
-    bool bad = false;
-#pragma unroll
-    for (int qb = 0; qb < NQB; ++qb)
-      bad = bad || (!(ltot[qb] >= 8.2718061e-25f && ltot[qb] <= 1.2980742e33f) && (q0 + qb * 16 + l16 < p.Nq));
-    int* flags = (int*)(smem + 8 * KTILE_BYTES);
-    const bool wbad = __any(bad);
-    if (lane == 0) flags[wave] = wbad ? 1 : 0;
-    __syncthreads();
-    redo = false;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) redo = redo || flags[w] != 0;
-    __syncthreads();
+    redo = attn_window_vote<NW, NQB>(smem, ltot, q0 + l16, p.Nq, lane, wave);
   }
   if (redo && !LD_Q128_ABLATE) safe_pass();          // (an ablated fast pass fails its window test: time it, do not redo it)
-  // Every LDS-DMA of this workgroup has LANDED before the workgroup ends: the loops above run ahead of the tiles they consume (and,
-  // having no peeled tail, request tiles nobody reads); a wave that ended with buffer_load ... lds in flight would let the data
-  // arrive in LDS that may by then belong to the next workgroup on this CU.  (Round 5: added while hunting the co-residency bug
-  // that turned out to be the packed-fp32 one -- csrc/build.sh -- and kept: it measures at 0 us of a 3.6 ms launch.)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  attn_dma_drain();
 
   if ((LD_Q128_ABLATE & 256) && p.kt_min && tid == 0) {
     unsigned long long* dbg = (unsigned long long*)p.kt_min + (long)blockIdx.x * 2;
@@ -470,17 +394,8 @@ __device__ __forceinline__ void attn_q128_body(const AttnParams& p, int force_sa
   mfma_settle();
   static_for<NQB>([&](auto qc) {
     constexpr int qb = decltype(qc)::value;
-    const int q = q0 + qb * 16 + l16;
-    const float inv = ltot[qb] > 0.f ? 1.0f / ltot[qb] : 0.f;
-    bf16_t* orow = p.O + (long)b * p.o_bs + (long)q * p.o_rs + h * D + h4 * 4;
-    static_for<4>([&](auto dc) {
-      constexpr int db = decltype(dc)::value;
-      const f32x4_t o4 = acc_read4<AO(db, qb)>();
-      u32x2_t w2;
-      w2[0] = pack_bf16x2(o4[0] * inv, o4[1] * inv);
-      w2[1] = pack_bf16x2(o4[2] * inv, o4[3] * inv);
-      if (q < p.Nq) *(u32x2_t*)(orow + db * 16) = w2;
-    });
+    attn_store_o(p, blk.b, blk.h, q0 + qb * 16 + l16, h4, ltot[qb], acc_read4<AO(0, qb)>(), acc_read4<AO(1, qb)>(), acc_read4<AO(2, qb)>(),
+                 acc_read4<AO(3, qb)>());
   });
 }
 #undef FENCE
@@ -504,24 +419,15 @@ LD_Q128_KERNEL(ld_attn_q128_s1n40_kernel, 40, 1)       // (LD_ATTN_NPRE=1040)
 
 // npre: 44 = the shipped exp2 split; 36 | 52 | 1036 | 1040 the other instantiations above; anything else runs the shipped one
 int ld_attn_q128_launch(const AttnParams& p, hipStream_t st, int safe, int npre, AttnRan* ran) {
-  constexpr int SMEM = 8 * KTILE_BYTES + 64;
   static thread_local LdSmemCache c44{}, c36{}, c52{}, cs1{}, cs2{};
   dim3 grid((unsigned)((long)p.B * p.H * ((p.Npad + Q128_ROWS - 1) / Q128_ROWS)));
-  if (npre != 44) {
-    void (*k)(AttnParams, int) = nullptr; LdSmemCache* c = nullptr; const char* name = nullptr;
-    if (npre == 36) { k = ld_attn_q128_n36_kernel; c = &c36; name = "ld_attn_q128_n36_kernel"; }
-    else if (npre == 52) { k = ld_attn_q128_n52_kernel; c = &c52; name = "ld_attn_q128_n52_kernel"; }
-    else if (npre == 1036) { k = ld_attn_q128_s1_kernel; c = &cs1; name = "ld_attn_q128_s1_kernel"; }
-    else if (npre == 1040) { k = ld_attn_q128_s1n40_kernel; c = &cs2; name = "ld_attn_q128_s1n40_kernel"; }
-    if (k) {
-      if (int rc = ld_ensure_dyn_smem((const void*)k, SMEM, c)) return rc;
-      *ran = {name, nullptr, safe ? 0 : 2};
-      hipLaunchKernelGGL(k, grid, dim3(256), SMEM, st, p, safe);
-      return ld_check_launch("ld_attn_fwd_bf16(q128)");
-    }
-  }
-  if (int rc = ld_ensure_dyn_smem((const void*)ld_attn_q128_kernel, SMEM, &c44)) return rc;
-  *ran = {safe ? "ld_attn_q128_kernel[safe pass forced]" : "ld_attn_q128_kernel", nullptr, safe ? 0 : 2};
-  hipLaunchKernelGGL(ld_attn_q128_kernel, grid, dim3(256), SMEM, st, p, safe);
-  return ld_check_launch("ld_attn_fwd_bf16(q128)");
+  auto go = [&](void (*k)(AttnParams, int), LdSmemCache* c, const char* name, const char* name_safe) {
+    return attn_launch(k, c, ATTN_SMEM_BYTES, grid, dim3(256), st, ran, attn_ran_static(name, name_safe, safe), "ld_attn_fwd_bf16(q128)", p, safe);
+  };
+  // (the other exp2 splits report their plain name under a forced safe pass too)
+  if (npre == 36) return go(ld_attn_q128_n36_kernel, &c36, "ld_attn_q128_n36_kernel", "ld_attn_q128_n36_kernel");
+  if (npre == 52) return go(ld_attn_q128_n52_kernel, &c52, "ld_attn_q128_n52_kernel", "ld_attn_q128_n52_kernel");
+  if (npre == 1036) return go(ld_attn_q128_s1_kernel, &cs1, "ld_attn_q128_s1_kernel", "ld_attn_q128_s1_kernel");
+  if (npre == 1040) return go(ld_attn_q128_s1n40_kernel, &cs2, "ld_attn_q128_s1n40_kernel", "ld_attn_q128_s1n40_kernel");
+  return go(ld_attn_q128_kernel, &c44, ATTN_KNAMES(ld_attn_q128_kernel));
 }

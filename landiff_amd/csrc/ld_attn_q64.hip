@@ -22,6 +22,7 @@
 // V^T fragments (half h+2), so a period that starts at tile t needs K_{t+1}, K_{t+2}, V_t, V_{t+1} resident and refills the
 // other slots with K_{t+3}, K_{t+4} (K waves) and V_{t+2}, V_{t+3} (V^T waves); one workgroup barrier per period.
 #include "ld_attn.h"
+#include "ld_attn_dev.h"
 #include <mutex>
 
 namespace {
@@ -63,10 +64,13 @@ constexpr int Q64_QSETS = 64;
 constexpr int Q64_MAXDEV = 16;
 __device__ unsigned g_q64_queue[Q64_QSETS][16];          // [set][0..7]: next block of XCD x's range (64 bytes per set)
 
-__global__ __launch_bounds__(256, 2) void ld_attn_q64_dyn_kernel(AttnParams p, int force_safe, int total, int set) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  int* bcast = (int*)(smem + 8 * KTILE_BYTES + 32);
-  int* flags = (int*)(smem + 8 * KTILE_BYTES);             // the body's per-wave "a row left the window" words
+// One pull loop for the dense and the frame-window body (two thin non-template entry points below: hipcc emits no host stub for a
+// kernel that is itself the template, ld_attn_pipe.hip).
+template <bool WIN>
+__device__ __forceinline__ void attn_q64_pull(const AttnParams& p, int force_safe, char* smem, int total, int set,
+                                              int prefix = 0, int group = 0, int frames = 0) {
+  int* bcast = (int*)(smem + ATTN_BCAST_OFF);
+  int* flags = (int*)(smem + ATTN_FLAGS_OFF);              // the body's per-wave "a row left the window" words (attn_window_vote)
   unsigned* Q = g_q64_queue[set];
   unsigned xcc;
   asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
@@ -85,50 +89,9 @@ __global__ __launch_bounds__(256, 2) void ld_attn_q64_dyn_kernel(AttnParams p, i
       // cleared HERE, inside the one thread-0 section of the iteration: a second `if (threadIdx.x == 0)` at the end of the loop
       // body gets threaded into this one by hipcc, which puts the barriers below inside a divergent loop (the launch hangs).
       if ((flags[0] | flags[1] | flags[2] | flags[3]) != 0) __hip_atomic_fetch_add(&Q[8], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      flags[0] = flags[1] = flags[2] = flags[3] = 0;      // (a block past Nq returns before it writes them)
-#endif
-      int bid = -1;
-      for (int kx = 0; kx < 8 && bid < 0; ++kx) {        // own range first, then the neighbours'
-        const int x = (int)((xcc + kx) & 7u);
-        if (__hip_atomic_load(&Q[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)cnt(x)) continue;
-        const unsigned i = __hip_atomic_fetch_add(&Q[x], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (i < (unsigned)cnt(x)) bid = base(x) + (int)i;
-      }
-      bcast[0] = bid;
-    }
-    __syncthreads();
-    const int bid = bcast[0];
-    __syncthreads();
-    if (bid < 0) break;
-    attn_q64_body<Q64_FAST>(p, force_safe, smem, bid);
-    __syncthreads();
-  }
-}
-
-// The window form pulled through the same counter sets, with the same fallback count word: the loop of ld_attn_q64_dyn_kernel
-// around the WIN body (a copy, so that the dense kernel's instruction stream stays what it was).
-__global__ __launch_bounds__(256, 2) void ld_attn_q64_win_dyn_kernel(AttnParams p, int force_safe, int total, int set,
-                                                                     int prefix, int group, int frames) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  int* bcast = (int*)(smem + 8 * KTILE_BYTES + 32);
-  int* flags = (int*)(smem + 8 * KTILE_BYTES);             // the body's per-wave "a row left the window" words
-  unsigned* Q = g_q64_queue[set];
-  unsigned xcc;
-  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-  xcc &= 7u;
-  const int per = total / 8, rem = total % 8;            // xcd_remap: XCD x owns [base(x), base(x) + cnt(x))
-  auto base = [&](int x) { return x < rem ? x * (per + 1) : rem * (per + 1) + (x - rem) * per; };
-  auto cnt = [&](int x) { return per + (x < rem ? 1 : 0); };
-#ifndef LD_Q64_NO_FBCOUNT
-  if (threadIdx.x == 0) flags[0] = flags[1] = flags[2] = flags[3] = 0;
-#endif
-  for (;;) {
-    if (threadIdx.x == 0) {
-#ifndef LD_Q64_NO_FBCOUNT
-      // (counted and cleared inside the ONE thread-0 section of the iteration: see ld_attn_q64_dyn_kernel)
-      if ((flags[0] | flags[1] | flags[2] | flags[3]) != 0) __hip_atomic_fetch_add(&Q[8], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       int z = 0;
-      asm volatile("" : "+v"(z));                         // a zero made HERE: hoisted out of the loop, the four-register zero of this store was spilled to scratch
+      // WIN: a zero made HERE: hoisted out of the loop, the four-register zero of this store was spilled to scratch
+      if constexpr (WIN) asm volatile("" : "+v"(z));
       flags[0] = flags[1] = flags[2] = flags[3] = z;      // (a block past Nq returns before it writes them)
 #endif
       int bid = -1;
@@ -141,12 +104,27 @@ __global__ __launch_bounds__(256, 2) void ld_attn_q64_win_dyn_kernel(AttnParams 
       bcast[0] = bid;
     }
     __syncthreads();
-    const int bid = __builtin_amdgcn_readfirstlane(bcast[0]);   // a scalar: the block's tile list and loop bounds derive from it
+    int bid = bcast[0];
+    if constexpr (WIN) bid = __builtin_amdgcn_readfirstlane(bid);   // a scalar: the block's tile list and loop bounds derive from it
     __syncthreads();
     if (bid < 0) break;
-    attn_q64_body<Q64_FAST, true>(p, force_safe, smem, bid, prefix, group, frames);
+    // (two calls, not attn_q64_body<Q64_FAST, WIN>: hipcc's host pass fails to substitute the dependent form)
+    if constexpr (WIN) attn_q64_body<Q64_FAST, true>(p, force_safe, smem, bid, prefix, group, frames);
+    else attn_q64_body<Q64_FAST>(p, force_safe, smem, bid);
     __syncthreads();
   }
+}
+
+__global__ __launch_bounds__(256, 2) void ld_attn_q64_dyn_kernel(AttnParams p, int force_safe, int total, int set) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  attn_q64_pull<false>(p, force_safe, smem, total, set);
+}
+
+// The window form pulled through the same counter sets, with the same fallback count word.
+__global__ __launch_bounds__(256, 2) void ld_attn_q64_win_dyn_kernel(AttnParams p, int force_safe, int total, int set,
+                                                                     int prefix, int group, int frames) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  attn_q64_pull<true>(p, force_safe, smem, total, set, prefix, group, frames);
 }
 
 __global__ void ld_q64_queue_fill_kernel(int set, unsigned value) {
@@ -198,11 +176,7 @@ int q64_device_info(int* dev_out, unsigned** base_out, int* slots_out) {
 // want_dyn (the plan: LD_ATTN_DYN and no forced safe pass): the dynamic form where it can be had -- a grid of at least four rounds of
 // the chip's slots, a stream that is not being captured and a counter set for it -- else the hardware's round-robin dispatch.
 int ld_attn_q64_launch(const AttnParams& p, hipStream_t st, const int* win, int safe, bool want_dyn, AttnRan* ran) {
-  constexpr int SMEM = 8 * KTILE_BYTES + 64;
-  static thread_local LdSmemCache cache{};
-  static thread_local LdSmemCache cache_w{};
-  if (int rc = win ? ld_ensure_dyn_smem((const void*)ld_attn_q64_win_kernel, SMEM, &cache_w)
-                   : ld_ensure_dyn_smem((const void*)ld_attn_q64_kernel, SMEM, &cache)) return rc;
+  static thread_local LdSmemCache cache{}, cache_w{}, cache_d{}, cache_wd{};
   const int total = (int)((long)p.B * p.H * ((p.Npad + Q64_ROWS - 1) / Q64_ROWS));
   if (want_dyn) {
     int dev = -1, slots = 0; unsigned* base = nullptr;
@@ -211,30 +185,22 @@ int ld_attn_q64_launch(const AttnParams& p, hipStream_t st, const int* win, int 
     if (dev >= 0 && total >= 4 * slots && hipStreamIsCapturing(st, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone) {
       const int set = q64_set_for(dev, st);
       if (set >= 0) {
-        static thread_local LdSmemCache cache_d{}, cache_wd{};
-        if (int rc = win ? ld_ensure_dyn_smem((const void*)ld_attn_q64_win_dyn_kernel, SMEM, &cache_wd)
-                         : ld_ensure_dyn_smem((const void*)ld_attn_q64_dyn_kernel, SMEM, &cache_d)) return rc;
         hipError_t e = hipMemsetAsync(base + set * 16, 0, 64, st);
         if (e != hipSuccess) return ld_set_error(LD_ERR_LAUNCH, "ld_attn_fwd_bf16(q64 dynamic): zeroing counter set %d: %s", set, hipGetErrorString(e));
-        if (win) {
-          *ran = {"ld_attn_q64_win_dyn_kernel", base + set * 16 + 8, 1};
-          hipLaunchKernelGGL(ld_attn_q64_win_dyn_kernel, dim3((unsigned)slots), dim3(256), SMEM, st, p, safe, total, set, win[0], win[1], win[2]);
-          return ld_check_launch("ld_attn_fwd_bf16_window(q64 dynamic)");
-        }
-        *ran = {"ld_attn_q64_dyn_kernel", base + set * 16 + 8, 1};
-        hipLaunchKernelGGL(ld_attn_q64_dyn_kernel, dim3((unsigned)slots), dim3(256), SMEM, st, p, safe, total, set);
-        return ld_check_launch("ld_attn_fwd_bf16(q64 dynamic)");
+        const unsigned* count = base + set * 16 + 8;      // fb_kind 1: the launch counts its fallbacks there
+        if (win) return attn_launch(ld_attn_q64_win_dyn_kernel, &cache_wd, ATTN_SMEM_BYTES, dim3((unsigned)slots), dim3(256), st, ran,
+                                    AttnRan{"ld_attn_q64_win_dyn_kernel", count, 1}, "ld_attn_fwd_bf16_window(q64 dynamic)",
+                                    p, safe, total, set, win[0], win[1], win[2]);
+        return attn_launch(ld_attn_q64_dyn_kernel, &cache_d, ATTN_SMEM_BYTES, dim3((unsigned)slots), dim3(256), st, ran,
+                           AttnRan{"ld_attn_q64_dyn_kernel", count, 1}, "ld_attn_fwd_bf16(q64 dynamic)", p, safe, total, set);
       }
     }
   }
-  if (win) {
-    *ran = {safe ? "ld_attn_q64_win_kernel[safe pass forced]" : "ld_attn_q64_win_kernel", nullptr, safe ? 0 : 2};
-    hipLaunchKernelGGL(ld_attn_q64_win_kernel, dim3((unsigned)total), dim3(256), SMEM, st, p, safe, win[0], win[1], win[2]);
-    return ld_check_launch("ld_attn_fwd_bf16_window(q64)");
-  }
-  *ran = {safe ? "ld_attn_q64_kernel[safe pass forced]" : "ld_attn_q64_kernel", nullptr, safe ? 0 : 2};
-  hipLaunchKernelGGL(ld_attn_q64_kernel, dim3((unsigned)total), dim3(256), SMEM, st, p, safe);
-  return ld_check_launch("ld_attn_fwd_bf16(q64)");
+  if (win) return attn_launch(ld_attn_q64_win_kernel, &cache_w, ATTN_SMEM_BYTES, dim3((unsigned)total), dim3(256), st, ran,
+                              attn_ran_static(ATTN_KNAMES(ld_attn_q64_win_kernel), safe), "ld_attn_fwd_bf16_window(q64)",
+                              p, safe, win[0], win[1], win[2]);
+  return attn_launch(ld_attn_q64_kernel, &cache, ATTN_SMEM_BYTES, dim3((unsigned)total), dim3(256), st, ran,
+                     attn_ran_static(ATTN_KNAMES(ld_attn_q64_kernel), safe), "ld_attn_fwd_bf16(q64)", p, safe);
 }
 
 // Forget which stream owns which counter set on the current device and zero the sets (on `stream`).  The caller guarantees that no

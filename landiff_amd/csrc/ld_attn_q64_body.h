@@ -1,9 +1,7 @@
 // The query-block body of the 64-query-row attention tile (see ld_attn_q64.hip for the design), shared by the headline kernels
 // (ld_attn_q64.hip: Q64_FAST) and the exact two-pass form (ld_attn_q64_exact.hip: Q64_EXACT).  Include inside an anonymous namespace,
-// after ld_attn.h.
+// after ld_attn_dev.h, whose pieces the body is assembled from.
 #define FENCE() __builtin_amdgcn_sched_barrier(0)
-
-__device__ __forceinline__ int q64_swz_k(int r) { return ((r >> 1) & 1) | (((r >> 3) & 3) << 1); }
 
 constexpr int Q64_NW = 4;               // waves per workgroup
 constexpr int Q64_ROWS = Q64_NW * 64;   // query rows per workgroup
@@ -19,14 +17,14 @@ enum { Q64_FAST = 0, Q64_EXACT = 1 };
 
 // WIN (ld_attn_q64_win_kernel / ld_attn_q64_win_dyn_kernel, Q64_FAST only): frame-window attention.  The query block walks the
 // LOGICAL tile list 0 .. pt-1, t_lo .. t_hi-1 of attn_window_block (ld_attn.h) instead of all n tiles: logical tile t is source
-// tile t < pt ? t : t + shift (in dma_piece, so every pass follows it), n is the list's length and the tail handling sees the
-// logical key count.  Wave-uniform scalars derived once per block; the loops, phases and barriers are the dense ones.
+// tile t < pt ? t : t + shift (src_tile, which every DMA of the body goes through, so every pass follows it), n is the list's
+// length and the tail handling sees the logical key count.  Wave-uniform scalars derived once per block; the loops, phases and
+// barriers are the dense ones.
 template <int MODE, bool WIN = false>
 __device__ __forceinline__ void attn_q64_body(const AttnParams& p, int force_safe, char* smem, const int bid,
                                               int win_prefix = 0, int win_group = 0, int win_frames = 0) {   // smem: K slots 0..3 | V^T slots 0..3 | flag words; bid: remapped block index
   static_assert(!WIN || MODE == Q64_FAST, "the window form exists for the fast pass only");
   constexpr int NW = Q64_NW;
-  constexpr int VBASE = 4 * KTILE_BYTES;
   int tid_ = threadIdx.x;
   // WIN: an opaque copy, so that the per-lane offsets are values of THIS block: hoisted out of the dynamic form's block loop they
   // stayed live across the pipelined loop, which has no register to spare (11 VGPRs spilled to scratch)
@@ -35,7 +33,6 @@ __device__ __forceinline__ void attn_q64_body(const AttnParams& p, int force_saf
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l16 = lane & 15, h4 = lane >> 4;
-  constexpr int NPW = 16 / NW;                    // LDS-DMA pieces per wave and tile
   const int nqb = (p.Npad + Q64_ROWS - 1) / Q64_ROWS;
   int n_ = (p.Nk + KT - 1) / KT, nk_ = p.Nk, wshift_ = 0, wpt_ = 0;
   if constexpr (WIN) {
@@ -53,69 +50,27 @@ __device__ __forceinline__ void attn_q64_body(const AttnParams& p, int force_saf
   const int wshift = wshift_, wpt = wpt_;
   const int NH = 2 * n;                           // halves
 
-  const int bh = bid / nqb, qblk = bid - bh * nqb;
-  const int b = bh / p.H, h = bh - b * p.H;
-  const bf16_t* Qb = p.Q + (long)bh * p.Npad * D;
-  const bf16_t* Kb = p.K + (long)bh * p.Npad * D;
-  const bf16_t* Vb = p.Vt + (long)bh * D * p.Npad;
-  const int q0 = qblk * Q64_ROWS + wave * 64;
-  if (qblk * Q64_ROWS >= p.Nq) return;
+  const AttnBlock blk = attn_block(p, bid, Q64_ROWS, 64, wave);
+  const bf16_t* Kb = blk.Kb;
+  const int q0 = blk.q0;
+  if (blk.past) return;
 #ifdef LD_Q64_TRACE   // timing builds (tools/attn_q64_trace.py): when, where and for how many cycles every workgroup ran, into kt_min
   const unsigned long long t_real0 = __builtin_amdgcn_s_memrealtime(), t_cyc0 = __builtin_amdgcn_s_memtime();
 #endif
 
-  // Q^T fragments (B operand): rows q0 + qb*16 + l16, d = ks*32 + h4*8 .. + 8, pre-multiplied by scale * log2(e)
-  bf16x8_t qf[4][2];
-#pragma unroll
-  for (int qb = 0; qb < 4; ++qb) {
-    const int q = q0 + qb * 16 + l16;
-    const bf16_t* qrow = Qb + (long)(q < p.Npad ? q : p.Npad - 1) * D + h4 * 8;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const u32x4_t raw = *(const u32x4_t*)(qrow + ks * 32);
-      u32x4_t sc;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) sc[e] = pack_bf16x2(bf_lo(raw[e]) * p.c, bf_hi(raw[e]) * p.c);
-      qf[qb][ks] = __builtin_bit_cast(bf16x8_t, sc);
-    }
-  }
+  bf16x8_t qf[4][2];                               // Q^T fragments [qb][ks]
+  attn_load_qt<4>(p, blk.Qb, q0, l16, h4, [&](int qb, int ks, const u32x4_t& w) { qf[qb][ks] = __builtin_bit_cast(bf16x8_t, w); });
 
-  // LDS-DMA: waves 0, 1 bring K tiles (rows = keys), waves 2, 3 V^T tiles (rows = d)
+  // LDS-DMA: waves 0, 1 bring K tiles, waves 2, 3 V^T tiles
   const bool kwave = wave < NW / 2;
-  const __amdgpu_buffer_rsrc_t rsrc =
-      __builtin_amdgcn_make_buffer_rsrc((void*)(kwave ? Kb : Vb), 0, 0x7fffffff, 0x00020000);   // raw buffer, wave-uniform
-  const int tstride = kwave ? KT * D * 2 : KT * 2;               // bytes per tile step in the source
-  const int rstride = kwave ? D : p.Npad;
-  uint32_t goff[NPW];
-  int ldsoff[NPW];
-#pragma unroll
-  for (int i = 0; i < NPW; ++i) {
-    const int piece = (wave % (NW / 2)) * NPW + i;
-    const int r = piece * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ (kwave ? q64_swz_k(r) : ((r >> 1) & 7));
-    goff[i] = (uint32_t)(r * rstride + chunk * 8) * 2u;
-    ldsoff[i] = (kwave ? 0 : VBASE) + piece * 1024;
-  }
-  auto dma_piece = [&](int i, int slot, int t) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(smem + slot * KTILE_BYTES + ldsoff[i]),
-                                             16, goff[i], (WIN ? (t < wpt ? t : t + wshift) : t) * tstride, 0, 0);
-  };
-  auto dma = [&](int slot, int t) {
-#pragma unroll
-    for (int i = 0; i < NPW; ++i) dma_piece(i, slot, t);
-  };
+  const AttnDma<NW, AttnSwzK16> ring(Kb, blk.Vb, p.Npad, wave, lane);
+  constexpr int NPW = decltype(ring)::NPW;
+  auto src_tile = [&](int t) { return WIN ? (t < wpt ? t : t + wshift) : t; };   // logical tile of this block's list -> source tile
+  auto dma_piece = [&](int i, int slot, int t) { ring.piece(smem, i, slot, src_tile(t)); };
+  auto dma = [&](int slot, int t) { ring.tile(smem, slot, src_tile(t)); };
 
-  // fragment read offsets: K block 2*kg + b, k-step ks: kofs[ks] + slot*8K + kg*4096 + b*512;  V^T block db, key group kg: vofs[kg] + slot*8K + db*2048
-  int kofs[2], vofs[2];
-  {
-    const int key = 8 * (l16 >> 2) + (l16 & 3);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int c = ks * 4 + h4;
-      kofs[ks] = key * 128 + ((c ^ q64_swz_k(key)) << 4);
-      vofs[ks] = VBASE + l16 * 128 + ((c ^ ((l16 >> 1) & 7)) << 4);
-    }
-  }
+  int kofs[2], vofs[2];                            // fragment read offsets
+  attn_frag_offsets(l16, h4, 0, ATTN_VBASE, kofs, vofs);
 
   f32x4_t o[4][4];                                 // O^T [db][qb]
   const f32x4_t zero4 = {0.f, 0.f, 0.f, 0.f};
@@ -123,18 +78,7 @@ __device__ __forceinline__ void attn_q64_body(const AttnParams& p, int force_saf
   auto C0 = [&](int qb) -> f32x4_t { if constexpr (MODE == Q64_EXACT) return cinit[qb]; else return zero4; };
 
   // keys of half hh (tile hh >> 1, key group hh & 1) past Nk (nk) -> -inf-like scores
-  auto mask_half = [&](f32x4_t (&s)[2][4], int hh) {
-#pragma unroll
-    for (int bb = 0; bb < 2; ++bb) {
-      const int key0 = (hh >> 1) * KT + (hh & 1) * 32 + h4 * 8 + bb * 4;
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (key0 + r >= nk) {
-#pragma unroll
-          for (int qb = 0; qb < 4; ++qb) s[bb][qb][r] = NEG_BIG;
-        }
-    }
-  };
+  auto mask_half = [&](f32x4_t (&s)[2][4], int hh) { attn_mask_half<4>(s, hh, h4, nk); };
   auto load_kh = [&](bf16x8_t (&kf)[2][2], int slot, int kg) {
 #pragma unroll
     for (int bb = 0; bb < 2; ++bb)
@@ -402,15 +346,11 @@ __device__ __forceinline__ void attn_q64_body(const AttnParams& p, int force_saf
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int r = (wave * 2 + i) * 8 + (lane_m >> 3);
-        ga[i] = (uint32_t)(r * D + ((lane_m & 7) ^ q64_swz_k(r)) * 8) * 2u;
+        ga[i] = (uint32_t)(r * D + ((lane_m & 7) ^ attn_swz_k(r)) * 8) * 2u;
       }
       const int l16m = lane_m & 15, h4m = lane_m >> 4;
-      int kofs_m[2];
-      {
-        const int key = 8 * (l16m >> 2) + (l16m & 3);
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) kofs_m[ks] = key * 128 + (((ks * 4 + h4m) ^ q64_swz_k(key)) << 4);
-      }
+      int kofs_m[2], vofs_m[2];                     // (the V^T offsets are not used: pass A reads K only)
+      attn_frag_offsets(l16m, h4m, 0, ATTN_VBASE, kofs_m, vofs_m);
       auto dma_group = [&](int set, int g) {      // tiles 4g .. 4g+3 (clamped: a re-fetch of the last tile) -> slots 4 set .. 4 set + 3
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
@@ -448,7 +388,7 @@ __device__ __forceinline__ void attn_q64_body(const AttnParams& p, int force_saf
               const int hh = 2 * (4 * g + t) + kg;      // (mask_half on this part's own lane values)
 #pragma unroll
               for (int bb = 0; bb < 2; ++bb) {
-                const int key0 = (hh >> 1) * KT + (hh & 1) * 32 + h4m * 8 + bb * 4;
+                const int key0 = attn_key0(hh, bb, h4m);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                   const bool dead = key0 + r >= p.Nk;
@@ -492,43 +432,13 @@ __device__ __forceinline__ void attn_q64_body(const AttnParams& p, int force_saf
     bool redo = force_safe != 0;
     if (!redo) {
       fast_pass();
-      // 2^-80 <= l <= 2^110 (NaN fails): see the header comment of ld_attn_pipe.hip
-      bool bad = false;
-#pragma unroll
-      for (int qb = 0; qb < 4; ++qb)
-        bad = bad || (!(ltot[qb] >= 8.2718061e-25f && ltot[qb] <= 1.2980742e33f) && (q0 + qb * 16 + l16 < p.Nq));
-      int* flags = (int*)(smem + 8 * KTILE_BYTES);
-      const bool wbad = __any(bad);
-      if (lane == 0) flags[wave] = wbad ? 1 : 0;
-      __syncthreads();
-      redo = false;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) redo = redo || flags[w] != 0;
-      __syncthreads();
+      redo = attn_window_vote<NW, 4>(smem, ltot, q0 + l16, p.Nq, lane, wave);
     }
     if (redo) safe_pass();
   }
-  // Every LDS-DMA of this workgroup has LANDED before the workgroup ends: the loops above run ahead of the tiles they consume (and,
-  // having no peeled tail, request tiles nobody reads); a wave that ended with buffer_load ... lds in flight would let the data
-  // arrive in LDS that may by then belong to the next workgroup on this CU.  (Round 5: added while hunting the co-residency bug
-  // that turned out to be the packed-fp32 one -- csrc/build.sh -- and kept: it measures at 0 us of a 3.6 ms launch.)
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-
+  attn_dma_drain();
 #pragma unroll
-  for (int qb = 0; qb < 4; ++qb) {
-    const int q = q0 + qb * 16 + l16;
-    const float inv = ltot[qb] > 0.f ? 1.0f / ltot[qb] : 0.f;
-    if (q < p.Nq) {
-      bf16_t* orow = p.O + (long)b * p.o_bs + (long)q * p.o_rs + h * D + h4 * 4;
-#pragma unroll
-      for (int db = 0; db < 4; ++db) {
-        u32x2_t w2;
-        w2[0] = pack_bf16x2(o[db][qb][0] * inv, o[db][qb][1] * inv);
-        w2[1] = pack_bf16x2(o[db][qb][2] * inv, o[db][qb][3] * inv);
-        *(u32x2_t*)(orow + db * 16) = w2;
-      }
-    }
-  }
+  for (int qb = 0; qb < 4; ++qb) attn_store_o(p, blk.b, blk.h, q0 + qb * 16 + l16, h4, ltot[qb], o[0][qb], o[1][qb], o[2][qb], o[3][qb]);
 #ifdef LD_Q64_TRACE
   if (p.kt_min && tid == 0) {
     unsigned hw, xcc;

@@ -7,6 +7,7 @@
 // accumulators, so the exponentials are 2^(s - max) <= 1 and no denominator can overflow or vanish.  No data-dependent branch, run to
 // run identical.  One workgroup per query block, dealt by the hardware.
 #include "ld_attn.h"
+#include "ld_attn_dev.h"
 
 namespace {
 
@@ -20,11 +21,9 @@ __global__ __launch_bounds__(256, 2) void ld_attn_q64_exact_kernel(AttnParams p)
 }  // namespace
 
 int ld_attn_q64_exact_launch(const AttnParams& p, hipStream_t st, AttnRan* ran) {
-  constexpr int SMEM = 8 * KTILE_BYTES + 64;
   static thread_local LdSmemCache cache{};
-  if (int rc = ld_ensure_dyn_smem((const void*)ld_attn_q64_exact_kernel, SMEM, &cache)) return rc;
   const int total = (int)((long)p.B * p.H * ((p.Npad + Q64_ROWS - 1) / Q64_ROWS));
-  *ran = {"ld_attn_q64_exact_kernel", nullptr, 0};          // a two-pass softmax: no window to leave
-  hipLaunchKernelGGL(ld_attn_q64_exact_kernel, dim3((unsigned)total), dim3(256), SMEM, st, p);
-  return ld_check_launch("ld_attn_fwd_bf16_exact(q64)");
+  return attn_launch(ld_attn_q64_exact_kernel, &cache, ATTN_SMEM_BYTES, dim3((unsigned)total), dim3(256), st, ran,
+                     AttnRan{"ld_attn_q64_exact_kernel", nullptr, 0},          // a two-pass softmax: no window to leave
+                     "ld_attn_fwd_bf16_exact(q64)", p);
 }

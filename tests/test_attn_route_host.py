@@ -121,3 +121,21 @@ def test_ops_wrapper_and_the_python_side_constant():
     assert all(r == (PLAIN if n < ops.ATTN_PIPELINED_MIN_TILES else Q64) for n, r in routes.items())
     # ... and the window form's minimum is the same number
     assert [n for n in range(1, 33) if _route(n * ops.ATTN_KEY_TILE, form="window") == Q64_WIN][0] == ops.ATTN_PIPELINED_MIN_TILES
+
+
+def test_vote_case_overflows_one_row_only():
+    """The input of test_attention_vote_across_waves (tests/test_gpu_variants.py) does what that test needs: in every head the
+    scaled row holds an exp2 exponent beyond 128 (its fast-pass denominator overflows fp32), every other row's exponents stay
+    tiny (denominators far inside [2^-80, 2^110]), and the fp32 reference is finite.  The scaled row's top exponent leads the
+    runner-up by more than 16: its softmax is one-hot beyond bf16, so the bf16 rounding of q * scale inside the kernels cannot
+    move its output."""
+    import torch
+    import attn_vote_case as c
+    q, k, v = c.inputs()
+    s = c.log2_scores(q, k)
+    top = s[:, :, c.ROW].topk(2, -1).values
+    assert (top[..., 0] > 128).all(), top
+    assert (top[..., 0] - top[..., 1] > 16).all(), top
+    others = torch.cat([s[:, :, :c.ROW], s[:, :, c.ROW + 1:]], 2)
+    assert others.abs().max().item() < 16
+    assert torch.isfinite(c.reference(q, k, v)).all()

@@ -171,6 +171,26 @@ print("HASH", h.hexdigest())
 """ % ROOT
 
 
+ATTN_VOTE_SNIPPET = r"""
+import sys, torch
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+from landiff_amd import ops
+import attn_vote_case as c
+q, k, v = (t.cuda() for t in c.inputs())
+Npad = (c.N + 127) // 128 * 128
+def pack(x):
+    o = torch.zeros(c.B, c.H, Npad, 64, device="cuda", dtype=x.dtype); o[:, :, :c.N] = x; return o
+out = torch.zeros(c.B, c.N, c.H * 64, device="cuda", dtype=torch.bfloat16)
+ops.attn_fwd(pack(q), pack(k), pack(v).transpose(2, 3).contiguous(), out, c.N, c.N, c.SCALE)
+ref = c.reference(q, k, v)
+err = (out.float() - ref).abs()
+rows = torch.arange(c.N, device="cuda") != c.ROW
+print("NAN", int(torch.isnan(out.float()).sum().item()))
+print("OTHERS", torch.nan_to_num(err[:, rows], nan=1e9).max().item())
+print("ROW", torch.nan_to_num(err[:, c.ROW], nan=1e9).max().item() / ref.abs().max().item())
+""" % (ROOT, os.path.join(ROOT, "tests"))
+
+
 def variants_lib() -> str:
     """Path of the variants build of the library (the measured alternatives live only there); __graft_entry__.build() makes it, and
     a tree that lacks it gets it built here (hipcc is on the GPU box too; a few minutes, once)."""
@@ -238,12 +258,30 @@ def test_attention_wave_tiles_bit_identical(cuda):
     looks like."""
     outs = []
     for env in ({"LD_ATTN_Q128": "0"}, {"LD_ATTN_Q64": "0", "LD_ATTN_Q128": "0"}, {"LD_ATTN_Q128": "2"},
-                {"LD_ATTN_Q128": "2", "LD_ATTN_NPRE": "36"}, {"LD_ATTN_Q128": "2", "LD_ATTN_NPRE": "52"}):
+                {"LD_ATTN_Q128": "2", "LD_ATTN_NPRE": "36"}, {"LD_ATTN_Q128": "2", "LD_ATTN_NPRE": "52"},
+                # the 8-wave workgroup of the 32-row tile: the one instantiation with two DMA pieces per wave and eight flag words
+                {"LD_ATTN_Q64": "0", "LD_ATTN_Q128": "0", "LD_ATTN_NW": "8"}):
         e = _env(env)                       # (the first two run on the shipped library, the 128-row tile on the variants build)
         r = subprocess.run([sys.executable, "-c", ATTN_HASH_SNIPPET], env=e, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         outs.append([l for l in r.stdout.splitlines() if l.startswith("HASH")][-1])
     assert all(o == outs[0] for o in outs[1:]), outs
+
+
+@pytest.mark.parametrize("env", [{}, {"LD_ATTN_Q64": "0", "LD_ATTN_NW": "4"}, {"LD_ATTN_Q64": "0", "LD_ATTN_NW": "8"}])
+def test_attention_vote_across_waves(cuda, env):
+    """One row of the last workgroup overflows the fast pass (tests/attn_vote_case.py; tests/test_attn_route_host.py checks the
+    input on the CPU), in the last wave that stores rows; no other row of the workgroup leaves the window.  The whole workgroup must
+    take the running-max pass: without that wave's flag reaching every wave, the row comes out NaN or zero (relative error 1).  Bounds:
+    the other rows the 2e-2 of test_attention_variants, the overflowing row the relative 0.2 of
+    test_attn_pipelined_overflow_falls_back (its softmax is one-hot: the expected error is the bf16 rounding of the output)."""
+    r = subprocess.run([sys.executable, "-c", ATTN_VOTE_SNIPPET], env=_env(env), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = {l.split()[0]: float(l.split()[1]) for l in r.stdout.splitlines() if l.split() and l.split()[0] in ("NAN", "OTHERS", "ROW")}
+    print(env, got)
+    assert got["NAN"] == 0, got
+    assert got["OTHERS"] < 2e-2, got
+    assert got["ROW"] < 0.2, got
 
 
 def test_variants_build_suite(cuda):
