@@ -1,6 +1,7 @@
 // Shared by the bf16 / fp8 GEMM and implicit-GEMM convolution files (ld_gemm*.hip): the kernel parameter block, the fused
 // epilogues (device code), the LDS-DMA staging helpers and the host-side launch helpers.  ld_gemm.hip plans a call (which kernel
-// family, which tiles); ld_gemm_2stage.hip, ld_gemm_8p.hip, ld_gemm_fp8.hip and ld_gemm_variants.hip hold the kernels and their launchers.
+// family, which tiles); ld_gemm_2stage.hip, ld_gemm_8p.hip, ld_gemm_fp8.hip and ld_gemm_variants.hip hold the kernels and their launchers;
+// ld_gemm_8p_dev.h holds what the kernels share around the main loop (raster, tile source, addresses, counted waits, tile walk).
 #pragma once
 #include "ld_common.h"
 #include "ld_mx.h"
@@ -45,8 +46,9 @@ struct GemmParams {
   const bf16_t* qn_w; const bf16_t* qn_b; const bf16_t* kn_w; const bf16_t* kn_b;   // QK-LayerNorm(64) weights
   int heads, Ntok, Npad;
   float qk_eps;
-  // 8-phase kernels: the launch covers tiles [tile_begin, tile_end) of the 256 x 256 raster (tile_end == 0: all of them).  The
-  // whole rounds of the chip go to ld_gemm8p_kernel, the partial last round to ld_gemm8p_n128_kernel as 256 x 128 half tiles.
+  // 8-phase kernels: the launch covers tiles [tile_begin, tile_end) of the 256 x 256 raster (tile_end == 0: all of them);
+  // walk_tiles (ld_gemm_8p_dev.h) is the one reader.  The whole rounds of the chip go to ld_gemm8p_kernel, the partial last round
+  // to ld_gemm8p_n128_kernel as 256 x 128 half tiles.
   int tile_begin, tile_end;
   // convolutions only: GroupNorm partial statistics of the bf16 output, [ceil(M / 64)][N / 4][2] fp32 = (sum, sum of squares) of
   // every 64-row x 4-channel patch, written by the epilogue that holds the values anyway (ld_conv_cl_bf16_gn); null: none

@@ -3,7 +3,7 @@
 // loop on fp8 operands (ld_gemm_f8_kernel) and, in the variants build, the register-staged round-1 loop (ld_gemm_w4r_kernel).
 // These three share one file on purpose: the compiler's register allocation for the 32x32x16 forms of ld_gemm_kernel and for
 // ld_gemm_w4r_kernel depends on ld_gemm_f8_kernel being in the same module (compared per function against the one-file build).
-#include "ld_gemm.h"
+#include "ld_gemm_8p_dev.h"     // the raster and the addresses (the 8-phase family's header states them once)
 
 namespace ldgemm {
 namespace {
@@ -29,17 +29,9 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN >= 16) ? 4 : 2) void ld_gemm
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave / WN, wc = wave % WN;
 
-  // Tile order: blockIdx -> XCD-contiguous logical id (each XCD has a private 4 MB L2) -> grouped raster: the ~64
-  // tiles resident on one XCD form a GROUP_M x (64/GROUP_M) patch, so an A panel and a W panel are each re-read from
-  // L2 ~8 times instead of W being re-streamed from MALL/HBM for every row of tiles.
   const int nbm = (p.M - p.m_begin + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-  const int bid = xcd_remap(blockIdx.x, nbm * nbn);
-  const int gm_sz = p.group_m;
-  const int per_group = gm_sz * nbn;
-  const int group = bid / per_group, in_group = bid - group * per_group;
-  const int first_m = group * gm_sz;
-  const int rows_here = (nbm - first_m) < gm_sz ? (nbm - first_m) : gm_sz;
-  const int m0 = p.m_begin + (first_m + in_group % rows_here) * BM, n0 = (in_group / rows_here) * BN;
+  int m0, n0;
+  tile_origin<BM, BN>(blockIdx.x, nbm, nbn, p.group_m, p.m_begin, m0, n0);      // one tile per workgroup, in the grouped raster's order
 
   // ---- per-thread source row offsets ----
   // element offsets, zero-extended where they are added to the pointers: < 2^32 for a convolution, whose padded input
@@ -48,13 +40,10 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN >= 16) ? 4 : 2) void ld_gemm
 #pragma unroll
   for (int i = 0; i < A_LOADS; ++i) {
     const int r = (wave * A_LOADS + i) * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((r >> 1) & 7);   // source-side swizzle
+    const int chunk = swz_chunk(lane, r);
     int gm = m0 + r; gm = gm < p.M ? gm : p.M - 1;
     if (CONV) {
-      const int hw = p.H * p.W_;
-      const int t = gm / hw, rem = gm - t * hw;
-      const int h = rem / p.W_, w = rem - h * p.W_;
-      offA[i] = (uint32_t)((((long)t * p.Hp + h) * p.Wp + w) * p.Cin + chunk * 8);
+      offA[i] = (uint32_t)(conv_row_elems(p, gm) + chunk * 8);
     } else {
       offA[i] = (uint32_t)((long)gm * p.lda + chunk * 8);
     }
@@ -62,7 +51,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN >= 16) ? 4 : 2) void ld_gemm
 #pragma unroll
   for (int i = 0; i < B_LOADS; ++i) {
     const int r = (wave * B_LOADS + i) * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((r >> 1) & 7);
+    const int chunk = swz_chunk(lane, r);
     int gn = n0 + r; gn = gn < p.N ? gn : p.N - 1;
     offW[i] = (uint32_t)((long)gn * p.K + chunk * 8);
   }
@@ -71,16 +60,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN >= 16) ? 4 : 2) void ld_gemm
   const int cpt = CONV ? p.Cin / BK : 1;   // K-tiles per tap
 
   auto stage = [&](int buf, int kt) {
-    long koffA;
-    if (CONV) {
-      const int tap = kt / cpt, c0 = (kt - tap * cpt) * BK;
-      const int khw = p.kH * p.kW;
-      const int dt = tap / khw, r2 = tap - dt * khw;
-      const int dh = r2 / p.kW, dw = r2 - dh * p.kW;
-      koffA = (((long)dt * p.Hp + dh) * p.Wp + dw) * p.Cin + c0;
-    } else {
-      koffA = (long)kt * BK;
-    }
+    const long koffA = CONV ? conv_tap_elems(p, kt, cpt) : (long)kt * BK;
     const long koffW = (long)kt * BK;
     char* base = smem + buf * STAGE;
 #pragma unroll
@@ -267,26 +247,20 @@ __global__ __launch_bounds__(512, 2) void ld_gemm_f8_kernel(GemmParams p) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave / WN, wc = wave % WN;
   const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-  const int bid = xcd_remap(blockIdx.x, nbm * nbn);
-  const int gm_sz = p.group_m;
-  const int per_group = gm_sz * nbn;
-  const int group = bid / per_group, in_group = bid - group * per_group;
-  const int first_m = group * gm_sz;
-  const int rows_here = (nbm - first_m) < gm_sz ? (nbm - first_m) : gm_sz;
-  const int m0 = (first_m + in_group % rows_here) * BM, n0 = (in_group / rows_here) * BN;
+  int m0, n0;
+  tile_origin<BM, BN>(blockIdx.x, nbm, nbn, p.group_m, 0, m0, n0);
   // LDS-DMA through raw buffer descriptors based at the tile origin (rows past M / N read as zeros, no clamping): the
   // wave-uniform part of every address -- K-tile, 16-row step between a wave's pieces -- is the scalar offset, the per-lane
   // part is ONE 32-bit offset per piece parity (the source-side swizzle key (row >> 1) & 7 repeats every 16 rows).
   const long ldab = p.lda, ldwb = p.K;
-  const auto clip = [](long v) { return (int)(v < 0x7fffffffL ? v : 0x7fffffffL); };
   const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.A + (long)m0 * ldab), 0, clip((long)(p.M - m0) * ldab), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.W + (long)n0 * ldwb), 0, clip((long)(p.N - n0) * ldwb), 0x00020000);
   uint32_t voA[2], voW[2];
 #pragma unroll
   for (int par = 0; par < 2; ++par) {
     const int ra = (wave * A_LOADS + par) * 8 + (lane >> 3), rb = (wave * B_LOADS + par) * 8 + (lane >> 3);
-    voA[par] = (uint32_t)(ra * ldab + (((lane & 7) ^ ((ra >> 1) & 7)) << 4));
-    voW[par] = (uint32_t)(rb * ldwb + (((lane & 7) ^ ((rb >> 1) & 7)) << 4));
+    voA[par] = (uint32_t)(ra * ldab + (swz_chunk(lane, ra) << 4));
+    voW[par] = (uint32_t)(rb * ldwb + (swz_chunk(lane, rb) << 4));
   }
   const int sa16 = (int)(16 * ldab), sw16 = (int)(16 * ldwb);
   const int nk = p.K / KB;
@@ -443,20 +417,13 @@ __global__ __launch_bounds__(256, 1) void ld_gemm_w4r_kernel(GemmParams p) {
   const int wr = wave >> 1, wc = wave & 1;
 
   const int nbm = (p.M - p.m_begin + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-  const int bid = xcd_remap(blockIdx.x, nbm * nbn);
-  const int gm_sz = p.group_m;
-  const int per_group = gm_sz * nbn;
-  const int group = bid / per_group, in_group = bid - group * per_group;
-  const int first_m = group * gm_sz;
-  const int rows_here = (nbm - first_m) < gm_sz ? (nbm - first_m) : gm_sz;
-  const int m0 = p.m_begin + (first_m + in_group % rows_here) * BM, n0 = (in_group / rows_here) * BN;
+  int m0, n0;
+  tile_origin<BM, BN>(blockIdx.x, nbm, nbn, p.group_m, p.m_begin, m0, n0);
 
   // this wave stages rows [wave*64, wave*64+64) of the A tile and of the W tile: 8 + 8 loads of 8 rows x 128 B per K-tile
   const long ldab = p.lda * 2, ldwb = (long)p.K * 2;
-  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.A + (long)m0 * ldab), 0,
-      (int)(((long)(p.M - m0) * ldab) < 0x7fffffffL ? ((long)(p.M - m0) * ldab) : 0x7fffffffL), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.W + (long)n0 * ldwb), 0,
-      (int)(((long)(p.N - n0) * ldwb) < 0x7fffffffL ? ((long)(p.N - n0) * ldwb) : 0x7fffffffL), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsA = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.A + (long)m0 * ldab), 0, clip((long)(p.M - m0) * ldab), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsW = __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)p.W + (long)n0 * ldwb), 0, clip((long)(p.N - n0) * ldwb), 0x00020000);
   const int rl = lane >> 3, cl = lane & 7;                         // row within the 8-row group, 16-byte chunk
   const uint32_t voA = (uint32_t)((wave * 64 + rl) * ldab + cl * 16);
   const uint32_t voW = (uint32_t)((wave * 64 + rl) * ldwb + cl * 16);

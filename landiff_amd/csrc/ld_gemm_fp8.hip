@@ -1,8 +1,9 @@
 // fp8 (OCP e4m3) GEMMs for the DiT's large linear layers: MXFP8 operands on the persistent 8-phase loop (ld_gemm8p_mx_kernel), the
 // two quantisers, and the fp8 / MXFP8 entry points.  (Per-row scaled and MXFP8 operands on the two-stage loop: ld_gemm_f8_kernel,
 // ld_gemm_2stage.hip.)
-// ld_gemm.h: what the GEMM files share.
-#include "ld_gemm.h"
+// ld_gemm.h: what the GEMM files share; ld_gemm_8p_dev.h: the raster, addresses, MFMA section and derived counted waits that
+// ld_gemm8p_mx_kernel takes from the bf16 8-phase kernels.
+#include "ld_gemm_8p_dev.h"
 #include "../../include/landiff_hip.h"
 
 namespace ldgemm {
@@ -25,6 +26,11 @@ namespace {
 //     scale layout S0) of each, packed four to a register -- the MFMA's op_sel picks the byte.
 // LDS: [K-tile buffer 0: 64 KB][scale strips: 2 x 2 KB][K-tile buffer 1: 64 KB]; the epilogue staging at the end of the 160 KB stays
 // clear of buffer 0 and the strips.
+// From ld_gemm_8p_dev.h: the raster, the swizzle and fragment addresses, bar(), mfma_section and the waits of StagePlan<2, 2, 1>.
+// The tile source (with its scale strip), the K-tile and the tile walk below stay this kernel's own text, although they restate
+// ktile_2phase / tile_main_loop / walk_tiles: built from those, with equal barrier, MFMA and counted-wait counts and no scratch, the
+// K = 1920 GEMMs of this kernel measured 2-3 % slower than the parent build (143 -> 148..150 us at 35552 x 1920 x 1920, outside the
+// spread of two files of the parent build), the only arms of profiles/gemm_refactor.txt to do so.
 // ------------------------------------------------------------------------------------------------
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void ld_gemm8p_mx_kernel(GemmParams p) {
@@ -36,6 +42,7 @@ __global__ __launch_bounds__(512, 2) void ld_gemm8p_mx_kernel(GemmParams p) {
   constexpr int EPI_OFF = (LD_LDS_TOTAL - EPI_BYTES) & ~15;
   constexpr bool PREFETCH = EPI_OFF >= BUF1 && EPI != EPI_QKV;
   constexpr bool SWAPACC = EPI != EPI_QKV;
+  using Plan = StagePlan<2, 2, 1>;                        // LDS-DMA instructions per wave: a half-tile = 2, a scale strip = 1
   static_assert(BUF1 + KBUF <= LD_LDS_TOTAL, "LDS layout");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
@@ -44,17 +51,7 @@ __global__ __launch_bounds__(512, 2) void ld_gemm8p_mx_kernel(GemmParams p) {
   const int wr = wave >> 2, wc = wave & 3;
   const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
   const int ntiles = nbm * nbn;
-  const int gm_sz = p.group_m;
-  auto tile_origin = [&](int v, int& m0, int& n0) {       // (ld_gemm8p_kernel's)
-    const int bid = xcd_remap(v, ntiles);
-    const int per_group = gm_sz * nbn;
-    const int group = bid / per_group, in_group = bid - group * per_group;
-    const int first_m = group * gm_sz;
-    const int rows_here = (nbm - first_m) < gm_sz ? (nbm - first_m) : gm_sz;
-    m0 = (first_m + in_group % rows_here) * BM;
-    n0 = (in_group / rows_here) * BN;
-  };
-  const auto clip = [](long v) { return (int)(v < 0x7fffffffL ? v : 0x7fffffffL); };
+  auto origin = [&](int v, int& m0, int& n0) { tile_origin<BM, BN>(v, nbm, nbn, p.group_m, 0, m0, n0); };
   const long ldab = p.lda, ldwb = p.K;                    // row strides in bytes
   struct Src { const unsigned char* a; const unsigned char* w; const unsigned char* s; int a_bytes, w_bytes, s_bytes; };
   const bool a_wave = wave < 4;                           // which operand's scale dwords this wave fetches
@@ -77,7 +74,7 @@ __global__ __launch_bounds__(512, 2) void ld_gemm8p_mx_kernel(GemmParams p) {
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int lr = wave * 16 + i * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((lr >> 1) & 7);
+    const int chunk = swz_chunk(lane, lr);
     const int tm = (lr >> 6) * 128 + (lr & 63);
     const int tn = (lr >> 5) * 64 + (lr & 31);
     offA[i] = (uint32_t)((long)tm * ldab + chunk * 16);
@@ -108,8 +105,6 @@ __global__ __launch_bounds__(512, 2) void ld_gemm8p_mx_kernel(GemmParams p) {
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)s.s, 0, s.s_bytes, 0x00020000);
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(smem + OFF + wave * 256), 4, offS, kt * sslab, 0, 0);
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
   auto stage_ktile0 = [&](const Src& s) {                 // 9 LDS-DMA instructions per wave
     stage_a(s, I0{}, I0{}, 0); stage_w(s, I0{}, I0{}, 0); stage_s(s, I0{}, 0); stage_w(s, I0{}, I1{}, 0); stage_a(s, I0{}, I1{}, 0);
   };
@@ -117,9 +112,8 @@ __global__ __launch_bounds__(512, 2) void ld_gemm8p_mx_kernel(GemmParams p) {
   int rdA[2], rdB[2];
 #pragma unroll
   for (int ks = 0; ks < 2; ++ks) {                        // 16-byte chunk g and chunk 4 + g of the row: the operand's two halves
-    const int c = (ks * 4 + (lane >> 4)) ^ (((lane & 15) >> 1) & 7);
-    rdA[ks] = (wr * 64 + (lane & 15)) * 128 + (c << 4);
-    rdB[ks] = (wc * 32 + (lane & 15)) * 128 + (c << 4);
+    rdA[ks] = frag_addr(wr * 64, lane, ks);
+    rdB[ks] = frag_addr(wc * 32, lane, ks);
   }
   f32x4_t acc[8][4];
   u32x4_t a[4][2], b0[2][2], b1[2][2];
@@ -165,26 +159,11 @@ __global__ __launch_bounds__(512, 2) void ld_gemm8p_mx_kernel(GemmParams p) {
       else
         acc[H * 4 + i][G * 2 + j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(frag(a[i]), frag(b[j]), acc[H * 4 + i][G * 2 + j], 0, 0, i, sA[H], 2 * G + j, sB);
     };
-    using I2 = std::integral_constant<int, 2>;
-    using I3 = std::integral_constant<int, 3>;
     one(I0{}, I0{}); one(I0{}, I1{}); one(I1{}, I0{}); one(I1{}, I1{});
     one(I2{}, I0{}); one(I2{}, I1{}); one(I3{}, I0{}); one(I3{}, I1{});
   };
   auto mma2 = [&](auto hc, auto g0c, u32x4_t (&bA)[2][2], auto g1c, u32x4_t (&bB)[2][2]) {
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_sched_barrier(0);
-    if (wave_live) {
-      __builtin_amdgcn_s_setprio(1);
-      mma1(hc, g0c, bA);
-      mma1(hc, g1c, bB);
-      __builtin_amdgcn_s_setprio(0);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  auto bar = [&]() {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
+    mfma_section(wave_live, [&]() { mma1(hc, g0c, bA); mma1(hc, g1c, bB); });
   };
   // LDS-DMA instructions per wave: a half-tile = 2, a scale strip = 1.  In flight on entry of P0(kt), oldest first:
   // A_1(kt) [2], then A_0 / B_0 / S(kt + 1) [5]
@@ -200,20 +179,20 @@ __global__ __launch_bounds__(512, 2) void ld_gemm8p_mx_kernel(GemmParams p) {
     read_scales(Bc{});
     if (kt + 1 < nk) {
       stage_w(src, Nc{}, I1{}, kt + 1); stage_a(src, Nc{}, I1{}, kt + 1);
-      asm volatile("s_waitcnt vmcnt(9) lgkmcnt(0)" ::: "memory");   // A_1(kt) has landed
+      wait_vm<Plan::P0, true>();   // A_1(kt) has landed
     } else {
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      wait_vm<0, true>();
     }
     bar(); mma2(I0{}, I0{}, b0, I1{}, b1); bar();
     // P1.  In flight: A_0 / B_0 / S(kt + 1) [5], B_1 / A_1(kt + 1) [4]
     read_a(Bc{}, I1{});
     if (kt + 2 < nk) {
       stage_a(src, Bc{}, I0{}, kt + 2); stage_w(src, Bc{}, I0{}, kt + 2); stage_s(src, Bc{}, kt + 2);
-      asm volatile("s_waitcnt vmcnt(7) lgkmcnt(0)" ::: "memory");   // A_0 / B_0 / S / B_1 of K-tile kt + 1 have landed
+      wait_vm<Plan::P1, true>();   // A_0 / B_0 / S / B_1 of K-tile kt + 1 have landed
     } else if (kt + 1 < nk) {
-      asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
+      wait_vm<Plan::P1_TAIL, true>();
     } else {
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+      wait_vm<0, true>();
     }
     bar(); mma2(I1{}, I1{}, b1, I0{}, b0); bar();
   };
@@ -221,7 +200,7 @@ __global__ __launch_bounds__(512, 2) void ld_gemm8p_mx_kernel(GemmParams p) {
   bool k0_staged = false;
   for (int v = blockIdx.x; v < ntiles; v += gridDim.x) {
     int m0, n0;
-    tile_origin(v, m0, n0);
+    origin(v, m0, n0);
     src = tile_src(m0, n0);
     wave_live = n0 + wc * 64 < p.N;
 #pragma unroll
@@ -233,9 +212,9 @@ __global__ __launch_bounds__(512, 2) void ld_gemm8p_mx_kernel(GemmParams p) {
     if (!k0_staged) stage_ktile0(src);
     if (nk > 1) {
       stage_a(src, I1{}, I0{}, 1); stage_w(src, I1{}, I0{}, 1); stage_s(src, I1{}, 1);
-      asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
+      wait_vm<Plan::PROLOGUE>();
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      wait_vm<0>();
     }
     bar();
     if (wr == 1) bar();
@@ -254,7 +233,7 @@ __global__ __launch_bounds__(512, 2) void ld_gemm8p_mx_kernel(GemmParams p) {
     k0_staged = false;
     if (PREFETCH && vn < ntiles) {
       int m1, n1;
-      tile_origin(vn, m1, n1);
+      origin(vn, m1, n1);
       nsrc = tile_src(m1, n1);
       k0_staged = true;
     }

@@ -223,6 +223,49 @@ def test_gemm_route_exact(cuda, case):
     _check_sentinels(bits, M, N)
 
 
+# The smallest shape that the planner sends down the half-tile route with every edge in the tail: 65 x 8 = 520 tiles = two whole
+# rounds + 8 tail tiles, among them the bottom-right corner tile -- a ragged last row (37 of 256) and a half-wide last column (120 of
+# 256: its second half tile is empty).
+HALF_TAIL_CORNER = (64 * 256 + 37, 7 * 256 + 120, 1024)
+
+
+def run_half_tail_corner(dev):
+    """Exact operands, bias + residual IN PLACE (out is resid, preset) on HALF_TAIL_CORNER, the output inside the sentinel buffer:
+    bit equality with the float64 reference.  A tile computed by both launches of the split adds its product twice.  (Also run in
+    a child process on the variants build: tests/test_gpu_variants.py.)"""
+    from landiff_amd import ops
+    M, N, K = HALF_TAIL_CORNER
+    lab = _tile_launch(M, N, 6)
+    assert int(lab.sum()) == 8 and int(lab[-1, -1]) == 1, "the tail is 8 tiles and holds the corner tile"
+    a, w, g = _operands(M, N, K, True, zlib.crc32(b"half_tail_corner"), dev, 64)
+    bits, out = _sentinel_buffer(M, N, N + 64, BF, dev)
+    out.copy_(_small((M, N), g, dev, -8, 8, True))
+    epi = dict(bias=_small((N,), g, dev, -4, 4, True), resid=out)
+    assert _route(M, N, K, out.stride(0), **epi) == (6, EPI_GENERIC)
+    ref, _ = _reference(a, w, dict(epi, resid=out.clone()), True, N)
+    ops.gemm(a, w, out=out, **epi)
+    torch.cuda.synchronize()
+    got = out.double()
+    bad = got != ref
+    if bool(bad.any()):
+        nbm, nbn = lab.shape
+        pad = torch.zeros(nbm * 256, nbn * 256, dtype=torch.bool, device=dev)
+        pad[:M, :N] = bad
+        per_tile = pad.view(nbm, 256, nbn, 256).any(dim=3).any(dim=1).cpu()
+        twice = got == ref + (a.double() @ w.double().t() + epi["bias"].double())      # (exact operands: bias + product, once more)
+        raise AssertionError(f"{int(bad.sum())} of {M * N} elements differ in {int(per_tile[lab == 0].sum())} tiles of the whole rounds and "
+                             f"{int(per_tile[lab == 1].sum())} of the 8 tail tiles, first at {tuple(bad.nonzero()[0].tolist())}; "
+                             f"{int((twice & bad).sum())} of them hold the product added twice; NaN: {int(torch.isnan(got).sum())}")
+    _check_sentinels(bits, M, N)
+
+
+@pytest.mark.parametrize("persist", ["1", "0"], ids=["persistent", "one_workgroup_per_tile"])
+def test_gemm_half_tail_corner_inplace(cuda, monkeypatch, persist):
+    """HALF_TAIL_CORNER with persistent workgroups and with LD_GEMM_PERSIST=0 (the knobs are re-read per call: LD_TUNING)."""
+    monkeypatch.setenv("LD_GEMM_PERSIST", persist)
+    run_half_tail_corner(cuda)
+
+
 # (id, route, epilogue kind, M, N, K, lda pad, act, epilogue form)
 RANDOM_CASES = [
     ("dit_h4_gelu_tanh", 6, EPI_GELU, M_DIT, 4 * D, D, 64, "gelu_tanh", "bias"),

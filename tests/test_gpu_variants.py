@@ -233,6 +233,17 @@ def test_gemm_main_loop_variants(cuda, env):
     assert _run(GEMM_SNIPPET, env) < 1e-2
 
 
+def test_gemm_half_tail_corner_software_pipelined(cuda):
+    """The smallest half-tile-route shape with an in-place residual (tests/test_gpu_gemm_routes.py: run_half_tail_corner) with the
+    whole rounds on the software-pipelined loop: it computes the tiles of ITS range only, the tail tiles are the half-tile kernel's.
+    (Before the GEMM kernels shared one tile walk, ld_gemm_sp_kernel ignored the range, computed the tail tiles too, and an in-place
+    residual got their product twice.)"""
+    code = ("import sys; sys.path[:0] = [%r, %r]; import test_gpu_gemm_routes as t; t.run_half_tail_corner('cuda'); print('CORNER OK')"
+            % (ROOT, os.path.join(ROOT, "tests")))
+    r = subprocess.run([sys.executable, "-c", code], env=_env({"LD_GEMM_SP": "1"}), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "CORNER OK" in r.stdout, r.stderr[-2000:]
+
+
 @pytest.mark.parametrize("env", [{"LD_ATTN_SAFE": "1"}, {"LD_ATTN_Q64": "0"}, {"LD_ATTN_Q64": "0", "LD_ATTN_SAFE": "1"}, {"LD_ATTN_Q64": "0", "LD_ATTN_NW": "8"}, {"LD_ATTN_Q64": "0", "LD_ATTN_NW": "8", "LD_ATTN_SAFE": "1"}, {"LD_ATTN_VARIANT": "9"}, {"LD_ATTN_VARIANT": "1"}, {"LD_ATTN_VARIANT": "4"},
                                  {"LD_ATTN_VARIANT": "8"}, {"LD_ATTN_VARIANT": "8", "LD_ATTN_SAFE": "1"}, {"LD_ATTN_VARIANT": "8", "LD_ATTN_NW": "8"},
                                  {"LD_ATTN_Q64": "0", "LD_ATTN_MSUM": "0"}, {"LD_ATTN_Q64": "0", "LD_ATTN_MSUM": "0", "LD_ATTN_SAFE": "1"},

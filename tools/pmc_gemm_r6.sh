@@ -1,6 +1,8 @@
 #!/bin/bash
-# rocprofv3 --pmc passes (SQ, LDS, GRBM: one pass each) over the four DiT GEMM shapes for two builds of the library -- the round-6
-# two-phase loop (shipped) and -DLD_GEMM_PH4 (rounds 3-5: four phases; tools/build_variant.sh ph4 ld_gemm.hip -DLD_GEMM_PH4=1) -> $1
+# rocprofv3 --pmc passes (SQ, LDS, GRBM: one pass each) over the four DiT GEMM shapes for two builds of the library -- the shipped
+# one and landiff_amd/variants/lib_ph4.so (tools/build_variant.sh ph4 <file> <flags>).  Round 6 compared the two-phase loop with
+# the four-phase K-tile of rounds 3-5 this way (profiles/r06_gemm_pmc_sq_two_phase.txt); that K-tile has left the sources since
+# (git history), so lib_ph4.so is whatever second build is to be compared -> $1
 export TMPDIR=/tmp
 out=$1; mkdir -p gpurun_out/pmc
 : > $out
