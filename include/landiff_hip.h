@@ -34,7 +34,8 @@ extern "C" {
  * ld_gemv_wide, ld_llm_decode_forward_wide and ld_llm_sample_advance_wide joined later, and so did ld_absdiff_sums,
  * ld_residual_sub, ld_residual_add, ld_attn_fwd_bf16_window, ld_attn_window_plan, ld_unpatchify_cfg_keep, ld_unpatchify_cond, ld_latent_pin and ld_mask_to_latent (additions do not change
  * the number: no existing signature moved).  16: ld_attn_route was added; ld_resize_u8 and ld_resize_mask_u8 joined later
- * (additions again).  17: ld_clip_diff_u8 and ld_clip_ssim_u8 were added; ld_retime_u8 joined later (an addition). */
+ * (additions again).  17: ld_clip_diff_u8 and ld_clip_ssim_u8 were added; ld_retime_u8 joined later (an addition), and so did
+ * ld_jpeg_size, ld_jpeg_coefs_u8, ld_jpeg_entropy_i16 and ld_jpeg_encode_u8 (additions again). */
 #define LD_ABI_VERSION 17
 
 int ld_version(void);
@@ -682,6 +683,59 @@ int ld_resize_mask_u8(const uint8_t* src, uint8_t* dst, const int32_t* frame_idx
 int ld_retime_u8(const uint8_t* src, uint8_t* dst, const int32_t* src_idx, const int32_t* phase_p, int32_t q, int16_t* mv,
                  int32_t* sad, int64_t F, int64_t n_out, int64_t H, int64_t W, int64_t C, int32_t search, int32_t penalty,
                  int32_t max_sad, void* stream);
+
+/* ---- the encode stage (ld_jpeg.hip; landiff_amd/encode.py) ----
+ * Baseline sequential JPEG of uint8 RGB frames, integer arithmetic only, the restart interval one MCU row: every MCU row of every
+ * frame is an independent byte-aligned segment (DC predictors reset, the last byte padded with 1-bits, every 0xFF followed by 0x00).
+ * subsampling: 420 (MCU 16 x 16, six blocks Y00 Y01 Y10 Y11 Cb Cr) or 444 (MCU 8 x 8, three blocks).  Frames whose size is no
+ * multiple of the MCU are extended by edge replication.  The arithmetic (DESIGN 8.12 states every rounding; tests/jpeg_ref.py
+ * restates it): Y, Cb, Cr by the JFIF matrix in 16-bit fixed point, (.. + 32768) >> 16, clamped to 0..255; 4:2:0 chroma = the rounded
+ * mean of the 2 x 2 cell's converted values; - 128; a separable 8 x 8 DCT, each pass sqrt(8) x the 1-D transform with 13-bit constants, t = (sum + 256)
+ * >> 9 after the rows, c8 = (sum + 65536) >> 17 after the columns (8 x the coefficient); q = sign(c8) (|c8| + 4 t) / (8 t) with the quantiser t =
+ * clamp((base s + 50) / 100, 1, 255), s = 5000 / quality below 50, else 200 - 2 quality; AC clamped to +-1023; zigzag order; Annex
+ * F.1.2 entropy coding with the given Huffman tables.
+ * `tables`: LD_JPEG_TABLE_WORDS int32 on the device, built by the caller (landiff_amd/encode.py device_tables: the one place the
+ * tables are stated): [0, 64) the DCT matrix K[u][x]; [64, 192) the base quantisation tables, luma then chroma, in zigzag order;
+ * [192, 256) the zigzag position of coefficient [v][u]; [256, 272) and [272, 288) the DC codes of luma and chroma by category;
+ * [288, 544) and [544, 800) the AC codes of luma and chroma by (run << 4 | size); a code word is code | length << 16.
+ * frames [F][H][W][3] with byte strides: row_stride >= 3 W between rows, frame_stride between frames.  All offsets are 64-bit; two
+ * runs give the same bits.  LD_ERR_INVALID: a null or misaligned pointer (tables 4, coefficients 16, int64 arrays 8 bytes), quality
+ * outside 1..100, an empty shape, strides that do not hold a frame, a capacity below ld_jpeg_size's.  LD_ERR_UNSUPPORTED: another
+ * subsampling, W > 8192 or H > 65535 (more than 3072 blocks in a segment).  Both before any launch.
+ *
+ * ld_jpeg_size: the sizes a caller allocates by, for F frames of H x W (negative: the refusal's code).  FRAME_BLOCKS: 8 x 8 blocks
+ * per frame; SEGMENTS: segments (MCU rows) per frame; SEGMENT_BLOCKS: blocks per segment; SEGMENT_BYTES: the most bytes a segment
+ * can take = 2 ceil(SEGMENT_BLOCKS * 1658 / 8) (the longest block is 20 + 63 * 26 bits, stuffing at most doubles the bytes);
+ * STREAM_BYTES: F (header_bytes + SEGMENTS (SEGMENT_BYTES + 2)), what ld_jpeg_encode_u8's `out` must hold.  The kernels never cut
+ * anything to fit: a capacity below the bound is refused. */
+#define LD_JPEG_TABLE_WORDS 800
+#define LD_JPEG_SIZE_FRAME_BLOCKS 0
+#define LD_JPEG_SIZE_SEGMENTS 1
+#define LD_JPEG_SIZE_SEGMENT_BLOCKS 2
+#define LD_JPEG_SIZE_SEGMENT_BYTES 3
+#define LD_JPEG_SIZE_STREAM_BYTES 4
+int64_t ld_jpeg_size(int32_t what, int64_t F, int64_t H, int64_t W, int32_t subsampling, int64_t header_bytes);
+
+/* pixels -> quantised coefficients int16 [F][FRAME_BLOCKS][64]: blocks in scan order (MCUs row by row, an MCU's blocks in the order
+ * above), a block's coefficients in zigzag order. */
+int ld_jpeg_coefs_u8(const uint8_t* frames, int64_t frame_stride, int64_t row_stride, const int32_t* tables, int16_t* coefs,
+                     int64_t F, int64_t H, int64_t W, int32_t subsampling, int32_t quality, void* stream);
+
+/* coefficients int16 [n_seg][mcus_per_row * (6 or 3)][64] -> the entropy-coded, stuffed bytes of every segment, without a marker:
+ * segs [n_seg][seg_capacity] (seg_capacity >= SEGMENT_BYTES of the row), seg_len int64 [n_seg].  Any int16 values: AC within
+ * +-1023 and DC differences within +-2047 are the caller's to keep (larger ones have no code). */
+int ld_jpeg_entropy_i16(const int16_t* coefs, const int32_t* tables, uint8_t* segs, int64_t seg_capacity, int64_t* seg_len,
+                        int64_t n_seg, int64_t mcus_per_row, int32_t subsampling, void* stream);
+
+/* pixels -> one contiguous stream per frame in `out`: frame f's bytes are out[offsets[f] .. offsets[f] + lengths[f]), the frames
+ * back to back from 0 (offsets, lengths: int64 [F] on the device).  A stream is `header` (header_bytes bytes on the device: SOI ..
+ * SOS, equal for every frame of the call; the caller builds it, DRI = MCUs per row), then per MCU row its segment and RST(row mod 8),
+ * EOI after the last.  Workspaces: coefs_ws int16 [F][FRAME_BLOCKS][64]; seg_ws int64 [2][F * SEGMENTS].  Four launches: the
+ * coefficients, a counting pass of the entropy coder (every segment's stuffed length), the layout (a scan), the writing pass. */
+int ld_jpeg_encode_u8(const uint8_t* frames, int64_t frame_stride, int64_t row_stride, const int32_t* tables,
+                      const uint8_t* header, int64_t header_bytes, int16_t* coefs_ws, int64_t* seg_ws, uint8_t* out,
+                      int64_t out_capacity, int64_t* offsets, int64_t* lengths, int64_t F, int64_t H, int64_t W,
+                      int32_t subsampling, int32_t quality, void* stream);
 
 /* ---- clip comparison (ld_metrics.hip; landiff_amd/metrics.py) ----
  * Two uint8 channels-last clips a, b [F][H][W][C], C 1 or 3 (the pipeline's output layout), and an optional keep-mask [F][H][W] u8

@@ -119,7 +119,23 @@ def parse_args(argv=None):
                              "block-matched interpolation looks like on a trained checkpoint's output is not measured.")
     parser.add_argument("--out_search", type=int, default=None, metavar="R",
                         help="With --out_fps: the block search range in pixels per axis, 0..32 (default 8, untuned; 0: a cross-fade).")
+    parser.add_argument("--video_encoder", choices=("host", "gpu"), default="host",
+                        help="gpu: every video is written as a Motion-JPEG <name>.avi whose frames are encoded on the GPU (baseline "
+                             "JPEG in integer arithmetic, one restart interval per MCU row; landiff_amd/encode.py), with "
+                             "<name>_encode.json beside it; with --out_fps the retimed frames never leave the device unencoded.  "
+                             "host (the default): the writer of save_video_tensor, unchanged.")
+    parser.add_argument("--jpeg_quality", type=int, default=None, metavar="Q",
+                        help="With --video_encoder gpu: IJG quality 1..100 (default 95, the host writer's).")
     args = parser.parse_args(argv)
+    args.jpeg = None
+    if args.video_encoder == "gpu":
+        from landiff_amd.encode import JpegConfig
+        try:
+            args.jpeg = JpegConfig(quality=95 if args.jpeg_quality is None else args.jpeg_quality)
+        except ValueError as e:
+            parser.error(f"--jpeg_quality: {e}")
+    elif args.jpeg_quality is not None:
+        parser.error("--jpeg_quality goes with --video_encoder gpu")
     args.retime = None
     if args.out_fps is None:
         if args.out_search is not None:
@@ -362,15 +378,38 @@ def _write_conform_json(args, last_conform):
         json.dump(last_conform, f, indent=1, allow_nan=False)
 
 
-def _save_retimed(video, path: str, fps: int, retime):
-    """--out_fps: the clip's frames at `fps` -> the retime stage on the current device -> save_video_tensor at the new rate, and
-    <name>_retime.json: the plan (source frame and phase of every frame written) and the motion profile of the model's frames."""
+def _save_encoded(frames, path: str, fps: int, jpeg):
+    """--video_encoder gpu: uint8 frames [F, H, W, 3] on the device -> <name>.avi (Motion-JPEG, the frames encoded where they are)
+    and <name>_encode.json (quality, subsampling, frame count, bytes per frame, total bytes, the table source)."""
+    import json
+    from landiff.utils import write_mjpeg_avi_encoded
+    from landiff_amd.encode import encode_jpeg, encode_report
+    jpegs = encode_jpeg(frames, jpeg)
+    stem = Path(path).with_suffix("")
+    stem.parent.mkdir(parents=True, exist_ok=True)
+    write_mjpeg_avi_encoded(jpegs, (int(frames.shape[2]), int(frames.shape[1])), f"{stem}.avi", fps=fps)
+    with open(f"{stem}_encode.json", "w") as f:
+        json.dump(encode_report(jpegs, jpeg), f, indent=1, allow_nan=False)
+    print(f"encoded {len(jpegs)} frames on the GPU: {stem}.avi, {stem}_encode.json")
+
+
+def _device_frames(video):
+    dev = torch.device(f"cuda:{torch.cuda.current_device()}")
+    return (video if video.dtype == torch.uint8 else torch.from_numpy(cthw_to_numpy_images(video))).to(dev).contiguous()
+
+
+def _save_retimed(video, path: str, fps: int, retime, jpeg=None):
+    """--out_fps: the clip's frames at `fps` -> the retime stage on the current device -> save_video_tensor at the new rate (with
+    --video_encoder gpu: _save_encoded, the retimed frames stay on the device), and <name>_retime.json: the plan (source frame and
+    phase of every frame written) and the motion profile of the model's frames."""
     import json
     from landiff_amd.retime import motion_profile, retime_clip, retime_plan
-    dev = torch.device(f"cuda:{torch.cuda.current_device()}")
-    frames = (video if video.dtype == torch.uint8 else torch.from_numpy(cthw_to_numpy_images(video))).to(dev).contiguous()
+    frames = _device_frames(video)
     plan = retime_plan(frames.shape[0], retime, src_fps=fps)
-    save_video_tensor(retime_clip(frames, plan), path, fps=int(plan.out_fps))
+    if jpeg is None:
+        save_video_tensor(retime_clip(frames, plan), path, fps=int(plan.out_fps))
+    else:
+        _save_encoded(retime_clip(frames, plan), path, int(plan.out_fps), jpeg)
     report = {"plan": plan.as_dict(),
               "motion": motion_profile(frames, retime.search, retime.penalty, retime.max_sad).as_dict() if frames.shape[0] > 1 else None}
     stem = Path(path).with_suffix("")
@@ -384,12 +423,15 @@ def _save_video(args, video, path: str, fps: int = 8):
     frames) and --compare_to (<name>_metrics.json: landiff_amd.metrics.compare_clips of the frames against the reference file's, and
     temporal_profile of both clips).  Without the two flags it is save_video_tensor alone.  --out_fps N: what is written is the
     clip retimed to N fps on the current device (landiff_amd.retime), with <name>_retime.json beside it; the two flags keep using the
-    model's own frames, and <name>.frames.npy is written after the video so that it holds them whatever the writer left there."""
-    retime = getattr(args, "retime", None)
-    if retime is None:
-        save_video_tensor(video, path, fps=fps)
+    model's own frames, and <name>.frames.npy is written after the video so that it holds them whatever the writer left there.
+    --video_encoder gpu: the video is <name>.avi, its JPEG frames encoded on the device (landiff_amd.encode), with <name>_encode.json."""
+    retime, jpeg = getattr(args, "retime", None), getattr(args, "jpeg", None)
+    if retime is not None:
+        _save_retimed(video, path, fps, retime, jpeg)
+    elif jpeg is not None:
+        _save_encoded(_device_frames(video), path, fps, jpeg)
     else:
-        _save_retimed(video, path, fps, retime)
+        save_video_tensor(video, path, fps=fps)
     ref_path = getattr(args, "compare_to", None)
     if not (getattr(args, "save_frames", False) or ref_path):
         return
@@ -440,15 +482,21 @@ def infer_diffusion(args, semantic_token):
 
 
 def load_clip(path: str) -> torch.Tensor:
-    """uint8 frames [F, H, W, 3] from a .npy (save_video_tensor's fallback format) or, through imageio, a video file."""
+    """uint8 frames [F, H, W, 3] from a .npy (save_video_tensor's fallback format) or, through imageio, a video file; without
+    imageio a Motion-JPEG .avi (what this project writes) is read with landiff.utils.read_mjpeg_avi."""
     if path.endswith(".npy"):
         arr = np.load(path)
     else:
         try:
             import imageio
         except ImportError as e:
-            raise ValueError(f"{path}: reading a video file needs imageio; give the uint8 frames as .npy instead") from e
-        arr = np.stack(list(imageio.get_reader(path)))
+            if not path.lower().endswith(".avi"):
+                raise ValueError(f"{path}: reading a video file needs imageio; give the uint8 frames as .npy or a Motion-JPEG "
+                                 ".avi instead") from e
+            from landiff.utils import read_mjpeg_avi
+            arr = read_mjpeg_avi(path)[0]
+        else:
+            arr = np.stack(list(imageio.get_reader(path)))
     if arr.dtype != np.uint8 or arr.ndim != 4 or arr.shape[-1] != 3:
         raise ValueError(f"{path}: expected uint8 frames [F, H, W, 3], got {arr.dtype} {arr.shape}")
     return torch.from_numpy(np.ascontiguousarray(arr))

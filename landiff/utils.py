@@ -129,19 +129,13 @@ def cthw_to_numpy_images(video: torch.Tensor) -> np.ndarray:
     return images.clip(0, 255).cpu().numpy().astype(np.uint8)
 
 
-def write_mjpeg_avi(images: np.ndarray, path, fps: int = 8, quality: int = 95):
-    """Motion-JPEG AVI (RIFF) writer with nothing but PIL for the JPEG frames: the playable fallback when imageio-ffmpeg (the
-    reference's H.264 mp4 writer, landiff/utils.py:334-342) is not installed.  images: uint8 [T, H, W, 3]."""
-    import io
+def write_mjpeg_avi_encoded(jpegs, size, path, fps: int = 8):
+    """Motion-JPEG AVI (RIFF) from already-encoded frames: jpegs a list of complete JPEG streams (bytes) of one size = (W, H) --
+    PIL's, or landiff_amd.encode.encode_jpeg's straight from device frames."""
     import struct
-    from PIL import Image
-    T, H, W, _ = images.shape
-    frames = []
-    for img in images:
-        buf = io.BytesIO()
-        Image.fromarray(np.ascontiguousarray(img), "RGB").save(buf, format="JPEG", quality=quality)
-        b = buf.getvalue()
-        frames.append(b + b"\0" * (len(b) & 1))                      # chunks are word aligned
+    W, H = size
+    T = len(jpegs)
+    frames = [b + b"\0" * (len(b) & 1) for b in jpegs]                # chunks are word aligned
     chunk = lambda tag, data: tag + struct.pack("<I", len(data)) + data + b"\0" * (len(data) & 1)
     lst = lambda tag, data: b"LIST" + struct.pack("<I", len(data) + 4) + tag + data
     maxb = max(len(f) for f in frames)
@@ -149,14 +143,66 @@ def write_mjpeg_avi(images: np.ndarray, path, fps: int = 8, quality: int = 95):
     strh = b"vids" + b"MJPG" + struct.pack("<IHHIIIIIIII4H", 0, 0, 0, 0, 1, fps, 0, T, maxb, 0xFFFFFFFF, 0, 0, 0, W, H)
     strf = struct.pack("<IiiHH4sIiiII", 40, W, H, 1, 24, b"MJPG", W * H * 3, 0, 0, 0, 0)
     hdrl = lst(b"hdrl", chunk(b"avih", avih) + lst(b"strl", chunk(b"strh", strh) + chunk(b"strf", strf)))
-    movi_body, idx, off = b"", b"", 4
+    movi, idx, off = [], [], 4
     for f in frames:
-        movi_body += b"00dc" + struct.pack("<I", len(f)) + f
-        idx += b"00dc" + struct.pack("<III", 0x10, off, len(f))   # AVIIF_KEYFRAME, offset from the 'movi' tag
+        movi.append(b"00dc" + struct.pack("<I", len(f)) + f)
+        idx.append(b"00dc" + struct.pack("<III", 0x10, off, len(f)))   # AVIIF_KEYFRAME, offset from the 'movi' tag
         off += 8 + len(f)
-    body = b"AVI " + hdrl + lst(b"movi", movi_body) + chunk(b"idx1", idx)
+    body = b"AVI " + hdrl + lst(b"movi", b"".join(movi)) + chunk(b"idx1", b"".join(idx))
     with open(path, "wb") as fh:
         fh.write(b"RIFF" + struct.pack("<I", len(body)) + body)
+
+
+def write_mjpeg_avi(images: np.ndarray, path, fps: int = 8, quality: int = 95):
+    """Motion-JPEG AVI (RIFF) writer with nothing but PIL for the JPEG frames: the playable fallback when imageio-ffmpeg (the
+    reference's H.264 mp4 writer, landiff/utils.py:334-342) is not installed.  images: uint8 [T, H, W, 3]."""
+    import io
+    from PIL import Image
+    T, H, W, _ = images.shape
+    jpegs = []
+    for img in images:
+        buf = io.BytesIO()
+        Image.fromarray(np.ascontiguousarray(img), "RGB").save(buf, format="JPEG", quality=quality)
+        jpegs.append(buf.getvalue())
+    write_mjpeg_avi_encoded(jpegs, (W, H), path, fps=fps)
+
+
+def read_mjpeg_avi(path):
+    """A Motion-JPEG AVI as write_mjpeg_avi_encoded lays it out -> (frames uint8 [T, H, W, 3], fps): the rate from the stream
+    header, the frames by walking idx1 (offsets from the 'movi' tag) and decoding each chunk with PIL."""
+    import io
+    import struct
+    from PIL import Image
+    raw = Path(path).read_bytes()
+    if raw[:4] != b"RIFF" or raw[8:12] != b"AVI ":
+        raise ValueError(f"{path}: not a RIFF AVI file")
+    pos, hdrl, movi, idx = 12, None, None, None                      # the top-level chunks: LIST hdrl, LIST movi, idx1
+    while pos + 8 <= len(raw):
+        tag, size = raw[pos:pos + 4], struct.unpack("<I", raw[pos + 4:pos + 8])[0]
+        if tag == b"LIST" and raw[pos + 8:pos + 12] == b"hdrl":
+            hdrl = raw[pos + 12:pos + 8 + size]
+        elif tag == b"LIST" and raw[pos + 8:pos + 12] == b"movi":
+            movi = pos + 8
+        elif tag == b"idx1":
+            idx = pos
+        pos += 8 + size + (size & 1)
+    at = -1 if hdrl is None else hdrl.find(b"strh")
+    if at < 0 or hdrl[at + 8:at + 16] != b"vidsMJPG":
+        raise ValueError(f"{path}: no Motion-JPEG video stream")
+    scale, rate = struct.unpack("<2I", hdrl[at + 28:at + 36])
+    if movi is None or idx is None or not scale:
+        raise ValueError(f"{path}: no movi list or no idx1 index")
+    n = struct.unpack("<I", raw[idx + 4:idx + 8])[0] // 16
+    frames = []
+    for k in range(n):
+        tag, _, off, size = struct.unpack("<4sIII", raw[idx + 8 + 16 * k:idx + 24 + 16 * k])
+        if tag != b"00dc":
+            continue
+        data = raw[movi + off + 8:movi + off + 8 + size]
+        frames.append(np.asarray(Image.open(io.BytesIO(data)).convert("RGB")))
+    if not frames:
+        raise ValueError(f"{path}: the index lists no video frame")
+    return np.stack(frames), (rate // scale if rate % scale == 0 else rate / scale)
 
 
 def save_video_tensor(video: torch.Tensor, video_path: str, fps: int = 8):

@@ -905,6 +905,92 @@ def retime_u8(frames, src_idx, phase_p, q, search, penalty, max_sad, want_motion
     return (out, mv, sad) if want_motion else out
 
 
+def _jpeg_sub(name, subsampling) -> int:
+    if subsampling not in ("420", "444"):
+        raise ValueError(f"{name}: subsampling must be '420' or '444', got {subsampling!r}")
+    return int(subsampling)
+
+
+def jpeg_size(what: int, F, H, W, subsampling: str, header_bytes: int = 0) -> int:
+    """ld_jpeg_size: 0 blocks per frame, 1 segments (MCU rows) per frame, 2 blocks per segment, 3 the most bytes of a segment, 4 the
+    most bytes of F streams with their headers (include/landiff_hip.h, LD_JPEG_SIZE_*).  Needs no GPU."""
+    n = _lib.load().ld_jpeg_size(int(what), int(F), int(H), int(W), _jpeg_sub("jpeg_size", subsampling), int(header_bytes))
+    if n < 0:
+        check(int(n), "ld_jpeg_size")
+    return int(n)
+
+
+def _jpeg_frames(name, frames, quality):
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
+        raise TypeError(f"{name}: the frames must be a uint8 tensor, got {getattr(frames, 'dtype', type(frames))}")
+    if frames.dim() != 4 or min(frames.shape) < 1 or frames.shape[3] != 3 or frames.stride(3) != 1 or frames.stride(2) != 3:
+        raise ValueError(f"{name}: the frames must be a non-empty [F, H, W, 3] with contiguous pixels (rows and frames may be strided), "
+                         f"got {tuple(frames.shape)} with strides {tuple(frames.stride()) if frames.dim() == 4 else None}")
+    if isinstance(quality, bool) or int(quality) != quality or not 1 <= quality <= 100:
+        raise ValueError(f"{name}: quality must be an integer in 1..100, got {quality!r}")
+    return tuple(int(v) for v in frames.shape[:3])
+
+
+def jpeg_coefs_u8(frames, quality: int, subsampling: str = "420"):
+    """uint8 RGB frames [F, H, W, 3] -> the quantised DCT coefficients int16 [F, blocks, 64] of their baseline JPEG, blocks in scan
+    order, coefficients in zigzag order.  One launch on the current stream; does not synchronise."""
+    from .encode import device_tables
+    F, H, W = _jpeg_frames("jpeg_coefs_u8", frames, quality)
+    sub = _jpeg_sub("jpeg_coefs_u8", subsampling)
+    coefs = torch.empty(F, jpeg_size(0, F, H, W, subsampling), 64, dtype=torch.int16, device=frames.device)
+    check(_lib.load().ld_jpeg_coefs_u8(_ptr(frames), frames.stride(0), frames.stride(1), _ptr(device_tables(frames.device)), _ptr(coefs),
+                                       F, H, W, sub, int(quality), _stream()), "ld_jpeg_coefs_u8")
+    return coefs
+
+
+def jpeg_entropy_i16(coefs, mcus_per_row: int, subsampling: str = "420"):
+    """coefficients int16 [n_seg, mcus_per_row * (6 | 3), 64] (every row of dim 0 one segment: an MCU row) -> (segs uint8
+    [n_seg, capacity], seg_len int64 [n_seg]): the entropy-coded, stuffed bytes of every segment, without markers.  Two launches."""
+    from .encode import device_tables
+    sub = _jpeg_sub("jpeg_entropy_i16", subsampling)
+    bpm = 6 if sub == 420 else 3
+    if not isinstance(coefs, torch.Tensor) or coefs.dtype != torch.int16:
+        raise TypeError(f"jpeg_entropy_i16: the coefficients must be an int16 tensor, got {getattr(coefs, 'dtype', type(coefs))}")
+    if coefs.dim() != 3 or not coefs.is_contiguous() or coefs.shape[0] < 1 or coefs.shape[1] != mcus_per_row * bpm or coefs.shape[2] != 64:
+        raise ValueError(f"jpeg_entropy_i16: the coefficients must be a contiguous [n_seg, {mcus_per_row} * {bpm}, 64], got {tuple(coefs.shape)}")
+    n_seg = int(coefs.shape[0])
+    cap = jpeg_size(3, 1, 8, int(mcus_per_row) * (16 if sub == 420 else 8), subsampling)
+    segs = torch.empty(n_seg, cap, dtype=torch.uint8, device=coefs.device)
+    seg_len = torch.empty(n_seg, dtype=torch.int64, device=coefs.device)
+    check(_lib.load().ld_jpeg_entropy_i16(_ptr(coefs), _ptr(device_tables(coefs.device)), _ptr(segs), cap, _ptr(seg_len), n_seg,
+                                          int(mcus_per_row), sub, _stream()), "ld_jpeg_entropy_i16")
+    return segs, seg_len
+
+
+_JPEG_HEADERS: dict = {}
+
+
+def jpeg_encode_u8(frames, quality: int, subsampling: str = "420"):
+    """uint8 RGB frames [F, H, W, 3] -> (stream buffer uint8 [capacity], offsets int64 [F], lengths int64 [F]), all on the device:
+    frame f's complete baseline JPEG is buffer[offsets[f] : offsets[f] + lengths[f]], the frames back to back.  The buffer is sized
+    by ld_jpeg_size's bound (nothing is ever cut to fit); only the streams' bytes of it are touched.  Four launches on the current
+    stream; does not synchronise."""
+    from .encode import device_tables, jpeg_header
+    F, H, W = _jpeg_frames("jpeg_encode_u8", frames, quality)
+    sub = _jpeg_sub("jpeg_encode_u8", subsampling)
+    dev = frames.device
+    key = (str(dev), H, W, int(quality), subsampling)
+    if key not in _JPEG_HEADERS:
+        if len(_JPEG_HEADERS) > 64:
+            _JPEG_HEADERS.clear()
+        _JPEG_HEADERS[key] = torch.frombuffer(bytearray(jpeg_header(H, W, int(quality), subsampling)), dtype=torch.uint8).to(dev)
+    header = _JPEG_HEADERS[key]
+    cap = jpeg_size(4, F, H, W, subsampling, header.numel())
+    coefs = torch.empty(F, jpeg_size(0, F, H, W, subsampling), 64, dtype=torch.int16, device=dev)
+    seg_ws = torch.empty(2, F * jpeg_size(1, F, H, W, subsampling), dtype=torch.int64, device=dev)
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    table = torch.empty(2, F, dtype=torch.int64, device=dev)
+    check(_lib.load().ld_jpeg_encode_u8(_ptr(frames), frames.stride(0), frames.stride(1), _ptr(device_tables(dev)), _ptr(header),
+                                        header.numel(), _ptr(coefs), _ptr(seg_ws), _ptr(out), cap, _ptr(table[0]), _ptr(table[1]),
+                                        F, H, W, sub, int(quality), _stream()), "ld_jpeg_encode_u8")
+    return out, table[0], table[1]
+
+
 SSIM_TAPS, SSIM_SIGMA = 11, 1.5                      # LD_SSIM_TAPS of include/landiff_hip.h
 SSIM_TILE_H, SSIM_TILE_ELEMS = 32, 48               # LD_SSIM_TILE_H / LD_SSIM_TILE_ELEMS: they size the workspace, which the library checks
 

@@ -99,6 +99,7 @@ class LanDiffPipeline:
         self.last_conform_frames = None   # ... and that clip at the model's frame, uint8 on the device (None: nothing was conformed)
         self.last_metrics = None          # compare: the ClipMetrics of the last comparison
         self.last_retime = None           # retime: RetimePlan.as_dict() of the last retimed clip
+        self.last_encode = None           # encode: encode.encode_report() of the last encoded clip
 
     def _conform(self, frames, conform, keep_mask=None):
         """The conform stage of extend_video / edit_video: `frames` of any size / frame rate -> the 4T-3 frames of
@@ -147,6 +148,23 @@ class LanDiffPipeline:
         self.last_retime = plan.as_dict()
         self._t("retime", t0)
         return out
+
+    def encode(self, frames, cfg=None):
+        """uint8 frames [F, H, W, 3] -> list of F `bytes`, each a complete baseline JPEG, encoded on the pipeline's device (cfg: an
+        encode.JpegConfig, default quality 95 at 4:2:0; landiff_amd.encode.encode_jpeg): the frames of a Motion-JPEG
+        AVI (landiff.utils.write_mjpeg_avi_encoded) or stills.  A function of the frames alone: it takes what __call__,
+        generate_stream, extend_video, edit_video or retime returned.  Timed as "encode"; the figures are self.last_encode."""
+        from .encode import JpegConfig, encode_jpeg, encode_report
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.dtype != torch.uint8 or frames.shape[-1] != 3:
+            raise ValueError(f"encode: frames must be uint8 [F, H, W, 3], got {getattr(frames, 'dtype', type(frames))} "
+                             f"{tuple(getattr(frames, 'shape', ()))}")
+        cfg = JpegConfig() if cfg is None else cfg
+        t0 = time.perf_counter()
+        with torch.cuda.device(self.dev):
+            jpegs = encode_jpeg(frames.to(self.dev), cfg)
+        self.last_encode = encode_report(jpegs, cfg)
+        self._t("encode", t0)
+        return jpegs
 
     def _t(self, name, t0):
         torch.cuda.current_stream(self.dev).synchronize()      # (the stage's own stream: an overlapped AR decode keeps running)
