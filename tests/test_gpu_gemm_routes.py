@@ -170,8 +170,9 @@ EXACT_CASES = [
 ]
 
 
-def _epilogue(form, M, N, g, dev, exact, out=None):
-    """The epilogue operands of a case form (the DiT's gate layout: ada [B, 12 N], image / text offsets as in dit.py)."""
+def _epilogue(form, M, N, g, dev, exact, out=None, batches=None):
+    """The epilogue operands of a case form (the DiT's gate layout: ada [B, 12 N], image / text offsets as in dit.py).
+    batches: (B, rows per batch, text rows) of a gate form, for callers with their own shapes (tests/test_gpu_fp8_routes.py)."""
     bias = _small((N,), g, dev, -4, 4, exact, 0.5)
     if form == "bias":
         return dict(bias=bias)
@@ -182,7 +183,7 @@ def _epilogue(form, M, N, g, dev, exact, out=None):
         return dict(bias=bias, resid=r, out_f32=True)
     if form == "resid_bf16":
         return dict(bias=bias, resid=_small((M, N), g, dev, -8, 8, exact))
-    B, rows, text = (5, 4130, TEXT) if form.endswith("_5b") else (2, ROWS, TEXT)
+    B, rows, text = batches or ((5, 4130, TEXT) if form.endswith("_5b") else (2, ROWS, TEXT))
     assert M == B * rows
     ada = _gate_values((B, 12 * N), g, dev, exact)
     e = dict(bias=bias, gate=ada, gate_bstride=12 * N, rows_per_batch=rows, text_len=text)
