@@ -35,7 +35,8 @@ extern "C" {
  * ld_residual_sub, ld_residual_add, ld_attn_fwd_bf16_window, ld_attn_window_plan, ld_unpatchify_cfg_keep, ld_unpatchify_cond, ld_latent_pin and ld_mask_to_latent (additions do not change
  * the number: no existing signature moved).  16: ld_attn_route was added; ld_resize_u8 and ld_resize_mask_u8 joined later
  * (additions again).  17: ld_clip_diff_u8 and ld_clip_ssim_u8 were added; ld_retime_u8 joined later (an addition), and so did
- * ld_jpeg_size, ld_jpeg_coefs_u8, ld_jpeg_entropy_i16 and ld_jpeg_encode_u8 (additions again). */
+ * ld_jpeg_size, ld_jpeg_coefs_u8, ld_jpeg_entropy_i16 and ld_jpeg_encode_u8 (additions again), then ld_jpeg_dec_size,
+ * ld_jpeg_find_segments, ld_jpeg_decode_entropy and ld_jpeg_decode_rgb (additions). */
 #define LD_ABI_VERSION 17
 
 int ld_version(void);
@@ -736,6 +737,68 @@ int ld_jpeg_encode_u8(const uint8_t* frames, int64_t frame_stride, int64_t row_s
                       const uint8_t* header, int64_t header_bytes, int16_t* coefs_ws, int64_t* seg_ws, uint8_t* out,
                       int64_t out_capacity, int64_t* offsets, int64_t* lengths, int64_t F, int64_t H, int64_t W,
                       int32_t subsampling, int32_t quality, void* stream);
+
+/* ---- the decode stage (ld_jpeg_dec.hip; landiff_amd/decode.py) ----
+ * Baseline JPEG streams on the device -> uint8 RGB frames, integer arithmetic only, equal to libjpeg's (PIL's) decode byte for
+ * byte: c = coefficient x quantiser; jidctint's "islow" inverse DCT with 13-bit constants, columns then rows, (x + (1 << (s - 1)))
+ * >> s with s = 11 and 18, in 64-bit (any int16 coefficient times any quantiser fits: there is no range refusal); the sample
+ * is v + 128 saturated to 0..255; at 4:2:0 the triangle chroma filter (3/4, 1/4 in both axes, roundings 8 and 7, clamped to the real chroma size
+ * ceil(H / 2) x ceil(W / 2); plain replication when that is 2 samples wide or fewer); Y, Cb, Cr -> R, G, B with 16-bit constants.
+ * DESIGN 8.13 states every formula; tests/jpeg_dec_ref.py restates it.  The host parses the headers (landiff_amd/decode.py
+ * parse_jpeg) and refuses what is not SOF0 / 8 bit / three components 4:2:0 or 4:4:4 / one interleaved scan before any launch.
+ * All frames of a call have one size and subsampling; W <= 8192, H <= 65535, F <= 65535.
+ *
+ * `tables`: n_sets table sets of LD_JPEG_DEC_TABLE_WORDS int32 each (decode.decode_tables); frame f uses set tset[f] (clamped to
+ * the sets there are).  A set: [0, 192) the quantisers of components 0, 1, 2 in zigzag order; then six Huffman tables of 544 words,
+ * DC and AC of component 0, 1, 2: [0, 16) limit[l - 1] = (the last code of length l + 1) << (16 - l), the running value where a
+ * length has no code; [16, 32) offset[l - 1] = the index of the first value of length l minus its first code; [32, 288) HUFFVAL;
+ * [288, 544) for every 8-bit prefix length << 8 | value of the code it starts with, 0 where that code is longer than 8 bits.
+ * `scan` int64 [F][2]: where frame f's entropy-coded data starts in `data` and how many bytes may be searched (to the stream's end);
+ * `ri` int32 [F]: its restart interval in MCUs, 0 = none.  Both are clamped into the buffer by the kernels.
+ *
+ * Segment table int64 [F][S][5] = (frame, start in `data`, length, first MCU, MCU count): row s < ceil(MCUs / ri) (1 without
+ * restarts) is the data between restart markers s - 1 and s; rows from that count on are (frame, 0, 0, 0, 0); rows whose marker
+ * was not found have start = length = 0.  frame_info int64 [F][3] = (restart markers found, 1 if they are numbered 0..7 in order,
+ * the length of the entropy-coded data: up to the first 0xFF that is followed by neither 0x00 nor 0xD0..0xD7).
+ * Coefficients int16 [F][FRAME_BLOCKS][64], zigzag order, blocks in scan order: ld_jpeg_coefs_u8's layout.
+ * status int32 [F][S], one word per segment (0 for rows past the frame's count): LD_JPEG_DEC_*.  BAD_CODE: no code of <= 16 bits
+ * matches, a DC size above 11 or an AC size above 10.  OVERFLOW: a run steps past coefficient 63.  OVERRUN: bits wanted past the
+ * segment's end.  MARKERS: the frame's restart markers are not exactly its segment count - 1, numbered in order (every segment of
+ * the frame reports it, nothing of the frame is decoded).  RANGE is never reported (the 64-bit passes).  A segment's blocks are
+ * all written whatever its status (zeros after the error).
+ * Every read of `data` is bounded by the segment's clamped end and every coefficient store by its block, whatever the tables and
+ * the stream hold.  LD_ERR_INVALID: a null or misaligned pointer (coefficients 16, int64 arrays and planes 8, int32 arrays 4
+ * bytes), an empty shape, strides that do not hold a frame.  LD_ERR_UNSUPPORTED: another subsampling, W > 8192 or H > 65535. */
+#define LD_JPEG_DEC_TABLE_WORDS 3456
+#define LD_JPEG_DEC_SIZE_FRAME_BLOCKS 0
+#define LD_JPEG_DEC_SIZE_MCUS 1
+#define LD_JPEG_DEC_SIZE_PLANE_BYTES 2
+#define LD_JPEG_DEC_SIZE_TABLE_WORDS 3
+#define LD_JPEG_DEC_OK 0
+#define LD_JPEG_DEC_BAD_CODE 1
+#define LD_JPEG_DEC_OVERFLOW 2
+#define LD_JPEG_DEC_OVERRUN 3
+#define LD_JPEG_DEC_RANGE 4
+#define LD_JPEG_DEC_MARKERS 5
+/* the sizes a caller allocates by (negative: the refusal's code): blocks per frame, MCUs per frame (the most segments a frame can
+ * have), the bytes of ld_jpeg_decode_rgb's plane workspace per frame, the words of a table set */
+int64_t ld_jpeg_dec_size(int32_t what, int64_t H, int64_t W, int32_t subsampling);
+
+/* One workgroup per frame finds every RSTn and the end of the entropy-coded data: seg_table and frame_info as above.  No atomics on
+ * global memory; the order is deterministic. */
+int ld_jpeg_find_segments(const uint8_t* data, int64_t data_bytes, const int64_t* scan, const int32_t* ri, int64_t* seg_table,
+                          int64_t* frame_info, int64_t F, int64_t S, int64_t H, int64_t W, int32_t subsampling, void* stream);
+
+/* Annex F.2.2, one lane per segment: seg_table -> coefs and status.  A stream without restart markers is one lane per frame. */
+int ld_jpeg_decode_entropy(const uint8_t* data, int64_t data_bytes, const int64_t* seg_table, const int64_t* frame_info,
+                           const int32_t* ri, const int32_t* tables, const int32_t* tset, int64_t n_sets, int16_t* coefs,
+                           int32_t* status, int64_t F, int64_t S, int64_t H, int64_t W, int32_t subsampling, void* stream);
+
+/* coefs -> out uint8 [F][H][W][3] with byte strides (row_stride >= 3 W).  Two launches: dequantise + inverse DCT + range limit into
+ * planes_ws (F x PLANE_BYTES, 8-byte aligned), then chroma upsampling + colour conversion, stored as whole rows. */
+int ld_jpeg_decode_rgb(const int16_t* coefs, const int32_t* tables, const int32_t* tset, int64_t n_sets, uint8_t* planes_ws,
+                       uint8_t* out, int64_t frame_stride, int64_t row_stride, int64_t F, int64_t H, int64_t W,
+                       int32_t subsampling, void* stream);
 
 /* ---- clip comparison (ld_metrics.hip; landiff_amd/metrics.py) ----
  * Two uint8 channels-last clips a, b [F][H][W][C], C 1 or 3 (the pipeline's output layout), and an optional keep-mask [F][H][W] u8

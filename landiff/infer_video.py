@@ -126,6 +126,14 @@ def parse_args(argv=None):
                              "host (the default): the writer of save_video_tensor, unchanged.")
     parser.add_argument("--jpeg_quality", type=int, default=None, metavar="Q",
                         help="With --video_encoder gpu: IJG quality 1..100 (default 95, the host writer's).")
+    parser.add_argument("--encode_verify", action="store_true",
+                        help="With --video_encoder gpu: decode the written streams again on the GPU and add what the file loses "
+                             "against the frames it was made from (PSNR, SSIM, the largest difference) to <name>_encode.json.")
+    parser.add_argument("--video_decoder", choices=("host", "gpu"), default="host",
+                        help="gpu: a Motion-JPEG .avi given to --extend_video, --edit_video or --compare_to is decoded on the GPU "
+                             "(baseline JPEG, equal to PIL's decode byte for byte; landiff_amd/decode.py): only the compressed bytes "
+                             "are uploaded, with --clip_fit only the frames the conform stage reads are decoded, and "
+                             "<name>_decode.json is written.  host (the default): PIL, frame by frame, unchanged.")
     args = parser.parse_args(argv)
     args.jpeg = None
     if args.video_encoder == "gpu":
@@ -136,6 +144,8 @@ def parse_args(argv=None):
             parser.error(f"--jpeg_quality: {e}")
     elif args.jpeg_quality is not None:
         parser.error("--jpeg_quality goes with --video_encoder gpu")
+    elif args.encode_verify:
+        parser.error("--encode_verify goes with --video_encoder gpu")
     args.retime = None
     if args.out_fps is None:
         if args.out_search is not None:
@@ -378,9 +388,10 @@ def _write_conform_json(args, last_conform):
         json.dump(last_conform, f, indent=1, allow_nan=False)
 
 
-def _save_encoded(frames, path: str, fps: int, jpeg):
+def _save_encoded(frames, path: str, fps: int, jpeg, verify: bool = False):
     """--video_encoder gpu: uint8 frames [F, H, W, 3] on the device -> <name>.avi (Motion-JPEG, the frames encoded where they are)
-    and <name>_encode.json (quality, subsampling, frame count, bytes per frame, total bytes, the table source)."""
+    and <name>_encode.json (quality, subsampling, frame count, bytes per frame, total bytes, the table source).  --encode_verify:
+    the streams decoded again on the device (landiff_amd.decode) and compared with the frames: "verify" in the same file."""
     import json
     from landiff.utils import write_mjpeg_avi_encoded
     from landiff_amd.encode import encode_jpeg, encode_report
@@ -388,8 +399,14 @@ def _save_encoded(frames, path: str, fps: int, jpeg):
     stem = Path(path).with_suffix("")
     stem.parent.mkdir(parents=True, exist_ok=True)
     write_mjpeg_avi_encoded(jpegs, (int(frames.shape[2]), int(frames.shape[1])), f"{stem}.avi", fps=fps)
+    report = encode_report(jpegs, jpeg)
+    if verify:
+        from landiff_amd.decode import decode_jpeg
+        from landiff_amd.metrics import _jsonable, compare_clips
+        m = compare_clips(frames, decode_jpeg(jpegs, frames.device)).as_dict()
+        report["verify"] = _jsonable({"clip": m["clip"], "frames": {k: m["frames"][k] for k in ("psnr", "ssim", "max_abs")}})
     with open(f"{stem}_encode.json", "w") as f:
-        json.dump(encode_report(jpegs, jpeg), f, indent=1, allow_nan=False)
+        json.dump(report, f, indent=1, allow_nan=False)
     print(f"encoded {len(jpegs)} frames on the GPU: {stem}.avi, {stem}_encode.json")
 
 
@@ -398,7 +415,7 @@ def _device_frames(video):
     return (video if video.dtype == torch.uint8 else torch.from_numpy(cthw_to_numpy_images(video))).to(dev).contiguous()
 
 
-def _save_retimed(video, path: str, fps: int, retime, jpeg=None):
+def _save_retimed(video, path: str, fps: int, retime, jpeg=None, verify: bool = False):
     """--out_fps: the clip's frames at `fps` -> the retime stage on the current device -> save_video_tensor at the new rate (with
     --video_encoder gpu: _save_encoded, the retimed frames stay on the device), and <name>_retime.json: the plan (source frame and
     phase of every frame written) and the motion profile of the model's frames."""
@@ -409,7 +426,7 @@ def _save_retimed(video, path: str, fps: int, retime, jpeg=None):
     if jpeg is None:
         save_video_tensor(retime_clip(frames, plan), path, fps=int(plan.out_fps))
     else:
-        _save_encoded(retime_clip(frames, plan), path, int(plan.out_fps), jpeg)
+        _save_encoded(retime_clip(frames, plan), path, int(plan.out_fps), jpeg, verify)
     report = {"plan": plan.as_dict(),
               "motion": motion_profile(frames, retime.search, retime.penalty, retime.max_sad).as_dict() if frames.shape[0] > 1 else None}
     stem = Path(path).with_suffix("")
@@ -426,10 +443,11 @@ def _save_video(args, video, path: str, fps: int = 8):
     model's own frames, and <name>.frames.npy is written after the video so that it holds them whatever the writer left there.
     --video_encoder gpu: the video is <name>.avi, its JPEG frames encoded on the device (landiff_amd.encode), with <name>_encode.json."""
     retime, jpeg = getattr(args, "retime", None), getattr(args, "jpeg", None)
+    verify = getattr(args, "encode_verify", False)
     if retime is not None:
-        _save_retimed(video, path, fps, retime, jpeg)
+        _save_retimed(video, path, fps, retime, jpeg, verify)
     elif jpeg is not None:
-        _save_encoded(_device_frames(video), path, fps, jpeg)
+        _save_encoded(_device_frames(video), path, fps, jpeg, verify)
     else:
         save_video_tensor(video, path, fps=fps)
     ref_path = getattr(args, "compare_to", None)
@@ -442,7 +460,7 @@ def _save_video(args, video, path: str, fps: int = 8):
         np.save(f"{stem}.frames.npy", frames.numpy())
     if ref_path:
         from landiff_amd.metrics import compare_clips, temporal_profile, write_metrics_json
-        ref = load_clip(ref_path)
+        ref = load_clip(ref_path, getattr(args, "video_decoder", "host"), report=f"{stem}_decode.json")
         if tuple(ref.shape) != tuple(frames.shape):
             raise ValueError(f"--compare_to {ref_path}: the reference is {tuple(ref.shape)}, the video written to {path} is "
                              f"{tuple(frames.shape)}; the shapes must be equal (nothing is resized)")
@@ -481,9 +499,33 @@ def infer_diffusion(args, semantic_token):
     print(f"save video to {task.save_file_name}")
 
 
-def load_clip(path: str) -> torch.Tensor:
+def load_clip(path: str, decoder: str = "host", needed=None, report: str | None = None) -> torch.Tensor:
     """uint8 frames [F, H, W, 3] from a .npy (save_video_tensor's fallback format) or, through imageio, a video file; without
-    imageio a Motion-JPEG .avi (what this project writes) is read with landiff.utils.read_mjpeg_avi."""
+    imageio a Motion-JPEG .avi (what this project writes) is read with landiff.utils.read_mjpeg_avi.
+    decoder="gpu" (--video_decoder gpu): a Motion-JPEG .avi is decoded on the current device (landiff_amd.decode: equal to PIL's
+    decode) and the frames returned are a device tensor; anything else is read as with "host".  needed: a function (F, H, W) ->
+    the frame indices that will be read (--clip_fit: conform_plan's); only those are decoded, the others are zero.  report: where
+    decode_report's figures are written (<name>_decode.json)."""
+    if decoder == "gpu" and path.lower().endswith(".avi"):
+        import json
+        from landiff.utils import read_mjpeg_avi_chunks
+        from landiff_amd.decode import decode_jpeg
+        chunks, (W, H), _ = read_mjpeg_avi_chunks(path)
+        dev = torch.device(f"cuda:{torch.cuda.current_device()}")
+        figures = {}
+        if needed is None:
+            clip = decode_jpeg(chunks, dev, report=figures)
+        else:
+            idx = sorted({int(k) for k in needed(len(chunks), H, W)})
+            clip = torch.zeros(len(chunks), H, W, 3, dtype=torch.uint8, device=dev)
+            clip[torch.tensor(idx, device=dev)] = decode_jpeg(chunks, dev, frames=idx, report=figures)
+            figures["decoded_frames"] = idx
+        if report:
+            figures["source"], figures["clip_frames"] = path, len(chunks)
+            Path(report).parent.mkdir(parents=True, exist_ok=True)
+            with open(report, "w") as f:
+                json.dump(figures, f, indent=1, allow_nan=False)
+        return clip
     if path.endswith(".npy"):
         arr = np.load(path)
     else:
@@ -500,6 +542,21 @@ def load_clip(path: str) -> torch.Tensor:
     if arr.dtype != np.uint8 or arr.ndim != 4 or arr.shape[-1] != 3:
         raise ValueError(f"{path}: expected uint8 frames [F, H, W, 3], got {arr.dtype} {arr.shape}")
     return torch.from_numpy(np.ascontiguousarray(arr))
+
+
+def _gpu_decoder(args) -> bool:
+    return getattr(args, "video_decoder", "host") == "gpu"
+
+
+def _load_clip_on_gpu(args, path: str, pipe) -> torch.Tensor:
+    """--video_decoder gpu: the clip of --extend_video / --edit_video through load_clip's device path, once the pipeline exists: with
+    --clip_fit only the frames the conform stage will read are decoded (its plan needs the header's size and the chunk count alone)."""
+    needed = None
+    if getattr(args, "conform", None) is not None:
+        from landiff_amd.conform import conform_plan
+        d = pipe.cfg.dit
+        needed = lambda F, H, W: conform_plan((F, H, W), 4 * d.latent_frames - 3, 8 * d.latent_h, 8 * d.latent_w, args.conform).frame_idx
+    return load_clip(path, "gpu", needed=needed, report=f"{args.save_file_name}_decode.json")
 
 
 def build_continuation(args, n_seg=None, theia=None):
@@ -539,8 +596,10 @@ def extend_diffusion(args):
     the decode continued against the VAE caches); --extend_tokens forces the decode's first segment to the clip's own tokens, and
     so does --theia_ckpt without --extend_tokens, with the tokens computed from the clip's frames.
     Writes the clip followed by the new frames; with --clip_fit cover / stretch the conformed window followed by the new frames."""
-    clip = load_clip(args.extend_video)
+    clip = None if _gpu_decoder(args) else load_clip(args.extend_video)
     pipe, inp = build_continuation(args)
+    if clip is None:
+        clip = _load_clip_on_gpu(args, args.extend_video, pipe)
     if args.extend_tokens:
         clip_tokens = torch.from_numpy(np.load(args.extend_tokens)).reshape(-1)
     else:
@@ -552,7 +611,7 @@ def extend_diffusion(args):
         _write_conform_json(args, pipe.last_conform)
     _write_dit_cache_report(args, args.save_file_name, pipe.dit_cache_reports)        # one list per appended chunk
     _write_dit_guidance_report(args, args.save_file_name, pipe.dit_guidance_reports)
-    frames = torch.cat([clip, new.cpu()], dim=0)
+    frames = torch.cat([clip.cpu(), new.cpu()], dim=0)        # (--video_decoder gpu left the clip on the device)
     path = f"{args.save_file_name}.mp4"
     _save_video(args, frames, path, fps=8)
     print(f"save video to {path} ({frames.shape[0]} frames, {new.shape[0]} new)")
@@ -572,9 +631,11 @@ def edit_diffusion(args):
     re-noised clip latent, the cells --edit_mask keeps held on the clip, the semantic tokens from the clip's frames (--edit_tokens
     from_frames: the default with --theia_ckpt), from the prompt or from a file.  Writes the edited clip and <name>_edit.json."""
     from landiff_amd.pipeline import write_edit_json
-    clip = load_clip(args.edit_video)
+    clip = None if _gpu_decoder(args) else load_clip(args.edit_video)
     mask = load_mask(args.edit_mask) if args.edit_mask else None
     pipe, inp = build_continuation(args, n_seg=1, theia=args.edit_tokens == "from_frames")
+    if clip is None:
+        clip = _load_clip_on_gpu(args, args.edit_video, pipe)
     kw = {}
     if args.edit_tokens == "from_frames":
         kw["clip_tokens"] = "from_frames"

@@ -167,12 +167,11 @@ def write_mjpeg_avi(images: np.ndarray, path, fps: int = 8, quality: int = 95):
     write_mjpeg_avi_encoded(jpegs, (W, H), path, fps=fps)
 
 
-def read_mjpeg_avi(path):
-    """A Motion-JPEG AVI as write_mjpeg_avi_encoded lays it out -> (frames uint8 [T, H, W, 3], fps): the rate from the stream
-    header, the frames by walking idx1 (offsets from the 'movi' tag) and decoding each chunk with PIL."""
-    import io
+def read_mjpeg_avi_chunks(path):
+    """A Motion-JPEG AVI as write_mjpeg_avi_encoded lays it out -> (chunks: the JPEG stream of every video frame as `bytes`,
+    (W, H) from the main header, fps from the stream header): the container walk alone (idx1, offsets from the 'movi' tag), nothing
+    is decoded."""
     import struct
-    from PIL import Image
     raw = Path(path).read_bytes()
     if raw[:4] != b"RIFF" or raw[8:12] != b"AVI ":
         raise ValueError(f"{path}: not a RIFF AVI file")
@@ -192,17 +191,27 @@ def read_mjpeg_avi(path):
     scale, rate = struct.unpack("<2I", hdrl[at + 28:at + 36])
     if movi is None or idx is None or not scale:
         raise ValueError(f"{path}: no movi list or no idx1 index")
+    ah = hdrl.find(b"avih")
+    W, H = struct.unpack("<2I", hdrl[ah + 40:ah + 48]) if ah >= 0 else (0, 0)
     n = struct.unpack("<I", raw[idx + 4:idx + 8])[0] // 16
-    frames = []
+    chunks = []
     for k in range(n):
         tag, _, off, size = struct.unpack("<4sIII", raw[idx + 8 + 16 * k:idx + 24 + 16 * k])
         if tag != b"00dc":
             continue
-        data = raw[movi + off + 8:movi + off + 8 + size]
-        frames.append(np.asarray(Image.open(io.BytesIO(data)).convert("RGB")))
-    if not frames:
+        chunks.append(raw[movi + off + 8:movi + off + 8 + size])
+    if not chunks:
         raise ValueError(f"{path}: the index lists no video frame")
-    return np.stack(frames), (rate // scale if rate % scale == 0 else rate / scale)
+    return chunks, (W, H), (rate // scale if rate % scale == 0 else rate / scale)
+
+
+def read_mjpeg_avi(path):
+    """A Motion-JPEG AVI as write_mjpeg_avi_encoded lays it out -> (frames uint8 [T, H, W, 3], fps): the rate from the stream
+    header, the frames by walking idx1 (read_mjpeg_avi_chunks) and decoding each chunk with PIL."""
+    import io
+    from PIL import Image
+    chunks, _, fps = read_mjpeg_avi_chunks(path)
+    return np.stack([np.asarray(Image.open(io.BytesIO(data)).convert("RGB")) for data in chunks]), fps
 
 
 def save_video_tensor(video: torch.Tensor, video_path: str, fps: int = 8):

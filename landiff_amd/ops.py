@@ -991,6 +991,90 @@ def jpeg_encode_u8(frames, quality: int, subsampling: str = "420"):
     return out, table[0], table[1]
 
 
+def jpeg_dec_size(what: int, H, W, subsampling: str) -> int:
+    """ld_jpeg_dec_size: 0 blocks per frame, 1 MCUs per frame, 2 bytes of the plane workspace per frame, 3 words of a table set
+    (include/landiff_hip.h, LD_JPEG_DEC_SIZE_*).  Needs no GPU."""
+    n = _lib.load().ld_jpeg_dec_size(int(what), int(H), int(W), _jpeg_sub("jpeg_dec_size", subsampling))
+    if n < 0:
+        check(int(n), "ld_jpeg_dec_size")
+    return int(n)
+
+
+def _jpeg_dec_arg(name, what, t, dtype, shape=None):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or not t.is_contiguous():
+        raise TypeError(f"{name}: {what} must be a contiguous {dtype} tensor, got {getattr(t, 'dtype', type(t))}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: {what} must be {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def jpeg_find_segments(data, scan, ri, n_rows: int, H: int, W: int, subsampling: str = "420"):
+    """data uint8 [n] (the frames' streams), scan int64 [F, 2] (where each frame's entropy-coded data starts, the bytes to search),
+    ri int32 [F] (restart intervals in MCUs, 0 = none) -> (segment table int64 [F, n_rows, 5], frame info int64 [F, 3]) as
+    include/landiff_hip.h states them.  n_rows >= the most segments a frame has.  One launch; does not synchronise."""
+    name = "jpeg_find_segments"
+    sub = _jpeg_sub(name, subsampling)
+    _jpeg_dec_arg(name, "data", data, torch.uint8)
+    F = int(_jpeg_dec_arg(name, "ri", ri, torch.int32).numel())
+    _jpeg_dec_arg(name, "scan", scan, torch.int64, (F, 2))
+    if data.dim() != 1 or ri.dim() != 1 or F < 1 or int(n_rows) < 1:
+        raise ValueError(f"{name}: data [n], ri [F] with F >= 1 and n_rows >= 1 are expected, got {tuple(data.shape)}, {tuple(ri.shape)}, {n_rows}")
+    seg = torch.empty(F, int(n_rows), 5, dtype=torch.int64, device=data.device)
+    info = torch.empty(F, 3, dtype=torch.int64, device=data.device)
+    check(_lib.load().ld_jpeg_find_segments(_ptr(data), data.numel(), _ptr(scan), _ptr(ri), _ptr(seg), _ptr(info), F, int(n_rows),
+                                            int(H), int(W), sub, _stream()), "ld_jpeg_find_segments")
+    return seg, info
+
+
+def jpeg_decode_entropy(data, seg_table, frame_info, ri, tables, tset, H: int, W: int, subsampling: str = "420"):
+    """The segments of jpeg_find_segments -> (coefficients int16 [F, blocks, 64] in ld_jpeg_coefs_u8's layout, status int32 [F, rows],
+    decode.STATUS per segment).  tables int32 [n_sets, words] (decode.decode_tables), tset int32 [F] the set of every frame.  One
+    launch, one lane per segment; does not synchronise."""
+    name = "jpeg_decode_entropy"
+    sub = _jpeg_sub(name, subsampling)
+    _jpeg_dec_arg(name, "data", data, torch.uint8)
+    F = int(_jpeg_dec_arg(name, "ri", ri, torch.int32).numel())
+    if seg_table.dim() != 3 or F < 1:
+        raise ValueError(f"{name}: the segment table must be [F, rows, 5], got {tuple(seg_table.shape)}")
+    S = int(seg_table.shape[1])
+    _jpeg_dec_arg(name, "seg_table", seg_table, torch.int64, (F, S, 5))
+    _jpeg_dec_arg(name, "frame_info", frame_info, torch.int64, (F, 3))
+    _jpeg_dec_arg(name, "tset", tset, torch.int32, (F,))
+    words = jpeg_dec_size(3, H, W, subsampling)
+    if _jpeg_dec_arg(name, "tables", tables, torch.int32).dim() != 2 or tables.shape[0] < 1 or tables.shape[1] != words:
+        raise ValueError(f"{name}: tables must be [n_sets, {words}], got {tuple(tables.shape)}")
+    coefs = torch.empty(F, jpeg_dec_size(0, H, W, subsampling), 64, dtype=torch.int16, device=data.device)
+    status = torch.empty(F, S, dtype=torch.int32, device=data.device)
+    check(_lib.load().ld_jpeg_decode_entropy(_ptr(data), data.numel(), _ptr(seg_table), _ptr(frame_info), _ptr(ri), _ptr(tables),
+                                             _ptr(tset), int(tables.shape[0]), _ptr(coefs), _ptr(status), F, S, int(H), int(W), sub,
+                                             _stream()), "ld_jpeg_decode_entropy")
+    return coefs, status
+
+
+def jpeg_decode_rgb(coefs, tables, tset, H: int, W: int, subsampling: str = "420", out=None):
+    """coefficients int16 [F, blocks, 64] -> uint8 frames [F, H, W, 3] (out: a uint8 [F, H, W, 3] whose rows and frames may be
+    strided, e.g. a window of a wider buffer).  Two launches; does not synchronise."""
+    name = "jpeg_decode_rgb"
+    sub = _jpeg_sub(name, subsampling)
+    blocks, words = jpeg_dec_size(0, H, W, subsampling), jpeg_dec_size(3, H, W, subsampling)
+    if not isinstance(coefs, torch.Tensor) or coefs.dim() != 3:
+        raise TypeError(f"{name}: the coefficients must be an int16 tensor [F, {blocks}, 64]")
+    F = int(coefs.shape[0])
+    _jpeg_dec_arg(name, "coefs", coefs, torch.int16, (F, blocks, 64))
+    _jpeg_dec_arg(name, "tset", tset, torch.int32, (F,))
+    if _jpeg_dec_arg(name, "tables", tables, torch.int32).dim() != 2 or tables.shape[0] < 1 or tables.shape[1] != words:
+        raise ValueError(f"{name}: tables must be [n_sets, {words}], got {tuple(tables.shape)}")
+    if out is None:
+        out = torch.empty(F, int(H), int(W), 3, dtype=torch.uint8, device=coefs.device)
+    if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (F, int(H), int(W), 3)
+            or out.stride(3) != 1 or out.stride(2) != 3):
+        raise ValueError(f"{name}: out must be uint8 [{F}, {H}, {W}, 3] with contiguous pixels (rows and frames may be strided)")
+    planes = torch.empty(F, jpeg_dec_size(2, H, W, subsampling), dtype=torch.uint8, device=coefs.device)
+    check(_lib.load().ld_jpeg_decode_rgb(_ptr(coefs), _ptr(tables), _ptr(tset), int(tables.shape[0]), _ptr(planes), _ptr(out),
+                                         out.stride(0), out.stride(1), F, int(H), int(W), sub, _stream()), "ld_jpeg_decode_rgb")
+    return out
+
+
 SSIM_TAPS, SSIM_SIGMA = 11, 1.5                      # LD_SSIM_TAPS of include/landiff_hip.h
 SSIM_TILE_H, SSIM_TILE_ELEMS = 32, 48               # LD_SSIM_TILE_H / LD_SSIM_TILE_ELEMS: they size the workspace, which the library checks
 

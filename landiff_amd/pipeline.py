@@ -100,6 +100,7 @@ class LanDiffPipeline:
         self.last_metrics = None          # compare: the ClipMetrics of the last comparison
         self.last_retime = None           # retime: RetimePlan.as_dict() of the last retimed clip
         self.last_encode = None           # encode: encode.encode_report() of the last encoded clip
+        self.last_decode = None           # decode: decode.decode_report() of the last decoded clip
 
     def _conform(self, frames, conform, keep_mask=None):
         """The conform stage of extend_video / edit_video: `frames` of any size / frame rate -> the 4T-3 frames of
@@ -149,11 +150,13 @@ class LanDiffPipeline:
         self._t("retime", t0)
         return out
 
-    def encode(self, frames, cfg=None):
+    def encode(self, frames, cfg=None, verify: bool = False):
         """uint8 frames [F, H, W, 3] -> list of F `bytes`, each a complete baseline JPEG, encoded on the pipeline's device (cfg: an
         encode.JpegConfig, default quality 95 at 4:2:0; landiff_amd.encode.encode_jpeg): the frames of a Motion-JPEG
         AVI (landiff.utils.write_mjpeg_avi_encoded) or stills.  A function of the frames alone: it takes what __call__,
-        generate_stream, extend_video, edit_video or retime returned.  Timed as "encode"; the figures are self.last_encode."""
+        generate_stream, extend_video, edit_video or retime returned.  Timed as "encode"; the figures are self.last_encode.
+        verify: the streams are decoded again where they are (landiff_amd.decode) and self.last_encode["verify"] holds
+        metrics.compare_clips(frames, decoded) -- PSNR, SSIM, the largest difference: what the written file loses."""
         from .encode import JpegConfig, encode_jpeg, encode_report
         if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.dtype != torch.uint8 or frames.shape[-1] != 3:
             raise ValueError(f"encode: frames must be uint8 [F, H, W, 3], got {getattr(frames, 'dtype', type(frames))} "
@@ -161,10 +164,34 @@ class LanDiffPipeline:
         cfg = JpegConfig() if cfg is None else cfg
         t0 = time.perf_counter()
         with torch.cuda.device(self.dev):
-            jpegs = encode_jpeg(frames.to(self.dev), cfg)
+            on_dev = frames.to(self.dev)
+            if verify:
+                from .decode import decode_jpeg
+                from .metrics import compare_clips
+                buf, offs, lens = encode_jpeg(on_dev, cfg, return_device=True)
+                raw = buf.cpu().numpy().tobytes()
+                jpegs = [raw[o:o + n] for o, n in zip(offs.tolist(), lens.tolist())]
+                m = compare_clips(on_dev.contiguous(), decode_jpeg((buf, offs, lens))).as_dict()
+            else:
+                jpegs = encode_jpeg(on_dev, cfg)
         self.last_encode = encode_report(jpegs, cfg)
+        if verify:
+            self.last_encode["verify"] = {"clip": m["clip"], "frames": {k: m["frames"][k] for k in ("psnr", "ssim", "max_abs")}}
         self._t("encode", t0)
         return jpegs
+
+    def decode_jpegs(self, jpegs, frames=None):
+        """(Named decode_jpegs: decode is the VAE's, latent -> frames.)  Baseline JPEG streams (a list of `bytes`, or the device triple of encode_jpeg(return_device=True)) -> uint8 frames
+        [F, H, W, 3] on the pipeline's device, equal to PIL's decode (landiff_amd.decode.decode_jpeg).  frames: the
+        indices to decode.  Timed as "decode"; the figures are self.last_decode."""
+        from .decode import decode_jpeg
+        t0 = time.perf_counter()
+        report = {}
+        with torch.cuda.device(self.dev):
+            out = decode_jpeg(jpegs, self.dev, frames=frames, report=report)
+        self.last_decode = report
+        self._t("decode", t0)
+        return out
 
     def _t(self, name, t0):
         torch.cuda.current_stream(self.dev).synchronize()      # (the stage's own stream: an overlapped AR decode keeps running)
