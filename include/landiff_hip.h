@@ -36,7 +36,7 @@ extern "C" {
  * the number: no existing signature moved).  16: ld_attn_route was added; ld_resize_u8 and ld_resize_mask_u8 joined later
  * (additions again).  17: ld_clip_diff_u8 and ld_clip_ssim_u8 were added; ld_retime_u8 joined later (an addition), and so did
  * ld_jpeg_size, ld_jpeg_coefs_u8, ld_jpeg_entropy_i16 and ld_jpeg_encode_u8 (additions again), then ld_jpeg_dec_size,
- * ld_jpeg_find_segments, ld_jpeg_decode_entropy and ld_jpeg_decode_rgb (additions). */
+ * ld_jpeg_find_segments, ld_jpeg_decode_entropy and ld_jpeg_decode_rgb (additions), then ld_gemv_route (an addition). */
 #define LD_ABI_VERSION 17
 
 int ld_version(void);
@@ -320,11 +320,29 @@ int ld_vq_nearest(const void* x, int64_t ldx, const float* codebook, int64_t* id
  * LlamaMLP2: landiff/llm/modules/transformer_blocks.py:67-88), then `resid + y`.  w_f32: fp32 weights,
  * x and out fp32 (GPT head, landiff/llm/models/transformer.py:115-118).  in_act is applied to x (bf16-rounded),
  * e.g. the SiLU in front of adaLN_modulation (landiff/diffusion/dit_video_concat.py:499-503).  norm_w (fp32 [K], optional)
- * fuses the block's RMSNorm in front of the projection: x -> bf16(x * rsqrt(mean(x^2) + norm_eps) * norm_w). */
+ * fuses the block's RMSNorm in front of the projection: x -> bf16(x * rsqrt(mean(x^2) + norm_eps) * norm_w).
+ * bias is bf16 [N]; resid has out's type (bf16, or fp32 when out_f32: the sum is then not rounded).
+ * in_act together with norm_w is NOT a form: no caller has one, and "normalise the activated x" and "activate the normalised x"
+ * are both plausible -- ld_gemv and ld_gemv_pairs refuse it (ld_gemv_wide refuses in_act altogether).
+ * LD_ERR_INVALID, nothing launched: null x / W / out, B outside [1, 4], N < 1, K or ldx no multiple of 8, B * K beyond the LDS
+ * (160 KB of bf16, or fp32 with fp32 weights), fp32 weights with W2 or without fp32 x and out, norm_w with fp32 x or weights,
+ * in_act with norm_w. */
 int ld_gemv(const void* x, int64_t ldx, int32_t x_f32, const void* W, const void* W2, int32_t w_f32,
             const void* bias, const void* resid, int64_t ldr, void* out, int64_t ldo, int32_t out_f32,
             int64_t B, int64_t N, int64_t K, int32_t in_act, int32_t act, const float* norm_w, float norm_eps,
             void* stream);
+
+/* The kernel ld_gemv takes for a call, without launching anything (the GEMV's ld_gemm_route): the launcher's own plan, run dry.
+ * gated: W2 given; normed: norm_w given.  Returns
+ *   0  the LDS-staged streaming kernel (ld_gemv_kernel): a wave takes *R weight rows at a time and keeps *U 16-byte loads per row
+ *      and lane in flight per trip over K (a trip covers 64 * U chunks of 8 elements); *J = 0.  fp32 weights: R = 1, U = 4.
+ *   1  the register-resident kernel (ld_gemv_reg_kernel; bf16 x and weights, no in_act, K <= 4096, or K <= 12288 for B <= 2 and no
+ *      W2): thread t of a workgroup owns chunks t, t + 256, ..., *J of them (1, 2 or 6), a workgroup takes *R rows at a time; *U = 0.
+ *   a negative code with ld_gemv's message for a shape or form ld_gemv refuses (see there; pointers and ldx are not part of the query).
+ * J, R, U may be null.  Honours LD_GEMV_MODE and LD_GEMV_R like the launch (read once per process).  Host logic only: it answers in
+ * a process without a GPU. */
+int ld_gemv_route(int64_t B, int64_t N, int64_t K, int32_t x_f32, int32_t w_f32, int32_t out_f32, int32_t gated, int32_t normed,
+                  int32_t in_act, int32_t* J, int32_t* R, int32_t* U);
 
 /* ld_gemv for P = B / 2 pairs of activation rows, 1 <= P <= LD_LLM_MAX_PAIRS: the P (cond, uncond) pairs of P samples of one
  * prompt decoded side by side (Semantic1DLM.sample once per seed, lm_model.py:417-508, through the cached blocks of
@@ -333,7 +351,8 @@ int ld_gemv(const void* x, int64_t ldx, int32_t x_f32, const void* W, const void
  * The bf16 forms the decode uses (K <= 4096, or K <= 12288 without W2) are one launch that reads every weight row from HBM once:
  * the register-resident kernel of the B = 2 route with the same chunk ownership per K and all 2P activation rows in registers.
  * Other forms (fp32 weights: the 17 MB head; fp32 x; in_act; longer K) run the B = 2 route once per pair.
- * LD_ERR_INVALID: odd B, null pointers, K % 8; LD_ERR_UNSUPPORTED: P > LD_LLM_MAX_PAIRS -- nothing is launched. */
+ * LD_ERR_INVALID: odd B, null pointers, K % 8, in_act with norm_w (see ld_gemv); LD_ERR_UNSUPPORTED: P > LD_LLM_MAX_PAIRS --
+ * nothing is launched. */
 #define LD_LLM_MAX_PAIRS 4
 int ld_gemv_pairs(const void* x, int64_t ldx, int32_t x_f32, const void* W, const void* W2, int32_t w_f32,
                   const void* bias, const void* resid, int64_t ldr, void* out, int64_t ldo, int32_t out_f32,

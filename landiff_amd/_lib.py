@@ -81,6 +81,7 @@ SIGNATURES: dict[str, list] = {
     "ld_gemv": _GEMV,
     "ld_gemv_pairs": _GEMV,
     "ld_gemv_wide": _GEMV,
+    "ld_gemv_route": [I64, I64, I64, I32, I32, I32, I32, I32, I32, POINTER(I32), POINTER(I32), POINTER(I32)],
     "ld_rmsnorm_bf16": [P, P, P, I64, I64, c_float, P],
     "ld_layernorm_bf16_to_f32": [P, I64, P, P, P, I64, I64, c_float, P],
     "ld_llm_rope_append": [P, P, P, P, P, P, P, I64, I64, I64, I64, P],

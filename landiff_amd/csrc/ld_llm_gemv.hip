@@ -29,7 +29,7 @@ struct GemvParams {
   long ldx, ldo, ldr;
   int x_f32, w_f32, out_f32;
   int in_act, act;
-  const float* norm_w;  // optional fused RMSNorm of x (bf16 x only): xn = bf16(x * rsqrt(mean(x^2)+eps) * norm_w)
+  const float* norm_w;  // optional fused RMSNorm of x (bf16 x only, never with in_act: gemv_check): xn = bf16(x * rsqrt(mean(x^2)+eps) * norm_w)
   float norm_eps;
   ChainSync cs;         // dependent-launch form (ld_gemv_reg_kernel<..., CHAIN = true> only)
 };
@@ -438,13 +438,55 @@ int launch_gemv_reg(const GemvParams& p, hipStream_t st, int* grid_out = nullptr
   return ld_check_launch(CHAIN ? "ld_gemv(chained)" : "ld_gemv");
 }
 
-// R rows per batch: R*J (x2 gated) 16-byte loads per thread in flight per batch, two batches deep.
+int gemv_mode() {
+  static const int mode = getenv("LD_GEMV_MODE") ? atoi(getenv("LD_GEMV_MODE")) : 0;     // 1 = streaming-loop kernel only
+  return mode;
+}
+
+int gemv_forced_r() {
+  static const int forced_r = getenv("LD_GEMV_R") ? atoi(getenv("LD_GEMV_R")) : 0;       // rows per batch of the register kernel
+  return forced_r;
+}
+
+// What a call will do (ld_gemv_route reports it; launch_gemv_b switches on it): the kernel and its template parameters.
+enum { GEMV_STREAM = 0, GEMV_REG = 1 };
+struct GemvPlan {
+  int kind;   // GEMV_STREAM: ld_gemv_kernel<B, w_f32, R, U>; GEMV_REG: ld_gemv_reg_kernel<B, R, J, gated, normed>
+  int J, R, U;
+};
+
+// The rows per batch the register kernel is instantiated with when `want` are asked for: R*J (x2 gated) 16-byte loads per thread
+// in flight per batch, two batches deep.
+constexpr int gemv_reg_rows(int B, int J, bool gated, int want) {
+  const int L1 = J * (gated ? 2 : 1);                // loads per thread per row
+  if (L1 <= 2 && B <= 2 && want >= 8) return 8;
+  if (L1 <= 4 && want >= 4) return 4;
+  return want >= 2 ? 2 : 1;
+}
+
+// The one statement of the dispatch.  Host logic only.
+GemvPlan gemv_plan(int B, int N, int K, bool x_f32, bool w_f32, bool gated, bool in_act) {
+  const int nchunk = K >> 3, forced_r = gemv_forced_r();
+  if (gemv_mode() != 1 && !w_f32 && !x_f32 && !in_act) {
+    int J = 0, want = 0;
+    if (nchunk <= 256) { J = 1; want = 4; }                                    // measured: tools/gemv_shapes.py
+    else if (nchunk <= 512) { J = 2; want = gated ? 2 : 4; }
+    else if (B <= 2 && nchunk <= 1536 && !gated) { J = 6; want = 2; }
+    if (J) return {GEMV_REG, J, gemv_reg_rows(B, J, gated, forced_r ? forced_r : want), 0};
+  }
+  if (w_f32) return {GEMV_STREAM, 0, 1, 4};
+  // short rows (one 16-byte load per lane covers a row: the DiT's adaLN modulations, K = 512): eight rows per wave and trip
+  // keep eight loads per lane in flight (1.3 -> 4+ TB/s on the 708 MB all-layers matrix)
+  if (!gated && nchunk <= 64 && N >= 4096) return {GEMV_STREAM, 0, 8, 1};
+  if (gated || N < 4096) return {GEMV_STREAM, 0, 1, 4};   // gated MLP, or few rows: keep all 256 CUs busy
+  return {GEMV_STREAM, 0, 2, 4};                          // (one row per wave measured slower at N = 6144: 12.4 vs 11.5 us)
+}
+
 template <int B, int J, bool GATED, bool NORM>
 int launch_gemv_reg_r(const GemvParams& p, int R, hipStream_t st) {
-  constexpr int L1 = J * (GATED ? 2 : 1);            // loads per thread per row
-  if constexpr (L1 <= 2 && B <= 2) { if (R >= 8) return launch_gemv_reg<B, 8, J, GATED, NORM>(p, st); }
-  if constexpr (L1 <= 4) { if (R >= 4) return launch_gemv_reg<B, 4, J, GATED, NORM>(p, st); }
-  if (R >= 2) return launch_gemv_reg<B, 2, J, GATED, NORM>(p, st);
+  if constexpr (gemv_reg_rows(B, J, GATED, 8) == 8) { if (R == 8) return launch_gemv_reg<B, 8, J, GATED, NORM>(p, st); }
+  if constexpr (gemv_reg_rows(B, J, GATED, 4) == 4) { if (R == 4) return launch_gemv_reg<B, 4, J, GATED, NORM>(p, st); }
+  if (R == 2) return launch_gemv_reg<B, 2, J, GATED, NORM>(p, st);
   return launch_gemv_reg<B, 1, J, GATED, NORM>(p, st);
 }
 
@@ -457,21 +499,14 @@ int launch_gemv_reg_j(const GemvParams& p, int R, hipStream_t st) {
   return norm ? launch_gemv_reg_r<B, J, false, true>(p, R, st) : launch_gemv_reg_r<B, J, false, false>(p, R, st);
 }
 
-int gemv_mode() {
-  static const int mode = getenv("LD_GEMV_MODE") ? atoi(getenv("LD_GEMV_MODE")) : 0;     // 1 = streaming-loop kernel only
-  return mode;
-}
+GemvPlan gemv_plan(const GemvParams& p, int B) { return gemv_plan(B, p.N, p.K, p.x_f32 != 0, p.w_f32 != 0, p.W2 != nullptr, p.in_act != 0); }
 
 // J of the register form launch_gemv_b<2> takes for these operands (0: it takes the LDS-staged kernel).  J fixes the bits of a
 // row's dot product (chunk ownership c = j * 256 + tid, the order of a thread's dot2 chain, the RMSNorm partial sums); R and B
 // do not: every (weight row, activation row) has its own accumulator, wave_sum_multi pairs lanes 32, 16, ..., 1 apart for any V.
 int gemv_pair_reg_j(const GemvParams& p) {
-  const int nchunk = p.K >> 3;
-  if (gemv_mode() == 1 || p.w_f32 || p.x_f32 || p.in_act) return 0;
-  if (nchunk <= 256) return 1;
-  if (nchunk <= 512) return 2;
-  if (nchunk <= 1536 && !p.W2) return 6;
-  return 0;
+  const GemvPlan pl = gemv_plan(p, 2);
+  return pl.kind == GEMV_REG ? pl.J : 0;
 }
 
 // ld_gemv_pairs, B = 2 P in {4, 6, 8}: ld_gemv_reg_kernel at the B = 2 route's J with all B activation rows in registers (B * J
@@ -501,23 +536,30 @@ bool gemv_pairs_in_one_launch(const GemvParams& p, int J) { return p.B > 2 && J 
 
 template <int B>
 int launch_gemv_b(const GemvParams& p, hipStream_t st) {
-  const int mode = gemv_mode();
-  static const int forced_r = getenv("LD_GEMV_R") ? atoi(getenv("LD_GEMV_R")) : 0;
-  const int nchunk = p.K >> 3;
-  const bool gated = p.W2 != nullptr;
-  if (mode != 1 && !p.w_f32 && !p.x_f32 && !p.in_act) {
-    if (nchunk <= 256) return launch_gemv_reg_j<B, 1>(p, forced_r ? forced_r : 4, st);     // measured: tools/gemv_shapes.py
-    if (nchunk <= 512) return launch_gemv_reg_j<B, 2>(p, forced_r ? forced_r : (gated ? 2 : 4), st);
-    if constexpr (B <= 2) {
-      if (nchunk <= 1536 && !gated) return launch_gemv_reg_j<B, 6>(p, forced_r ? forced_r : 2, st);
-    }
+  const GemvPlan pl = gemv_plan(p, B);
+  if (pl.kind == GEMV_REG) {
+    if (pl.J == 1) return launch_gemv_reg_j<B, 1>(p, pl.R, st);
+    if (pl.J == 2) return launch_gemv_reg_j<B, 2>(p, pl.R, st);
+    if constexpr (B <= 2) return launch_gemv_reg_j<B, 6>(p, pl.R, st);
+    return ld_set_error(LD_ERR_UNSUPPORTED, "ld_gemv: no register form J = %d for B = %d", pl.J, B);
   }
   if (p.w_f32) return launch_gemv_cfg<B, true, 1>(p, st);
-  // short rows (one 16-byte load per lane covers a row: the DiT's adaLN modulations, K = 512): eight rows per wave and trip
-  // keep eight loads per lane in flight (1.3 -> 4+ TB/s on the 708 MB all-layers matrix)
-  if (!p.W2 && nchunk <= 64 && p.N >= 4096) return launch_gemv_cfg<B, false, 8, 1>(p, st);
-  if (p.W2 || p.N < 4096) return launch_gemv_cfg<B, false, 1>(p, st);   // gated MLP, or few rows: keep all 256 CUs busy
-  return launch_gemv_cfg<B, false, 2>(p, st);     // (one row per wave measured slower at N = 6144: 12.4 vs 11.5 us)
+  if (pl.R == 8) return launch_gemv_cfg<B, false, 8, 1>(p, st);
+  if (pl.R == 2) return launch_gemv_cfg<B, false, 2>(p, st);
+  return launch_gemv_cfg<B, false, 1>(p, st);
+}
+
+// The argument rules of ld_gemv (ld_gemv_route answers with the same codes and messages; it has no ldx: 0).
+int gemv_check(int64_t B, int64_t N, int64_t K, int64_t ldx, int32_t x_f32, int32_t w_f32, int32_t out_f32, bool gated, bool normed,
+               int32_t in_act) {
+  LD_REQUIRE(B >= 1 && B <= MAXB, "ld_gemv: batch %ld not in [1,%d]", (long)B, MAXB);
+  LD_REQUIRE(N >= 1 && K >= 8 && K % 8 == 0 && ldx % 8 == 0, "ld_gemv: K and ldx must be multiples of 8");
+  LD_REQUIRE((size_t)B * K * (w_f32 ? 4 : 2) + 64 <= 160 * 1024, "ld_gemv: B*K too large for the LDS-staged activations");
+  LD_REQUIRE(!(w_f32 && gated), "ld_gemv: gated form needs bf16 weights");
+  LD_REQUIRE(!w_f32 || (x_f32 && out_f32), "ld_gemv: fp32 weights need fp32 in/out");
+  LD_REQUIRE(!normed || (!x_f32 && !w_f32), "ld_gemv: fused RMSNorm needs bf16 x and weights");
+  LD_REQUIRE(!(in_act && normed), "ld_gemv: in_act with a fused RMSNorm is not a form (no caller has one)");
+  return 0;
 }
 
 GemvParams make_gemv_params(const void* x, int64_t ldx, int32_t x_f32, const void* W, const void* W2, int32_t w_f32, const void* bias,
@@ -538,12 +580,7 @@ LD_API int ld_gemv(const void* x, int64_t ldx, int32_t x_f32, const void* W, con
                    int64_t B, int64_t N, int64_t K, int32_t in_act, int32_t act, const float* norm_w, float norm_eps,
                    void* stream) {
   LD_REQUIRE(x && W && out, "ld_gemv: null pointer");
-  LD_REQUIRE(B >= 1 && B <= MAXB, "ld_gemv: batch %ld not in [1,%d]", (long)B, MAXB);
-  LD_REQUIRE(K % 8 == 0 && ldx % 8 == 0, "ld_gemv: K and ldx must be multiples of 8");
-  LD_REQUIRE((size_t)B * K * (w_f32 ? 4 : 2) + 64 <= 160 * 1024, "ld_gemv: B*K too large for the LDS-staged activations");
-  LD_REQUIRE(!(w_f32 && W2), "ld_gemv: gated form needs bf16 weights");
-  LD_REQUIRE(!w_f32 || (x_f32 && out_f32), "ld_gemv: fp32 weights need fp32 in/out");
-  LD_REQUIRE(!norm_w || (!x_f32 && !w_f32), "ld_gemv: fused RMSNorm needs bf16 x and weights");
+  if (int rc = gemv_check(B, N, K, ldx, x_f32, w_f32, out_f32, W2 != nullptr, norm_w != nullptr, in_act)) return rc;
   const GemvParams p = make_gemv_params(x, ldx, x_f32, W, W2, w_f32, bias, resid, ldr, out, ldo, out_f32, B, N, K, in_act, act, norm_w, norm_eps);
   hipStream_t st = (hipStream_t)stream;
   switch (B) {
@@ -552,6 +589,17 @@ LD_API int ld_gemv(const void* x, int64_t ldx, int32_t x_f32, const void* W, con
     case 3: return launch_gemv_b<3>(p, st);
     default: return launch_gemv_b<4>(p, st);
   }
+}
+
+// ld_gemv's dispatch run dry: no HIP call.
+LD_API int ld_gemv_route(int64_t B, int64_t N, int64_t K, int32_t x_f32, int32_t w_f32, int32_t out_f32, int32_t gated, int32_t normed,
+                         int32_t in_act, int32_t* J, int32_t* R, int32_t* U) {
+  if (int rc = gemv_check(B, N, K, 0, x_f32, w_f32, out_f32, gated != 0, normed != 0, in_act)) return rc;
+  const GemvPlan pl = gemv_plan((int)B, (int)N, (int)K, x_f32 != 0, w_f32 != 0, gated != 0, in_act != 0);
+  if (J) *J = pl.J;
+  if (R) *R = pl.R;
+  if (U) *U = pl.U;
+  return pl.kind;
 }
 
 // ld_gemv for P = B / 2 pairs of activation rows (P samples of one prompt decoded side by side): rows (2p, 2p+1) come out with
@@ -569,6 +617,7 @@ LD_API int ld_gemv_pairs(const void* x, int64_t ldx, int32_t x_f32, const void* 
   LD_REQUIRE(!(w_f32 && W2), "ld_gemv_pairs: gated form needs bf16 weights");
   LD_REQUIRE(!w_f32 || (x_f32 && out_f32), "ld_gemv_pairs: fp32 weights need fp32 in/out");
   LD_REQUIRE(!norm_w || (!x_f32 && !w_f32), "ld_gemv_pairs: fused RMSNorm needs bf16 x and weights");
+  LD_REQUIRE(!(in_act && norm_w), "ld_gemv_pairs: in_act with a fused RMSNorm is not a form (no caller has one)");
   const GemvParams p = make_gemv_params(x, ldx, x_f32, W, W2, w_f32, bias, resid, ldr, out, ldo, out_f32, B, N, K, in_act, act, norm_w, norm_eps);
   hipStream_t st = (hipStream_t)stream;
   const int J = gemv_pair_reg_j(p);

@@ -314,6 +314,15 @@ def _gemv(symbol, x, w, out, w2, bias, resid, in_act, act, norm_w, norm_eps):
     B, K = x.shape
     N = w.shape[0]
     assert w.shape[1] == K and out.shape == (B, N) and x.stride(1) == 1 and out.stride(1) == 1 and w.is_contiguous()
+    # the kernels read bias as bf16 always, resid as out's type, norm_w as K floats: another dtype would be misread, not refused
+    if bias is not None and bias.dtype != torch.bfloat16:
+        raise ValueError(f"{symbol}: bias must be bf16, got {bias.dtype}")
+    if resid is not None and resid.dtype != out.dtype:
+        raise ValueError(f"{symbol}: resid must have out's dtype {out.dtype}, got {resid.dtype}")
+    if w2 is not None and not (w2.dtype == w.dtype and w2.shape == w.shape and w2.is_contiguous()):
+        raise ValueError(f"{symbol}: w2 must be contiguous {w.dtype} {tuple(w.shape)} like w, got {w2.dtype} {tuple(w2.shape)}")
+    if norm_w is not None and not (norm_w.dtype == torch.float32 and norm_w.numel() == K and norm_w.is_contiguous()):
+        raise ValueError(f"{symbol}: norm_w must be contiguous fp32 [{K}], got {norm_w.dtype} {tuple(norm_w.shape)}")
     check(getattr(_lib.load(), symbol)(_ptr(x), x.stride(0), int(x.dtype == torch.float32), _ptr(w), _ptr(w2),
                                        int(w.dtype == torch.float32), _ptr(bias), _ptr(resid),
                                        resid.stride(0) if resid is not None else 0, _ptr(out), out.stride(0),
