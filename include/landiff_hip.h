@@ -36,7 +36,8 @@ extern "C" {
  * the number: no existing signature moved).  16: ld_attn_route was added; ld_resize_u8 and ld_resize_mask_u8 joined later
  * (additions again).  17: ld_clip_diff_u8 and ld_clip_ssim_u8 were added; ld_retime_u8 joined later (an addition), and so did
  * ld_jpeg_size, ld_jpeg_coefs_u8, ld_jpeg_entropy_i16 and ld_jpeg_encode_u8 (additions again), then ld_jpeg_dec_size,
- * ld_jpeg_find_segments, ld_jpeg_decode_entropy and ld_jpeg_decode_rgb (additions), then ld_gemv_route (an addition). */
+ * ld_jpeg_find_segments, ld_jpeg_decode_entropy and ld_jpeg_decode_rgb (additions), then ld_gemv_route (an addition), then
+ * ld_jpeg_dec_sync_size and ld_jpeg_decode_entropy_sync (additions). */
 #define LD_ABI_VERSION 17
 
 int ld_version(void);
@@ -818,6 +819,31 @@ int ld_jpeg_decode_entropy(const uint8_t* data, int64_t data_bytes, const int64_
 int ld_jpeg_decode_rgb(const int16_t* coefs, const int32_t* tables, const int32_t* tset, int64_t n_sets, uint8_t* planes_ws,
                        uint8_t* out, int64_t frame_stride, int64_t row_stride, int64_t F, int64_t H, int64_t W,
                        int32_t subsampling, void* stream);
+
+/* ---- the decode stage's second entropy route (ld_jpeg_dec_sync.hip; DESIGN 8.14, restated in tests/jpeg_sync_ref.py) ----
+ * One lane per subsequence of sub_bytes raw bytes of a restart segment (a power of two in 64 .. 1024) instead of one lane per
+ * segment: for streams without restart markers.  coefs and status are exactly ld_jpeg_decode_entropy's, whatever max_rounds is
+ * (1 .. 4096): a segment whose subsequences have not agreed after max_rounds rounds, and a segment with an error, is decoded once
+ * more by the lane-per-segment kernel in the same call, without a host round trip.  Two runs give the same bits.
+ * scan_bytes: an upper bound the host knows of the summed lengths of all segments (the frames' scan bytes; <= data_bytes); it
+ * sizes the flat list of subsequences, SUBSEQUENCES = scan_bytes / sub_bytes + F S + 64 F rounded up to 64, and with it the
+ * workspace (16-byte aligned) and every grid.  A frame that does not fit the list (a table that ld_jpeg_find_segments did not
+ * write) falls back whole.
+ * sync_info int32 [F][S][2]: the rounds that changed an exit of the segment (its rounds to the fixed point, at most max_rounds),
+ * and 1 if the segment fell back.  exits (optional, with exits_index; for tests) int64 [SUBSEQUENCES][4]: per subsequence the exit
+ * state p = 8 x raw byte + bit, j the block within the MCU, k the next zigzag index, and the blocks it completed; exits_index int32
+ * [F][S][2]: the segment's first row of `exits` and its rows (0 for rows the frame does not use and for frames with MARKERS).
+ * Every refusal answers before a launch. */
+#define LD_JPEG_DEC_SYNC_SIZE_WORKSPACE 0
+#define LD_JPEG_DEC_SYNC_SIZE_SUBSEQUENCES 1
+/* bytes of the workspace / rows of `exits` (negative: the refusal's code; sub_bytes and max_rounds are checked before anything else) */
+int64_t ld_jpeg_dec_sync_size(int32_t what, int64_t scan_bytes, int64_t F, int64_t S, int32_t sub_bytes, int32_t max_rounds);
+
+int ld_jpeg_decode_entropy_sync(const uint8_t* data, int64_t data_bytes, const int64_t* seg_table, const int64_t* frame_info,
+                                const int32_t* ri, const int32_t* tables, const int32_t* tset, int64_t n_sets, int16_t* coefs,
+                                int32_t* status, int64_t F, int64_t S, int64_t H, int64_t W, int32_t subsampling, int64_t scan_bytes,
+                                int32_t sub_bytes, int32_t max_rounds, void* workspace, int64_t workspace_bytes, int32_t* sync_info,
+                                int64_t* exits, int32_t* exits_index, void* stream);
 
 /* ---- clip comparison (ld_metrics.hip; landiff_amd/metrics.py) ----
  * Two uint8 channels-last clips a, b [F][H][W][C], C 1 or 3 (the pipeline's output layout), and an optional keep-mask [F][H][W] u8

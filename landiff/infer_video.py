@@ -134,7 +134,14 @@ def parse_args(argv=None):
                              "(baseline JPEG, equal to PIL's decode byte for byte; landiff_amd/decode.py): only the compressed bytes "
                              "are uploaded, with --clip_fit only the frames the conform stage reads are decoded, and "
                              "<name>_decode.json is written.  host (the default): PIL, frame by frame, unchanged.")
+    parser.add_argument("--jpeg_entropy", choices=("segment", "sync", "auto"), default="segment",
+                        help="With --video_decoder gpu: how the Huffman decode is spread over the GPU.  segment (the default): one "
+                             "lane per restart segment, unchanged.  sync: one lane per 256 bytes of a segment, for files written "
+                             "without restart markers (PIL, ffmpeg, cameras; landiff_amd/decode.py, DESIGN 8.14); the same frames "
+                             "byte for byte.  auto: sync where the file's segments are long.")
     args = parser.parse_args(argv)
+    if args.jpeg_entropy != "segment" and args.video_decoder != "gpu":
+        parser.error("--jpeg_entropy goes with --video_decoder gpu")
     args.jpeg = None
     if args.video_encoder == "gpu":
         from landiff_amd.encode import JpegConfig
@@ -460,7 +467,8 @@ def _save_video(args, video, path: str, fps: int = 8):
         np.save(f"{stem}.frames.npy", frames.numpy())
     if ref_path:
         from landiff_amd.metrics import compare_clips, temporal_profile, write_metrics_json
-        ref = load_clip(ref_path, getattr(args, "video_decoder", "host"), report=f"{stem}_decode.json")
+        ref = load_clip(ref_path, getattr(args, "video_decoder", "host"), report=f"{stem}_decode.json",
+                        entropy=getattr(args, "jpeg_entropy", "segment"))
         if tuple(ref.shape) != tuple(frames.shape):
             raise ValueError(f"--compare_to {ref_path}: the reference is {tuple(ref.shape)}, the video written to {path} is "
                              f"{tuple(frames.shape)}; the shapes must be equal (nothing is resized)")
@@ -499,13 +507,16 @@ def infer_diffusion(args, semantic_token):
     print(f"save video to {task.save_file_name}")
 
 
-def load_clip(path: str, decoder: str = "host", needed=None, report: str | None = None) -> torch.Tensor:
+def load_clip(path: str, decoder: str = "host", needed=None, report: str | None = None, entropy: str = "segment") -> torch.Tensor:
     """uint8 frames [F, H, W, 3] from a .npy (save_video_tensor's fallback format) or, through imageio, a video file; without
     imageio a Motion-JPEG .avi (what this project writes) is read with landiff.utils.read_mjpeg_avi.
     decoder="gpu" (--video_decoder gpu): a Motion-JPEG .avi is decoded on the current device (landiff_amd.decode: equal to PIL's
     decode) and the frames returned are a device tensor; anything else is read as with "host".  needed: a function (F, H, W) ->
     the frame indices that will be read (--clip_fit: conform_plan's); only those are decoded, the others are zero.  report: where
-    decode_report's figures are written (<name>_decode.json)."""
+    decode_report's figures are written (<name>_decode.json).  entropy (--jpeg_entropy): decode_jpeg's entropy route, with
+    decoder="gpu" only."""
+    if entropy != "segment" and decoder != "gpu":
+        raise ValueError(f"load_clip: entropy={entropy!r} goes with decoder=\"gpu\"")
     if decoder == "gpu" and path.lower().endswith(".avi"):
         import json
         from landiff.utils import read_mjpeg_avi_chunks
@@ -514,11 +525,11 @@ def load_clip(path: str, decoder: str = "host", needed=None, report: str | None 
         dev = torch.device(f"cuda:{torch.cuda.current_device()}")
         figures = {}
         if needed is None:
-            clip = decode_jpeg(chunks, dev, report=figures)
+            clip = decode_jpeg(chunks, dev, report=figures, entropy=entropy)
         else:
             idx = sorted({int(k) for k in needed(len(chunks), H, W)})
             clip = torch.zeros(len(chunks), H, W, 3, dtype=torch.uint8, device=dev)
-            clip[torch.tensor(idx, device=dev)] = decode_jpeg(chunks, dev, frames=idx, report=figures)
+            clip[torch.tensor(idx, device=dev)] = decode_jpeg(chunks, dev, frames=idx, report=figures, entropy=entropy)
             figures["decoded_frames"] = idx
         if report:
             figures["source"], figures["clip_frames"] = path, len(chunks)
@@ -556,7 +567,8 @@ def _load_clip_on_gpu(args, path: str, pipe) -> torch.Tensor:
         from landiff_amd.conform import conform_plan
         d = pipe.cfg.dit
         needed = lambda F, H, W: conform_plan((F, H, W), 4 * d.latent_frames - 3, 8 * d.latent_h, 8 * d.latent_w, args.conform).frame_idx
-    return load_clip(path, "gpu", needed=needed, report=f"{args.save_file_name}_decode.json")
+    return load_clip(path, "gpu", needed=needed, report=f"{args.save_file_name}_decode.json",
+                     entropy=getattr(args, "jpeg_entropy", "segment"))
 
 
 def build_continuation(args, n_seg=None, theia=None):

@@ -129,6 +129,8 @@ SIGNATURES: dict[str, list] = {
     "ld_jpeg_find_segments": [P, I64, P, P, P, P, I64, I64, I64, I64, I32, P],
     "ld_jpeg_decode_entropy": [P, I64, P, P, P, P, P, I64, P, P, I64, I64, I64, I64, I32, P],
     "ld_jpeg_decode_rgb": [P, P, P, I64, P, P, I64, I64, I64, I64, I64, I32, P],
+    "ld_jpeg_dec_sync_size": [I32, I64, I64, I64, I32, I32],
+    "ld_jpeg_decode_entropy_sync": [P, I64, P, P, P, P, P, I64, P, P, I64, I64, I64, I64, I32, I64, I32, I32, P, I64, P, P, P, P],
     "ld_clip_diff_u8": [P, P, P, P, I64, I64, I64, I64, P],
     "ld_clip_ssim_u8": [P, P, P, P, P, P, I64, I64, I64, I64, I64, P],
     "ld_timestep_embedding": [P, P, I64, I64, c_float, P],
@@ -187,7 +189,8 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = (c_char_p if name in ("ld_last_error", "ld_attn_last_kernel") else
-                      ctypes.c_int64 if name in ("ld_groupnorm_stats_blocks", "ld_conv_gn_partials_size", "ld_jpeg_size", "ld_jpeg_dec_size")
+                      ctypes.c_int64 if name in ("ld_groupnorm_stats_blocks", "ld_conv_gn_partials_size", "ld_jpeg_size", "ld_jpeg_dec_size",
+                                              "ld_jpeg_dec_sync_size")
                       else c_int)
     _lib = lib
     return lib

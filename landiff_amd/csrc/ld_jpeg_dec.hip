@@ -22,65 +22,17 @@
 // jpeg_colour_kernel: one workgroup per 256 pixels of one output row: chroma upsampling (read clamped to the real chroma size),
 //   colour conversion, the 768 bytes staged in LDS and stored as consecutive bytes.  All offsets are 64-bit.
 // Nothing depends on the order in which lanes or workgroups finish: two runs give the same bits.
-#include "ld_common.h"
-#include "../../include/landiff_hip.h"
+// The table layout, the geometry and the bit reader are ld_jpeg_dec_dev.h's, shared with the second entropy route
+// (ld_jpeg_dec_sync.hip), which also launches jpeg_decode_entropy_kernel under a mask for the segments it hands back.
+#include "ld_jpeg_dec_dev.h"
+
+using namespace ld_jpeg_dec;
 
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxWidth = 8192, kMaxHeight = 65535;          // the encoder's limits (ld_jpeg.hip)
 constexpr int kFindBytes = 16;                               // bytes a thread searches per chunk
 constexpr int kChunk = kThreads * kFindBytes;
-// offsets into one table set (int32 words; LD_JPEG_DEC_TABLE_WORDS in all)
-constexpr int kTabQuant = 0, kTabHuff = 192, kHuffWords = 544, kTabWords = LD_JPEG_DEC_TABLE_WORDS;
-constexpr int kHuffLimit = 0, kHuffOff = 16, kHuffVals = 32, kHuffLook = 288;      // within one Huffman table
-static_assert(kTabHuff + 6 * kHuffWords == kTabWords, "table layout");
-
-struct Geom {
-  int mcu, bpm, mcux, mcuy, PH, PW;                // MCU edge, blocks per MCU, MCUs per row / column, the planes' padded size
-  long mcus, frame_blocks;
-};
-
-// The geometry of a frame; non-zero: the refusal's code (the message is set).
-int geometry(const char* who, int64_t H, int64_t W, int32_t subsampling, Geom* g) {
-  if (subsampling != 420 && subsampling != 444)
-    return ld_set_error(LD_ERR_UNSUPPORTED, "%s: subsampling must be 420 or 444, got %d", who, (int)subsampling);
-  LD_REQUIRE(H > 0 && W > 0, "%s: empty shape", who);
-  if (W > kMaxWidth || H > kMaxHeight)
-    return ld_set_error(LD_ERR_UNSUPPORTED, "%s: frames up to %d wide and %d high are supported, got %lld x %lld (H x W)", who,
-                        kMaxWidth, kMaxHeight, (long long)H, (long long)W);
-  g->mcu = subsampling == 420 ? 16 : 8;
-  g->bpm = subsampling == 420 ? 6 : 3;
-  g->mcux = (int)((W + g->mcu - 1) / g->mcu);
-  g->mcuy = (int)((H + g->mcu - 1) / g->mcu);
-  g->PH = g->mcuy * g->mcu;
-  g->PW = g->mcux * g->mcu;
-  g->mcus = (long)g->mcux * g->mcuy;
-  g->frame_blocks = g->mcus * g->bpm;
-  return LD_OK;
-}
-
-__device__ __forceinline__ long clampl(long v, long lo, long hi) { return v < lo ? lo : v > hi ? hi : v; }
-
-// the segments of a frame of `mcus` MCUs at restart interval ri, never more than the table's S rows
-__device__ __forceinline__ long segments_of(long mcus, long ri, long S) { return min(ri > 0 ? (mcus + ri - 1) / ri : 1L, S); }
-
-// exclusive scan of one value per thread over the workgroup (tmp: kThreads ints); the total is returned to every thread
-__device__ __forceinline__ int block_scan(int v, int* tmp, int* total) {
-  const int tid = threadIdx.x;
-  tmp[tid] = v;
-  __syncthreads();
-  for (int o = 1; o < kThreads; o <<= 1) {
-    const int add = tid >= o ? tmp[tid - o] : 0;
-    __syncthreads();
-    tmp[tid] += add;
-    __syncthreads();
-  }
-  const int incl = tmp[tid];
-  *total = tmp[kThreads - 1];
-  __syncthreads();
-  return incl - v;
-}
 
 struct FindArgs {
   const uint8_t* data;
@@ -126,7 +78,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_find_segments_kernel(FindArgs a
     const int e = first_end;
     if (lo - c0 >= e) mine = 0;                    // markers after the end are no markers (the end's own thread stopped there)
     int total;
-    long k = count + block_scan(mine, tmp, &total);
+    long k = count + block_scan<kThreads>(mine, tmp, &total);
     for (long i = lo; i < hi && mine > 0; ++i) {
       if (p[i] != 0xFF || kind(i, &m) != 1) continue;
       if (m != (int)(k & 7)) order = 0;
@@ -164,6 +116,7 @@ struct EntropyArgs {
   const int32_t* tset;                             // [F]
   int16_t* coefs;                                  // [F][frame_blocks][64]
   int32_t* status;                                 // [F][S]
+  const int32_t* mask;                             // null, or [F][S]: only segments with a non-zero word are decoded
   long data_bytes, S, mcus, frame_blocks, n_sets;
   int bpm;
 };
@@ -179,6 +132,7 @@ __global__ __launch_bounds__(64) void jpeg_decode_entropy_kernel(EntropyArgs a) 
   __syncthreads();
   const long s = (long)blockIdx.x * 64 + threadIdx.x;
   if (s >= a.S) return;
+  if (a.mask && !a.mask[f * a.S + s]) return;     // (the sync route's fallback: the other segments are left as they are)
   const long nf = segments_of(a.mcus, max(a.ri[f], 0), a.S);
   if (s >= nf) { a.status[f * a.S + s] = LD_JPEG_DEC_OK; return; }
   const int64_t* row = a.seg + (f * a.S + s) * 5;
@@ -188,44 +142,10 @@ __global__ __launch_bounds__(64) void jpeg_decode_entropy_kernel(EntropyArgs a) 
   int16_t* out = a.coefs + (f * a.frame_blocks + fm * a.bpm) * 64;
   int status = (a.info[3 * f] == nf - 1 && a.info[3 * f + 1] == 1) ? LD_JPEG_DEC_OK : LD_JPEG_DEC_MARKERS;
 
-  unsigned long long buf = 0;                      // the next bits, from bit 63 down; zeros past the segment's end
-  int nbits = 0;
-  long pos = 0;
-  auto fill = [&]() {
-    while (nbits <= 56 && pos < end) {
-      const unsigned long long b = p[pos++];
-      if (b == 0xFF) ++pos;                        // the stuffed 0x00
-      buf |= b << (56 - nbits);
-      nbits += 8;
-    }
-  };
-  // one Huffman symbol (>= 0) or minus a status
-  auto symbol = [&](const int* T) {
-    fill();
-    const uint32_t c16 = (uint32_t)(buf >> 48);
-    const int e = T[kHuffLook + (c16 >> 8)];
-    int l = e >> 8, v = e & 255;
-    if (!e) {                                      // no code of 8 bits or fewer
-      l = 9;
-      while (l <= 16 && c16 >= (uint32_t)T[kHuffLimit + l - 1]) ++l;
-      if (l > 16) return nbits < 16 ? -LD_JPEG_DEC_OVERRUN : -LD_JPEG_DEC_BAD_CODE;
-      v = T[kHuffVals + ((T[kHuffOff + l - 1] + (int)(c16 >> (16 - l))) & 255)] & 255;
-    }
-    if (l > nbits) return -LD_JPEG_DEC_OVERRUN;
-    buf <<= l;
-    nbits -= l;
-    return v;
-  };
-  // n in 1..15 bits, EXTENDed (F.2.2.1); false: past the segment's end
-  auto receive = [&](int n, int* v) {
-    fill();
-    if (n > nbits) return false;
-    const int r = (int)(buf >> (64 - n));
-    buf <<= n;
-    nbits -= n;
-    *v = r < (1 << (n - 1)) ? r - (1 << n) + 1 : r;
-    return true;
-  };
+  BitReader<false> rd;
+  rd.open(p, end, 0, 0);
+  auto symbol = [&](const int* T) { return rd.symbol(T); };
+  auto receive = [&](int n, int* v) { return rd.receive(n, v); };
 
   int pred0 = 0, pred1 = 0, pred2 = 0;            // the DC predictors: 0 at the segment's start
   for (long b = 0; b < nblk; ++b) {
@@ -234,7 +154,7 @@ __global__ __launch_bounds__(64) void jpeg_decode_entropy_kernel(EntropyArgs a) 
 #pragma unroll
     for (int i = 0; i < 8; ++i) z[i] = make_int4(0, 0, 0, 0);
     if (status) continue;
-    const int j = (int)(b % a.bpm), c = a.bpm == 6 ? (j < 4 ? 0 : j - 3) : j;
+    const int c = component_of((int)(b % a.bpm), a.bpm);
     const int* dc = tab + 2 * c * kHuffWords;
     const int* ac = dc + kHuffWords;
     int t = symbol(dc), v = 0;
@@ -390,14 +310,14 @@ __global__ __launch_bounds__(kThreads) void jpeg_colour_kernel(ColourArgs a) {
   for (int i = tid; i < nbytes; i += kThreads) dst[i] = line[i];
 }
 
-bool aligned(const void* p, size_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
-
-int check_frames(const char* who, int64_t F) {
-  LD_REQUIRE(F > 0 && F < (1 << 16), "%s: 1 .. 65535 frames a call, got %lld", who, (long long)F);
-  return LD_OK;
-}
-
 }  // namespace
+
+void ld_jpeg_dec::launch_entropy_segments(const uint8_t* data, long data_bytes, const int64_t* seg_table, const int64_t* frame_info,
+                                          const int32_t* ri, const int32_t* tables, const int32_t* tset, long n_sets, int16_t* coefs,
+                                          int32_t* status, const int32_t* mask, long F, long S, const Geom& g, hipStream_t stream) {
+  EntropyArgs a{data, seg_table, frame_info, ri, tables, tset, coefs, status, mask, data_bytes, S, g.mcus, g.frame_blocks, n_sets, g.bpm};
+  hipLaunchKernelGGL(jpeg_decode_entropy_kernel, dim3((unsigned)((S + 63) / 64), (unsigned)F), dim3(64), 0, stream, a);
+}
 
 LD_API int64_t ld_jpeg_dec_size(int32_t what, int64_t H, int64_t W, int32_t subsampling) {
   Geom g;
@@ -438,9 +358,8 @@ LD_API int ld_jpeg_decode_entropy(const uint8_t* data, int64_t data_bytes, const
   Geom g;
   if (int rc = geometry("ld_jpeg_decode_entropy", H, W, subsampling, &g)) return rc;
   LD_REQUIRE((S + 63) / 64 < (1L << 31), "ld_jpeg_decode_entropy: %lld segments a frame exceed one launch", (long long)S);
-  EntropyArgs a{data, seg_table, frame_info, ri, tables, tset, coefs, status, (long)data_bytes, (long)S, g.mcus, g.frame_blocks,
-                (long)n_sets, g.bpm};
-  hipLaunchKernelGGL(jpeg_decode_entropy_kernel, dim3((unsigned)((S + 63) / 64), (unsigned)F), dim3(64), 0, (hipStream_t)stream, a);
+  launch_entropy_segments(data, (long)data_bytes, seg_table, frame_info, ri, tables, tset, (long)n_sets, coefs, status, nullptr, (long)F,
+                          (long)S, g, (hipStream_t)stream);
   return ld_check_launch("ld_jpeg_decode_entropy");
 }
 

@@ -20,6 +20,13 @@ STATUS = ("OK", "BAD_CODE", "OVERFLOW", "OVERRUN", "RANGE", "MARKERS")          
 TABLE_WORDS = 3456                                                               # LD_JPEG_DEC_TABLE_WORDS
 _LIMIT, _VALS = 0, 32                                                            # within one Huffman table's 544 words
 LATER = "4:2:2, other sampling factors and greyscale are later work"
+ENTROPY_ROUTES = ("segment", "sync", "auto")
+SUB_BYTES = (64, 128, 256, 512, 1024)                                            # what ld_jpeg_dec_sync_size accepts
+MAX_ROUNDS = 4096
+# "auto" takes the sync route when a segment holds more than this many subsequences on average.  Measured (DESIGN 8.14,
+# profiles/jpeg_decode_sync.txt): on noise frames at sub_bytes 256 the sync route loses at 17.6 subsequences a segment (0.65 x) and
+# wins at 52.8 (1.41 x); nothing between was measured on noise, so the threshold sits where no measured case loses.
+AUTO_SUBSEQUENCES_PER_SEGMENT = 32
 
 
 @dataclass(frozen=True)
@@ -247,7 +254,27 @@ def _device_headers(buf, offsets, lengths, sel):
             n *= 2
 
 
-def decode_jpeg(jpegs, device=None, frames=None, return_coefs: bool = False, out=None, report: dict | None = None):
+def check_entropy(entropy, sub_bytes, max_rounds, who="decode_jpeg") -> None:
+    """The refusals of the entropy route's arguments, on the host."""
+    if entropy not in ENTROPY_ROUTES:
+        raise ValueError(f"{who}: entropy must be one of {', '.join(ENTROPY_ROUTES)}, got {entropy!r}")
+    if isinstance(sub_bytes, bool) or not isinstance(sub_bytes, int) or sub_bytes not in SUB_BYTES:
+        raise ValueError(f"{who}: sub_bytes must be a power of two in 64 .. 1024, got {sub_bytes!r}")
+    if isinstance(max_rounds, bool) or not isinstance(max_rounds, int) or not 1 <= max_rounds <= MAX_ROUNDS:
+        raise ValueError(f"{who}: max_rounds must be in 1 .. {MAX_ROUNDS}, got {max_rounds!r}")
+
+
+def entropy_route(infos, sizes, sub_bytes: int = 256) -> str:
+    """What entropy="auto" decodes a call with, from what the host knows: "sync" when the mean bytes per restart segment (the scans'
+    bytes over the segments the headers promise) exceed AUTO_SUBSEQUENCES_PER_SEGMENT x sub_bytes, else "segment".  A pure function."""
+    if not infos or len(infos) != len(sizes):
+        raise ValueError("entropy_route: one size per stream is expected")
+    scan = sum(max(int(n) - i.scan_offset, 0) for i, n in zip(infos, sizes))
+    return "sync" if scan > AUTO_SUBSEQUENCES_PER_SEGMENT * sub_bytes * sum(i.segments for i in infos) else "segment"
+
+
+def decode_jpeg(jpegs, device=None, frames=None, return_coefs: bool = False, out=None, report: dict | None = None,
+                entropy: str = "segment", sub_bytes: int = 256, max_rounds: int = 32):
     """Baseline JPEG streams of one size -> uint8 frames [F, H, W, 3] on the device, equal to PIL's decode.
 
     jpegs: a list of `bytes` on the host (their bytes are uploaded once), or the (buffer, offsets, lengths) that
@@ -255,9 +282,13 @@ def decode_jpeg(jpegs, device=None, frames=None, return_coefs: bool = False, out
     that order (default: all).  out: a uint8 [F, H, W, 3] on the device to write into (rows and frames may be strided).
     return_coefs: (frames, coefficients int16 [F, blocks, 64] in ops.jpeg_coefs_u8's layout).  report: a dict that receives
     decode_report's figures.  Four launches, then one device-to-host copy: the segments' status words; any that is not 0 raises
-    ValueError with the frame, the segment and the status name, and no pixels are returned."""
+    ValueError with the frame, the segment and the status name, and no pixels are returned.
+    entropy: "segment" (one lane per restart segment: the launches above), "sync" (one lane per sub_bytes bytes of a segment, for
+    streams without restart markers; at most max_rounds rounds, then the segment route for what has not settled: DESIGN 8.14; its
+    sync_info words come back in the same copy as the status words) or "auto" (entropy_route decides for the call)."""
     import torch
     from . import ops
+    check_entropy(entropy, sub_bytes, max_rounds)
     triple = isinstance(jpegs, tuple) and len(jpegs) == 3 and isinstance(jpegs[0], torch.Tensor)
     count = len(jpegs[1]) if triple else len(jpegs)
     sel = list(range(count)) if frames is None else [int(k) for k in frames]
@@ -309,25 +340,44 @@ def decode_jpeg(jpegs, device=None, frames=None, return_coefs: bool = False, out
     rows = max(i.segments for i in infos)
     with torch.cuda.device(dev):
         seg, finfo = ops.jpeg_find_segments(data, small, meta[0], rows, H, W, sub)
-        coefs, status = ops.jpeg_decode_entropy(data, seg, finfo, meta[0], tables, meta[1], H, W, sub)
+        route = entropy_route(infos, sizes, sub_bytes) if entropy == "auto" else entropy
+        sync = None
+        if route == "sync":
+            coefs, status, sync = ops.jpeg_decode_entropy_sync(data, seg, finfo, meta[0], tables, meta[1], H, W, sub, sub_bytes, max_rounds,
+                                                               scan_bytes=sum(n - i.scan_offset for n, i in zip(sizes, infos)))
+        else:
+            coefs, status = ops.jpeg_decode_entropy(data, seg, finfo, meta[0], tables, meta[1], H, W, sub)
         pixels = ops.jpeg_decode_rgb(coefs, tables, meta[1], H, W, sub, out=out)
-        bad = status.cpu()                                                       # the one device-to-host copy
+        if sync is None:
+            bad = status.cpu()                                                   # the one device-to-host copy
+        else:                                                                    # (still one: the sync_info words ride along)
+            both = torch.cat([status[..., None], sync], dim=-1).cpu()
+            bad, sync = both[..., 0], both[..., 1:]
     if bool(bad.any()):
         r, s = (int(v) for v in bad.nonzero()[0])
         code = int(bad[r, s])
         raise ValueError(f"decode_jpeg: frame {sel[r]} segment {s}: {STATUS[code] if 0 <= code < len(STATUS) else code}")
     if report is not None:
-        report.update(decode_report(infos, sizes))
+        report.update(decode_report(infos, sizes, entropy=route, sub_bytes=sub_bytes, sync_info=sync))
     return (pixels, coefs) if return_coefs else pixels
 
 
-def decode_report(infos, sizes) -> dict:
-    """What <name>_decode.json holds: infos the decoded frames' JpegInfo, sizes their streams' bytes."""
+def decode_report(infos, sizes, entropy: str = "segment", sub_bytes: int = 256, sync_info=None) -> dict:
+    """What <name>_decode.json holds: infos the decoded frames' JpegInfo, sizes their streams' bytes; entropy the route that
+    decoded them, and for "sync" its sub_bytes and sync_info [F, rows, 2] (the rows a frame uses are counted)."""
     first = infos[0]
     segs = [i.segments for i in infos]
+    rounds, fallen = [], 0
+    if sync_info is not None:
+        for f, i in enumerate(infos):
+            rounds += [int(v) for v in sync_info[f, :i.segments, 0]]
+            fallen += int(sync_info[f, :i.segments, 1].sum())
+    extra = dict(entropy=entropy, sub_bytes=sub_bytes if entropy == "sync" else None,
+                 rounds=dict(max=max(rounds), mean=sum(rounds) / len(rounds)) if rounds else None,
+                 segments_fallen_back=fallen if entropy == "sync" else None)
     return dict(decoder="gpu", frames=len(infos), width=first.width, height=first.height, subsampling=first.subsampling,
                 total_bytes=sum(sizes), bytes_per_frame=dict(min=min(sizes), mean=sum(sizes) / len(sizes), max=max(sizes)),
                 table_sets=len({(i.quant, i.huffman) for i in infos}), restart_intervals=sorted({i.restart_interval for i in infos}),
                 segments_per_frame=dict(min=min(segs), max=max(segs)),
                 frames_without_restarts=sum(1 for i in infos if i.segments == 1 and i.mcus > 1),
-                rule="libjpeg islow inverse DCT, triangle chroma upsampling, 16-bit colour constants (DESIGN 8.13)")
+                rule="libjpeg islow inverse DCT, triangle chroma upsampling, 16-bit colour constants (DESIGN 8.13)", **extra)

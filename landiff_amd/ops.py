@@ -1060,6 +1060,55 @@ def jpeg_decode_entropy(data, seg_table, frame_info, ri, tables, tset, H: int, W
     return coefs, status
 
 
+def jpeg_dec_sync_size(what: int, scan_bytes: int, F: int, S: int, sub_bytes: int = 256, max_rounds: int = 32) -> int:
+    """ld_jpeg_dec_sync_size: 0 bytes of jpeg_decode_entropy_sync's workspace, 1 rows of its flat list of subsequences (and of the
+    exit table), from what the host knows: the frames' summed scan bytes, F frames of at most S segments.  Needs no GPU."""
+    n = _lib.load().ld_jpeg_dec_sync_size(int(what), int(scan_bytes), int(F), int(S), int(sub_bytes), int(max_rounds))
+    if n < 0:
+        check(int(n), "ld_jpeg_dec_sync_size")
+    return int(n)
+
+
+def jpeg_decode_entropy_sync(data, seg_table, frame_info, ri, tables, tset, H: int, W: int, subsampling: str = "420",
+                             sub_bytes: int = 256, max_rounds: int = 32, return_exits: bool = False, scan_bytes=None):
+    """jpeg_decode_entropy by the second route: one lane per subsequence of sub_bytes raw bytes of a segment, for
+    streams without restart markers -> (coefficients, status, sync_info int32 [F, rows, 2] = (rounds to the fixed point, 1 if the
+    segment fell back to the lane-per-segment kernel)[, (exits int64 [subsequences, 4] = (p, j, k, blocks), index int32 [F, rows, 2]
+    = (first row, rows) of every segment)]).  Coefficients and status are jpeg_decode_entropy's whatever max_rounds is.
+    scan_bytes: the frames' summed scan bytes where the caller knows them (default: all of data); it sizes the grids.  A fixed
+    number of launches; does not synchronise."""
+    name = "jpeg_decode_entropy_sync"
+    sub = _jpeg_sub(name, subsampling)
+    _jpeg_dec_arg(name, "data", data, torch.uint8)
+    F = int(_jpeg_dec_arg(name, "ri", ri, torch.int32).numel())
+    if seg_table.dim() != 3 or F < 1:
+        raise ValueError(f"{name}: the segment table must be [F, rows, 5], got {tuple(seg_table.shape)}")
+    S = int(seg_table.shape[1])
+    _jpeg_dec_arg(name, "seg_table", seg_table, torch.int64, (F, S, 5))
+    _jpeg_dec_arg(name, "frame_info", frame_info, torch.int64, (F, 3))
+    _jpeg_dec_arg(name, "tset", tset, torch.int32, (F,))
+    words = jpeg_dec_size(3, H, W, subsampling)
+    if _jpeg_dec_arg(name, "tables", tables, torch.int32).dim() != 2 or tables.shape[0] < 1 or tables.shape[1] != words:
+        raise ValueError(f"{name}: tables must be [n_sets, {words}], got {tuple(tables.shape)}")
+    scan_bytes = data.numel() if scan_bytes is None else min(int(scan_bytes), data.numel())
+    ws_bytes = jpeg_dec_sync_size(0, scan_bytes, F, S, sub_bytes, max_rounds)
+    dev = data.device
+    coefs = torch.empty(F, jpeg_dec_size(0, H, W, subsampling), 64, dtype=torch.int16, device=dev)
+    status = torch.empty(F, S, dtype=torch.int32, device=dev)
+    sync_info = torch.empty(F, S, 2, dtype=torch.int32, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    exits = index = None
+    if return_exits:
+        exits = torch.zeros(jpeg_dec_sync_size(1, scan_bytes, F, S, sub_bytes, max_rounds), 4, dtype=torch.int64, device=dev)
+        index = torch.empty(F, S, 2, dtype=torch.int32, device=dev)
+    check(_lib.load().ld_jpeg_decode_entropy_sync(_ptr(data), data.numel(), _ptr(seg_table), _ptr(frame_info), _ptr(ri), _ptr(tables),
+                                                  _ptr(tset), int(tables.shape[0]), _ptr(coefs), _ptr(status), F, S, int(H), int(W), sub,
+                                                  scan_bytes, int(sub_bytes), int(max_rounds), _ptr(ws), ws_bytes, _ptr(sync_info),
+                                                  _ptr(exits) if return_exits else None, _ptr(index) if return_exits else None,
+                                                  _stream()), "ld_jpeg_decode_entropy_sync")
+    return (coefs, status, sync_info, (exits, index)) if return_exits else (coefs, status, sync_info)
+
+
 def jpeg_decode_rgb(coefs, tables, tset, H: int, W: int, subsampling: str = "420", out=None):
     """coefficients int16 [F, blocks, 64] -> uint8 frames [F, H, W, 3] (out: a uint8 [F, H, W, 3] whose rows and frames may be
     strided, e.g. a window of a wider buffer).  Two launches; does not synchronise."""

@@ -180,15 +180,17 @@ class LanDiffPipeline:
         self._t("encode", t0)
         return jpegs
 
-    def decode_jpegs(self, jpegs, frames=None):
+    def decode_jpegs(self, jpegs, frames=None, entropy: str = "segment", sub_bytes: int = 256, max_rounds: int = 32):
         """(Named decode_jpegs: decode is the VAE's, latent -> frames.)  Baseline JPEG streams (a list of `bytes`, or the device triple of encode_jpeg(return_device=True)) -> uint8 frames
         [F, H, W, 3] on the pipeline's device, equal to PIL's decode (landiff_amd.decode.decode_jpeg).  frames: the
-        indices to decode.  Timed as "decode"; the figures are self.last_decode."""
+        indices to decode.  entropy, sub_bytes, max_rounds: decode_jpeg's entropy route ("sync" / "auto": one lane per sub_bytes
+        bytes of a restart segment, for streams without restart markers).  Timed as "decode"; the figures are
+        self.last_decode."""
         from .decode import decode_jpeg
         t0 = time.perf_counter()
         report = {}
         with torch.cuda.device(self.dev):
-            out = decode_jpeg(jpegs, self.dev, frames=frames, report=report)
+            out = decode_jpeg(jpegs, self.dev, frames=frames, report=report, entropy=entropy, sub_bytes=sub_bytes, max_rounds=max_rounds)
         self.last_decode = report
         self._t("decode", t0)
         return out

@@ -22,6 +22,28 @@ sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
 
 
+def stage_clip(chunks, dev):
+    """What decode_jpeg hands the kernels for these streams (also tools/jpeg_sync_bench.py's staging) -> dict(infos, data, scan, ri,
+    tables, tset, n_sets, rows, sub, seg, finfo, scan_bytes), the segment table already found."""
+    import numpy as np
+    import torch
+    from landiff_amd import decode as D
+    from landiff_amd import ops
+    infos = [D.parse_jpeg(c) for c in chunks]
+    starts = np.cumsum([0] + [len(c) for c in chunks[:-1]]).tolist()
+    data = torch.frombuffer(bytearray(b"".join(chunks)), dtype=torch.uint8).to(dev)
+    scan = torch.tensor([[s + i.scan_offset, len(c) - i.scan_offset] for s, i, c in zip(starts, infos, chunks)], dtype=torch.int64).to(dev)
+    ri = torch.tensor([i.restart_interval for i in infos], dtype=torch.int32).to(dev)
+    sets = {}
+    tset_l = [sets.setdefault((i.quant, i.huffman), len(sets)) for i in infos]
+    tables = torch.tensor([D.decode_tables(next(i for i, t in zip(infos, tset_l) if t == s)) for s in range(len(sets))], dtype=torch.int32).to(dev)
+    tset = torch.tensor(tset_l, dtype=torch.int32).to(dev)
+    rows, sub = max(i.segments for i in infos), infos[0].subsampling
+    seg, finfo = ops.jpeg_find_segments(data, scan, ri, rows, infos[0].height, infos[0].width, sub)
+    return dict(infos=infos, data=data, scan=scan, ri=ri, tables=tables, tset=tset, n_sets=len(sets), rows=rows, sub=sub, seg=seg, finfo=finfo,
+                scan_bytes=sum(len(c) - i.scan_offset for c, i in zip(chunks, infos)))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=5, help="calls between the two events of a window")
@@ -91,21 +113,13 @@ def main():
         else:
             write_mjpeg_avi(clip.cpu().numpy(), path, fps=fps)
         chunks, _, _ = read_mjpeg_avi_chunks(path)
-        infos = [D.parse_jpeg(c) for c in chunks]
+        st = stage_clip(chunks, dev)
+        infos, data, scan, ri, tables, tset, rows, sub, seg, finfo = (st[k] for k in ("infos", "data", "scan", "ri", "tables", "tset", "rows", "sub", "seg", "finfo"))
+        sets = range(st["n_sets"])
         total = sum(len(c) for c in chunks)
         say(f"{F} frames of {H} x {W} x 3 ({clip.numel() / 1e6:.0f} MB raw, {total / 1e6:.2f} MB of streams) written by {name}; "
             f"{infos[0].segments} segment(s) a frame")
         # ---- the launches, on what decode_jpeg hands them ----
-        starts = np.cumsum([0] + [len(c) for c in chunks[:-1]]).tolist()
-        data = torch.frombuffer(bytearray(b"".join(chunks)), dtype=torch.uint8).to(dev)
-        scan = torch.tensor([[s + i.scan_offset, len(c) - i.scan_offset] for s, i, c in zip(starts, infos, chunks)], dtype=torch.int64).to(dev)
-        ri = torch.tensor([i.restart_interval for i in infos], dtype=torch.int32).to(dev)
-        sets = {}
-        tset_l = [sets.setdefault((i.quant, i.huffman), len(sets)) for i in infos]
-        tables = torch.tensor([D.decode_tables(next(i for i, t in zip(infos, tset_l) if t == s)) for s in range(len(sets))], dtype=torch.int32).to(dev)
-        tset = torch.tensor(tset_l, dtype=torch.int32).to(dev)
-        rows, sub = max(i.segments for i in infos), infos[0].subsampling
-        seg, finfo = ops.jpeg_find_segments(data, scan, ri, rows, H, W, sub)
         coefs, status = ops.jpeg_decode_entropy(data, seg, finfo, ri, tables, tset, H, W, sub)
         out = ops.jpeg_decode_rgb(coefs, tables, tset, H, W, sub)
         assert not bool(status.any()) and torch.equal(out.cpu(), torch.from_numpy(read_mjpeg_avi(path)[0]))
