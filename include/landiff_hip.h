@@ -37,8 +37,9 @@ extern "C" {
  * (additions again).  17: ld_clip_diff_u8 and ld_clip_ssim_u8 were added; ld_retime_u8 joined later (an addition), and so did
  * ld_jpeg_size, ld_jpeg_coefs_u8, ld_jpeg_entropy_i16 and ld_jpeg_encode_u8 (additions again), then ld_jpeg_dec_size,
  * ld_jpeg_find_segments, ld_jpeg_decode_entropy and ld_jpeg_decode_rgb (additions), then ld_gemv_route (an addition), then
- * ld_jpeg_dec_sync_size and ld_jpeg_decode_entropy_sync (additions). */
-#define LD_ABI_VERSION 17
+ * ld_jpeg_dec_sync_size and ld_jpeg_decode_entropy_sync (additions).  18: ld_jpeg_rate_size, ld_jpeg_c8_u8, ld_jpeg_quant_i16 and
+ * ld_jpeg_encode_rate_u8 were added. */
+#define LD_ABI_VERSION 18
 
 int ld_version(void);
 const char* ld_last_error(void);
@@ -757,6 +758,52 @@ int ld_jpeg_encode_u8(const uint8_t* frames, int64_t frame_stride, int64_t row_s
                       const uint8_t* header, int64_t header_bytes, int16_t* coefs_ws, int64_t* seg_ws, uint8_t* out,
                       int64_t out_capacity, int64_t* offsets, int64_t* lengths, int64_t F, int64_t H, int64_t W,
                       int32_t subsampling, int32_t quality, void* stream);
+
+/* ---- rate control for the encode stage (ld_jpeg.hip; landiff_amd/encode.py JpegRateConfig) ----
+ * The encode above with the quality found on the device, so that the streams fit a byte budget.  Sizes are exact: a trial's size is
+ * counted by the counting pass that lays out the final stream (header, every stuffed segment and its marker); nothing is estimated.
+ * Two modes, exactly one a call (the other budget 0): frame_bytes = N, every stream <= N, each frame searching its own quality;
+ * clip_bytes = N, the streams together <= N at one quality for all frames.  The search is a stated bisection between the floor q_min
+ * and the ceiling q_max: lo = q_min - 1, hi = q_max + 1, the first trial is q_max; a trial that fits sets lo = q, another hi = q;
+ * the next trial is (lo + hi) / 2 while hi - lo > 1; the result is max(lo, q_min) with over_budget = (lo == q_min - 1) -- such a
+ * frame is still encoded, at q_min; nothing is cut.  Stream size is not monotone in quality, so the result fits and is this
+ * bisection's, not necessarily the largest quality that fits.  ROUNDS = 1 + ceil(log2(q_max - q_min + 1)) rounds are queued whatever
+ * the data; a frame (clip) that has finished skips the rest, and its trial rows there read (0, 0).
+ * The colour conversion and the DCT run once (c8, 8 x the coefficient before the quantiser: |c8| <= 8192, an int16); a round is
+ * three launches (quantise c8 at every frame's trial quality, the counting pass, the step that applies the rule), the final encode
+ * four (quantise at the chosen qualities, count, layout, write): LAUNCHES = 1 + 3 ROUNDS + 4, no synchronisation, no kernel waits on
+ * another's flag.  Integer arithmetic only, 64-bit offsets; two runs give the same bits.
+ *
+ * ld_jpeg_rate_size: ROUNDS; LAUNCHES; STATE_WORDS = 3 F int32 (state_ws); TRIAL_WORDS = 2 ROUNDS F int64 (trials).  Negative: the
+ * refusal's code (q_min <= q_max outside 1..100, an empty shape, an unsupported geometry). */
+#define LD_JPEG_RATE_SIZE_ROUNDS 0
+#define LD_JPEG_RATE_SIZE_LAUNCHES 1
+#define LD_JPEG_RATE_SIZE_STATE_WORDS 2
+#define LD_JPEG_RATE_SIZE_TRIAL_WORDS 3
+int64_t ld_jpeg_rate_size(int32_t what, int64_t F, int64_t H, int64_t W, int32_t subsampling, int32_t q_min, int32_t q_max);
+
+/* pixels -> c8 int16 [F][FRAME_BLOCKS][64]: ld_jpeg_coefs_u8 up to the quantiser, in its layout (blocks in scan order, zigzag order). */
+int ld_jpeg_c8_u8(const uint8_t* frames, int64_t frame_stride, int64_t row_stride, const int32_t* tables, int16_t* c8, int64_t F,
+                  int64_t H, int64_t W, int32_t subsampling, void* stream);
+
+/* c8 [F][frame_blocks][64] and quality int32 [F] on the device (1..100 each, the caller's to keep; 0: the frame is left untouched)
+ * -> coefs [F][frame_blocks][64], exactly ld_jpeg_coefs_u8's of frame f at quality[f].  One launch. */
+int ld_jpeg_quant_i16(const int16_t* c8, const int32_t* tables, const int32_t* quality, int16_t* coefs, int64_t F,
+                      int64_t frame_blocks, int32_t subsampling, void* stream);
+
+/* ld_jpeg_encode_u8 under a budget.  `header`: one template for the call (any quality's); the writing pass stores frame f's two
+ * 64-byte DQT bodies at dqt_luma and dqt_chroma of its copy (encode.jpeg_dqt_offsets), so that stream f is byte for byte what
+ * ld_jpeg_encode_u8 writes at quality[f].  Workspaces: c8_ws and coefs_ws int16 [F][FRAME_BLOCKS][64]; seg_ws int64 [2][F * SEGMENTS];
+ * state_ws int32 [STATE_WORDS].  Outputs, int64 on the device: offsets, lengths, quality, over_budget [F]; trials [ROUNDS][F][2] =
+ * (quality, that frame's size) of every trial (trials_capacity: its int64 words).  LD_ERR_INVALID, before any launch: a null or
+ * misaligned pointer, q_min or q_max outside 1..100, q_min > q_max, a negative budget, both budgets or neither, DQT offsets outside
+ * the header, out_capacity below ld_jpeg_size's STREAM_BYTES, trials_capacity below TRIAL_WORDS. */
+int ld_jpeg_encode_rate_u8(const uint8_t* frames, int64_t frame_stride, int64_t row_stride, const int32_t* tables,
+                           const uint8_t* header, int64_t header_bytes, int64_t dqt_luma, int64_t dqt_chroma, int16_t* c8_ws,
+                           int16_t* coefs_ws, int64_t* seg_ws, int32_t* state_ws, uint8_t* out, int64_t out_capacity,
+                           int64_t* offsets, int64_t* lengths, int64_t* quality, int64_t* over_budget, int64_t* trials,
+                           int64_t trials_capacity, int64_t F, int64_t H, int64_t W, int32_t subsampling, int32_t q_min,
+                           int32_t q_max, int64_t frame_bytes, int64_t clip_bytes, void* stream);
 
 /* ---- the decode stage (ld_jpeg_dec.hip; landiff_amd/decode.py) ----
  * Baseline JPEG streams on the device -> uint8 RGB frames, integer arithmetic only, equal to libjpeg's (PIL's) decode byte for

@@ -126,6 +126,13 @@ def parse_args(argv=None):
                              "host (the default): the writer of save_video_tensor, unchanged.")
     parser.add_argument("--jpeg_quality", type=int, default=None, metavar="Q",
                         help="With --video_encoder gpu: IJG quality 1..100 (default 95, the host writer's).")
+    parser.add_argument("--jpeg_frame_bytes", type=int, default=None, metavar="N",
+                        help="With --video_encoder gpu: every frame's JPEG stream takes at most N bytes; each frame's quality is "
+                             "searched on the GPU below --jpeg_quality (a stated bisection on exact sizes; landiff_amd/encode.py, "
+                             "DESIGN 8.15).  A frame that does not fit at quality 1 is written there and reported.")
+    parser.add_argument("--video_max_bytes", type=int, default=None, metavar="N",
+                        help="With --video_encoder gpu: the .avi on disk takes at most N bytes; one quality for every frame, searched "
+                             "on the GPU below --jpeg_quality.  <name>_encode.json says so if even quality 1 does not fit.")
     parser.add_argument("--encode_verify", action="store_true",
                         help="With --video_encoder gpu: decode the written streams again on the GPU and add what the file loses "
                              "against the frames it was made from (PSNR, SSIM, the largest difference) to <name>_encode.json.")
@@ -142,15 +149,29 @@ def parse_args(argv=None):
     args = parser.parse_args(argv)
     if args.jpeg_entropy != "segment" and args.video_decoder != "gpu":
         parser.error("--jpeg_entropy goes with --video_decoder gpu")
-    args.jpeg = None
+    args.jpeg = args.jpeg_rate = None
     if args.video_encoder == "gpu":
         from landiff_amd.encode import JpegConfig
         try:
             args.jpeg = JpegConfig(quality=95 if args.jpeg_quality is None else args.jpeg_quality)
         except ValueError as e:
             parser.error(f"--jpeg_quality: {e}")
+        if args.jpeg_frame_bytes is not None and args.video_max_bytes is not None:
+            parser.error("--jpeg_frame_bytes and --video_max_bytes are mutually exclusive")
+        if args.jpeg_frame_bytes is not None:
+            from landiff_amd.encode import JpegRateConfig
+            try:
+                args.jpeg_rate = JpegRateConfig(frame_bytes=args.jpeg_frame_bytes)
+            except ValueError as e:
+                parser.error(f"--jpeg_frame_bytes: {e}")
+        if args.video_max_bytes is not None and args.video_max_bytes < 1:
+            parser.error(f"--video_max_bytes: must be an integer >= 1, got {args.video_max_bytes}")
     elif args.jpeg_quality is not None:
         parser.error("--jpeg_quality goes with --video_encoder gpu")
+    elif args.jpeg_frame_bytes is not None:
+        parser.error("--jpeg_frame_bytes goes with --video_encoder gpu")
+    elif args.video_max_bytes is not None:
+        parser.error("--video_max_bytes goes with --video_encoder gpu")
     elif args.encode_verify:
         parser.error("--encode_verify goes with --video_encoder gpu")
     args.retime = None
@@ -395,18 +416,29 @@ def _write_conform_json(args, last_conform):
         json.dump(last_conform, f, indent=1, allow_nan=False)
 
 
-def _save_encoded(frames, path: str, fps: int, jpeg, verify: bool = False):
+def _save_encoded(frames, path: str, fps: int, jpeg, verify: bool = False, rate=None, max_bytes=None):
     """--video_encoder gpu: uint8 frames [F, H, W, 3] on the device -> <name>.avi (Motion-JPEG, the frames encoded where they are)
     and <name>_encode.json (quality, subsampling, frame count, bytes per frame, total bytes, the table source).  --encode_verify:
-    the streams decoded again on the device (landiff_amd.decode) and compared with the frames: "verify" in the same file."""
+    the streams decoded again on the device (landiff_amd.decode) and compared with the frames: "verify" in the same file.
+    rate (--jpeg_frame_bytes: a JpegRateConfig) or max_bytes (--video_max_bytes: the cap on the .avi, turned into the clip budget
+    mjpeg_avi_stream_budget leaves for this many frames; refused before any launch if nothing is left): the rate-controlled encode
+    (DESIGN 8.15), its report under "rate"."""
     import json
-    from landiff.utils import write_mjpeg_avi_encoded
-    from landiff_amd.encode import encode_jpeg, encode_report
-    jpegs = encode_jpeg(frames, jpeg)
+    from landiff.utils import mjpeg_avi_stream_budget, write_mjpeg_avi_encoded
+    from landiff_amd.encode import JpegRateConfig, encode_jpeg, encode_report
+    if max_bytes is not None:
+        rate = JpegRateConfig(clip_bytes=mjpeg_avi_stream_budget(max_bytes, int(frames.shape[0])))
+    info = None
+    if rate is None:
+        jpegs = encode_jpeg(frames, jpeg)
+    else:
+        jpegs, info = encode_jpeg(frames, jpeg, rate=rate, return_rate=True)
     stem = Path(path).with_suffix("")
     stem.parent.mkdir(parents=True, exist_ok=True)
     write_mjpeg_avi_encoded(jpegs, (int(frames.shape[2]), int(frames.shape[1])), f"{stem}.avi", fps=fps)
-    report = encode_report(jpegs, jpeg)
+    report = encode_report(jpegs, jpeg, rate, info)
+    if max_bytes is not None:
+        report["rate"]["video_max_bytes"] = int(max_bytes)
     if verify:
         from landiff_amd.decode import decode_jpeg
         from landiff_amd.metrics import _jsonable, compare_clips
@@ -422,7 +454,7 @@ def _device_frames(video):
     return (video if video.dtype == torch.uint8 else torch.from_numpy(cthw_to_numpy_images(video))).to(dev).contiguous()
 
 
-def _save_retimed(video, path: str, fps: int, retime, jpeg=None, verify: bool = False):
+def _save_retimed(video, path: str, fps: int, retime, jpeg=None, verify: bool = False, rate=None, max_bytes=None):
     """--out_fps: the clip's frames at `fps` -> the retime stage on the current device -> save_video_tensor at the new rate (with
     --video_encoder gpu: _save_encoded, the retimed frames stay on the device), and <name>_retime.json: the plan (source frame and
     phase of every frame written) and the motion profile of the model's frames."""
@@ -433,7 +465,7 @@ def _save_retimed(video, path: str, fps: int, retime, jpeg=None, verify: bool = 
     if jpeg is None:
         save_video_tensor(retime_clip(frames, plan), path, fps=int(plan.out_fps))
     else:
-        _save_encoded(retime_clip(frames, plan), path, int(plan.out_fps), jpeg, verify)
+        _save_encoded(retime_clip(frames, plan), path, int(plan.out_fps), jpeg, verify, rate, max_bytes)
     report = {"plan": plan.as_dict(),
               "motion": motion_profile(frames, retime.search, retime.penalty, retime.max_sad).as_dict() if frames.shape[0] > 1 else None}
     stem = Path(path).with_suffix("")
@@ -451,10 +483,11 @@ def _save_video(args, video, path: str, fps: int = 8):
     --video_encoder gpu: the video is <name>.avi, its JPEG frames encoded on the device (landiff_amd.encode), with <name>_encode.json."""
     retime, jpeg = getattr(args, "retime", None), getattr(args, "jpeg", None)
     verify = getattr(args, "encode_verify", False)
+    rate, max_bytes = getattr(args, "jpeg_rate", None), getattr(args, "video_max_bytes", None)
     if retime is not None:
-        _save_retimed(video, path, fps, retime, jpeg, verify)
+        _save_retimed(video, path, fps, retime, jpeg, verify, rate, max_bytes)
     elif jpeg is not None:
-        _save_encoded(_device_frames(video), path, fps, jpeg, verify)
+        _save_encoded(_device_frames(video), path, fps, jpeg, verify, rate, max_bytes)
     else:
         save_video_tensor(video, path, fps=fps)
     ref_path = getattr(args, "compare_to", None)

@@ -153,6 +153,30 @@ def write_mjpeg_avi_encoded(jpegs, size, path, fps: int = 8):
         fh.write(b"RIFF" + struct.pack("<I", len(body)) + body)
 
 
+MJPEG_AVI_FIXED_BYTES = 232        # RIFF + size + "AVI " (12), LIST hdrl (12 + avih 64 + LIST strl (12 + strh 64 + strf 48)), LIST movi's head (12), idx1's head (8)
+MJPEG_AVI_FRAME_BYTES = 24         # per frame: the 00dc chunk's head (8) and its idx1 entry (16)
+
+
+def mjpeg_avi_bytes(sizes) -> int:
+    """The exact size of the file write_mjpeg_avi_encoded writes for streams of these sizes (bytes each): the fixed parts, 24 bytes a
+    frame, and every stream padded to an even length.  Pure arithmetic: what a byte budget for the file leaves for the streams."""
+    sizes = [int(n) for n in sizes]
+    if not sizes or min(sizes) < 0:
+        raise ValueError(f"mjpeg_avi_bytes: one size >= 0 per frame, at least one frame, got {sizes!r}")
+    return MJPEG_AVI_FIXED_BYTES + sum(MJPEG_AVI_FRAME_BYTES + n + (n & 1) for n in sizes)
+
+
+def mjpeg_avi_stream_budget(max_bytes: int, T: int) -> int:
+    """What a cap of max_bytes on the .avi leaves for the T streams together: the cap minus the container's bytes for T frames, minus
+    T for the worst case of one padding byte per odd-length stream.  Streams within it give a file within the cap; ValueError when
+    nothing is left."""
+    left = int(max_bytes) - mjpeg_avi_bytes([0] * int(T)) - int(T)
+    if left < 1:
+        raise ValueError(f"a cap of {max_bytes} bytes leaves nothing for the streams of {T} frames: the container alone takes "
+                         f"{mjpeg_avi_bytes([0] * int(T))} bytes, the padding up to {T}")
+    return left
+
+
 def write_mjpeg_avi(images: np.ndarray, path, fps: int = 8, quality: int = 95):
     """Motion-JPEG AVI (RIFF) writer with nothing but PIL for the JPEG frames: the playable fallback when imageio-ffmpeg (the
     reference's H.264 mp4 writer, landiff/utils.py:334-342) is not installed.  images: uint8 [T, H, W, 3]."""

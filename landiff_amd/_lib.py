@@ -44,7 +44,7 @@ class LlmLayer(Structure):
 
 
 _lib = None
-ABI_VERSION = 17         # LD_ABI_VERSION of include/landiff_hip.h that SIGNATURES below were written against
+ABI_VERSION = 18         # LD_ABI_VERSION of include/landiff_hip.h that SIGNATURES below were written against
 
 I64 = c_int64
 I32 = c_int32
@@ -125,6 +125,11 @@ SIGNATURES: dict[str, list] = {
     "ld_jpeg_coefs_u8": [P, I64, I64, P, P, I64, I64, I64, I32, I32, P],
     "ld_jpeg_entropy_i16": [P, P, P, I64, P, I64, I64, I32, P],
     "ld_jpeg_encode_u8": [P, I64, I64, P, P, I64, P, P, P, I64, P, P, I64, I64, I64, I32, I32, P],
+    "ld_jpeg_rate_size": [I32, I64, I64, I64, I32, I32, I32],
+    "ld_jpeg_c8_u8": [P, I64, I64, P, P, I64, I64, I64, I32, P],
+    "ld_jpeg_quant_i16": [P, P, P, P, I64, I64, I32, P],
+    "ld_jpeg_encode_rate_u8": [P, I64, I64, P, P, I64, I64, I64, P, P, P, P, P, I64, P, P, P, P, P, I64, I64, I64, I64, I32, I32, I32,
+                               I64, I64, P],
     "ld_jpeg_dec_size": [I32, I64, I64, I32],
     "ld_jpeg_find_segments": [P, I64, P, P, P, P, I64, I64, I64, I64, I32, P],
     "ld_jpeg_decode_entropy": [P, I64, P, P, P, P, P, I64, P, P, I64, I64, I64, I64, I32, P],
@@ -189,7 +194,7 @@ def load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = (c_char_p if name in ("ld_last_error", "ld_attn_last_kernel") else
-                      ctypes.c_int64 if name in ("ld_groupnorm_stats_blocks", "ld_conv_gn_partials_size", "ld_jpeg_size", "ld_jpeg_dec_size",
+                      ctypes.c_int64 if name in ("ld_groupnorm_stats_blocks", "ld_conv_gn_partials_size", "ld_jpeg_size", "ld_jpeg_rate_size", "ld_jpeg_dec_size",
                                               "ld_jpeg_dec_sync_size")
                       else c_int)
     _lib = lib

@@ -9,6 +9,9 @@ from the DQT and DHT segments of a file PIL (libjpeg-turbo) wrote at quality 50 
 reads them again and compares -- and the kernels receive them as one device array (device_tables).  The rule itself is stated in
 DESIGN 8.12 and restated in numpy in tests/jpeg_ref.py; the kernels are held to that bit for bit.
 
+Rate control (JpegRateConfig, DESIGN 8.15, restated in tests/jpeg_rate_ref.py): the quality is searched on the device, by a stated
+bisection over exact stream sizes, so that every frame or the whole clip fits a byte budget; off unless asked for.
+
 Nothing here runs unless it is asked for.  What quality-95 Motion-JPEG of a trained checkpoint's output looks like is not measured.
 """
 from __future__ import annotations
@@ -168,28 +171,112 @@ def jpeg_header(H: int, W: int, quality: int, subsampling: str) -> bytes:
     return out + seg(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0]))
 
 
-def encode_jpeg(frames, cfg: JpegConfig | None = None, return_device: bool = False):
+JPEG_HEADER_BYTES = 629                       # len(jpeg_header(...)) for any size, quality and subsampling this stage writes
+
+
+def jpeg_dqt_offsets() -> tuple:
+    """Where jpeg_header's two 64-byte quantisation tables (luma, chroma) lie: after SOI (2), APP0 (18) and the DQT's marker, length
+    and table id (5); the chroma DQT follows the luma body.  Headers of two qualities differ in these 128 bytes only, which is what
+    lets the rate-controlled writing pass work from one header template."""
+    luma = 2 + 18 + 5
+    return luma, luma + 64 + 5
+
+
+def rate_rounds(q_min: int, q_max: int) -> int:
+    """The rounds of the rate search: 1 + ceil(log2(q_max - q_min + 1)) (8 for 1..95 and for 1..100), in integers."""
+    if not 1 <= q_min <= q_max <= 100:
+        raise ValueError(f"rate_rounds: 1 <= q_min <= q_max <= 100, got {q_min!r}, {q_max!r}")
+    return 1 + (q_max - q_min).bit_length()
+
+
+@dataclass(frozen=True)
+class JpegRateConfig:
+    """A byte budget for encode_jpeg, exactly one of: frame_bytes (every stream <= it; each frame searches its own
+    quality) and clip_bytes (the streams of the call together <= it; one quality for all frames).  JpegConfig.quality is the
+    search's ceiling and min_quality its floor.  A frame that does not fit at the floor is encoded there and reported over budget."""
+    frame_bytes: int | None = None
+    clip_bytes: int | None = None
+    min_quality: int = 1
+
+    def __post_init__(self):
+        if (self.frame_bytes is None) == (self.clip_bytes is None):
+            raise ValueError(f"JpegRateConfig: give exactly one of frame_bytes and clip_bytes, got {self.frame_bytes!r} and {self.clip_bytes!r}")
+        for name in ("frame_bytes", "clip_bytes"):
+            v = getattr(self, name)
+            if v is not None and (isinstance(v, bool) or not isinstance(v, int) or v < 1):
+                raise ValueError(f"JpegRateConfig: {name} must be an integer >= 1, got {v!r}")
+        if isinstance(self.min_quality, bool) or not isinstance(self.min_quality, int) or not 1 <= self.min_quality <= 100:
+            raise ValueError(f"JpegRateConfig: min_quality must be an integer in 1..100, got {self.min_quality!r}")
+
+    @property
+    def mode(self) -> str:
+        return "frame" if self.clip_bytes is None else "clip"
+
+    @property
+    def budget(self) -> int:
+        return self.frame_bytes if self.clip_bytes is None else self.clip_bytes
+
+
+def encode_jpeg(frames, cfg: JpegConfig | None = None, return_device: bool = False, rate: JpegRateConfig | None = None,
+                return_rate: bool = False):
     """uint8 frames [F, H, W, 3] on the device (the rows may be strided, as a crop of a wider clip is) -> list of F `bytes`, each a
     complete baseline JPEG (ops.jpeg_encode_u8: four launches; then one device-to-host copy of the lengths and one of the streams).
-    return_device: (stream buffer uint8 on the device, offsets int64 [F], lengths int64 [F] on the host) instead."""
+    return_device: (stream buffer uint8 on the device, offsets int64 [F], lengths int64 [F] on the host) instead.
+    rate (a JpegRateConfig): the qualities are searched on the device so that the streams fit the budget (ops.jpeg_encode_rate_u8,
+    DESIGN 8.15; cfg.quality is the ceiling); no frame crosses the bus before the answer is known.  return_rate (with rate): the
+    result is followed by dict(qualities [F], over_budget [F] of bool, trials [R][F][2] = the (quality, size) of every trial; (0, 0)
+    where a frame had finished), which arrive in the same copy as the lengths."""
     import torch
     from . import ops
     cfg = JpegConfig() if cfg is None else cfg
     if not isinstance(cfg, JpegConfig):
         raise TypeError(f"encode_jpeg: expected a JpegConfig, got {type(cfg).__name__}")
-    buf, offsets, lengths = ops.jpeg_encode_u8(frames, cfg.quality, cfg.subsampling)
-    table = torch.stack([offsets, lengths]).cpu()
+    if rate is not None and not isinstance(rate, JpegRateConfig):
+        raise TypeError(f"encode_jpeg: rate must be a JpegRateConfig or None, got {type(rate).__name__}")
+    if return_rate and rate is None:
+        raise ValueError("encode_jpeg: return_rate goes with rate")
+    info = None
+    if rate is None:
+        buf, offsets, lengths = ops.jpeg_encode_u8(frames, cfg.quality, cfg.subsampling)
+        table = torch.stack([offsets, lengths]).cpu()
+    else:
+        if rate.min_quality > cfg.quality:
+            raise ValueError(f"encode_jpeg: min_quality {rate.min_quality} is above the ceiling, JpegConfig.quality = {cfg.quality}")
+        buf, table = ops.jpeg_encode_rate_u8(frames, cfg.quality, cfg.subsampling, frame_bytes=rate.frame_bytes,
+                                             clip_bytes=rate.clip_bytes, q_min=rate.min_quality)
+        table = table.cpu()
+        F = table.shape[1]
+        info = dict(qualities=table[2].tolist(), over_budget=[bool(v) for v in table[3].tolist()],
+                    trials=table[4:].reshape(-1, F, 2).tolist())
     offs, lens = table[0].tolist(), table[1].tolist()
     total = offs[-1] + lens[-1]
     if return_device:
-        return buf[:total], table[0], table[1]
-    raw = buf[:total].cpu().numpy().tobytes()
-    return [raw[o:o + n] for o, n in zip(offs, lens)]
+        res = (buf[:total], table[0], table[1])
+    else:
+        raw = buf[:total].cpu().numpy().tobytes()
+        res = [raw[o:o + n] for o, n in zip(offs, lens)]
+    if return_rate:
+        return (*res, info) if return_device else (res, info)
+    return res
 
 
-def encode_report(jpegs, cfg: JpegConfig) -> dict:
-    """What <name>_encode.json holds."""
+def rate_report(rate: JpegRateConfig, cfg: JpegConfig, info: dict) -> dict:
+    """encode_report's `rate` entry: the mode, the budget, the floor and the ceiling, the rounds queued and the trials the slowest
+    frame took, min / mean / max of the chosen qualities, and the frames that do not fit even at the floor."""
+    q = info["qualities"]
+    return dict(mode=rate.mode, budget=rate.budget, min_quality=rate.min_quality, max_quality=cfg.quality,
+                quality=dict(min=min(q), mean=sum(q) / len(q), max=max(q)),
+                over_budget_frames=[f for f, o in enumerate(info["over_budget"]) if o], rounds=len(info["trials"]),
+                trials_used=max(sum(1 for row in info["trials"] if row[f][0]) for f in range(len(q))))
+
+
+def encode_report(jpegs, cfg: JpegConfig, rate: JpegRateConfig | None = None, rate_info: dict | None = None) -> dict:
+    """What <name>_encode.json holds.  rate, rate_info (encode_jpeg's return_rate): a rate-controlled encode; `quality` is then the
+    search's ceiling and the chosen qualities are under `rate`."""
     sizes = [len(j) for j in jpegs]
-    return dict(encoder="gpu", quality=cfg.quality, subsampling=cfg.subsampling, frames=len(sizes), total_bytes=sum(sizes),
-                bytes_per_frame=dict(min=min(sizes), mean=sum(sizes) / len(sizes), max=max(sizes)), restart_interval="one MCU row",
-                table_source=TABLE_SOURCE)
+    rep = dict(encoder="gpu", quality=cfg.quality, subsampling=cfg.subsampling, frames=len(sizes), total_bytes=sum(sizes),
+               bytes_per_frame=dict(min=min(sizes), mean=sum(sizes) / len(sizes), max=max(sizes)), restart_interval="one MCU row",
+               table_source=TABLE_SOURCE)
+    if rate is not None:
+        rep["rate"] = rate_report(rate, cfg, rate_info)
+    return rep

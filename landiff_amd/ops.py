@@ -1000,6 +1000,95 @@ def jpeg_encode_u8(frames, quality: int, subsampling: str = "420"):
     return out, table[0], table[1]
 
 
+def jpeg_rate_size(what: int, F, H, W, subsampling: str, q_min: int, q_max: int) -> int:
+    """ld_jpeg_rate_size: 0 the rounds of the search 1 + ceil(log2(q_max - q_min + 1)), 1 the launches of ld_jpeg_encode_rate_u8, 2 the
+    int32 words of its state workspace, 3 the int64 words of its trial table (include/landiff_hip.h, LD_JPEG_RATE_SIZE_*).  Needs no GPU."""
+    n = _lib.load().ld_jpeg_rate_size(int(what), int(F), int(H), int(W), _jpeg_sub("jpeg_rate_size", subsampling), int(q_min), int(q_max))
+    if n < 0:
+        check(int(n), "ld_jpeg_rate_size")
+    return int(n)
+
+
+def jpeg_c8_u8(frames, subsampling: str = "420"):
+    """uint8 RGB frames [F, H, W, 3] -> c8 int16 [F, blocks, 64]: jpeg_coefs_u8 up to the quantiser (8 x the DCT coefficient, |c8| <=
+    8192), in its layout.  One launch on the current stream; does not synchronise."""
+    from .encode import device_tables
+    F, H, W = _jpeg_frames("jpeg_c8_u8", frames, 1)
+    sub = _jpeg_sub("jpeg_c8_u8", subsampling)
+    if not frames.is_cuda:
+        raise ValueError("jpeg_c8_u8: the frames must be on the GPU, got a CPU tensor")
+    c8 = torch.empty(F, jpeg_size(0, F, H, W, subsampling), 64, dtype=torch.int16, device=frames.device)
+    check(_lib.load().ld_jpeg_c8_u8(_ptr(frames), frames.stride(0), frames.stride(1), _ptr(device_tables(frames.device)), _ptr(c8),
+                                    F, H, W, sub, _stream()), "ld_jpeg_c8_u8")
+    return c8
+
+
+def jpeg_quant_i16(c8, quality, subsampling: str = "420"):
+    """c8 int16 [F, blocks, 64] (jpeg_c8_u8) and quality int32 [F] on the same device, every entry in 1..100 -> the quantised
+    coefficients int16 [F, blocks, 64]: frame f's are jpeg_coefs_u8's at quality[f].  One launch; the qualities are not read on the
+    host, so keeping them in range is the caller's."""
+    from .encode import device_tables
+    sub = _jpeg_sub("jpeg_quant_i16", subsampling)
+    bpm = 6 if sub == 420 else 3
+    if not isinstance(c8, torch.Tensor) or c8.dtype != torch.int16:
+        raise TypeError(f"jpeg_quant_i16: c8 must be an int16 tensor, got {getattr(c8, 'dtype', type(c8))}")
+    if not isinstance(quality, torch.Tensor) or quality.dtype != torch.int32:
+        raise TypeError(f"jpeg_quant_i16: quality must be an int32 tensor, got {getattr(quality, 'dtype', type(quality))}")
+    if not c8.is_cuda or quality.device != c8.device:
+        raise ValueError(f"jpeg_quant_i16: c8 and quality must be on one GPU, got {c8.device} and {quality.device}")
+    if c8.dim() != 3 or not c8.is_contiguous() or min(c8.shape) < 1 or c8.shape[1] % bpm or c8.shape[2] != 64:
+        raise ValueError(f"jpeg_quant_i16: c8 must be a contiguous [F, blocks (a multiple of {bpm}), 64], got {tuple(c8.shape)}")
+    if quality.dim() != 1 or quality.shape[0] != c8.shape[0] or not quality.is_contiguous():
+        raise ValueError(f"jpeg_quant_i16: quality must be a contiguous [{c8.shape[0]}], got {tuple(quality.shape)}")
+    coefs = torch.empty_like(c8)
+    check(_lib.load().ld_jpeg_quant_i16(_ptr(c8), _ptr(device_tables(c8.device)), _ptr(quality), _ptr(coefs), int(c8.shape[0]),
+                                        int(c8.shape[1]), sub, _stream()), "ld_jpeg_quant_i16")
+    return coefs
+
+
+def jpeg_encode_rate_u8(frames, q_max: int, subsampling: str = "420", frame_bytes=None, clip_bytes=None, q_min: int = 1):
+    """jpeg_encode_u8 under a byte budget: exactly one of frame_bytes (every stream <= it, a quality per frame) and
+    clip_bytes (the streams together <= it, one quality); the qualities are searched in q_min..q_max on the device.  -> (stream
+    buffer uint8 [capacity], table int64 [4 + 2 R, F]), both on the device: table[0] offsets, [1] lengths, [2] qualities, [3]
+    over_budget, table[4:].view(R, F, 2) the (quality, size) of every trial.  1 + 3 R + 4 launches on the current stream; does not
+    synchronise."""
+    from .encode import device_tables, jpeg_dqt_offsets, jpeg_header
+    name = "jpeg_encode_rate_u8"
+    F, H, W = _jpeg_frames(name, frames, q_max)
+    sub = _jpeg_sub(name, subsampling)
+    if isinstance(q_min, bool) or int(q_min) != q_min or not 1 <= q_min <= q_max:
+        raise ValueError(f"{name}: q_min must be an integer in 1..q_max = {q_max}, got {q_min!r}")
+    if (frame_bytes is None) == (clip_bytes is None):
+        raise ValueError(f"{name}: give exactly one of frame_bytes and clip_bytes, got {frame_bytes!r} and {clip_bytes!r}")
+    budget = frame_bytes if clip_bytes is None else clip_bytes
+    if isinstance(budget, bool) or int(budget) != budget or budget < 1:
+        raise ValueError(f"{name}: the budget must be an integer >= 1, got {budget!r}")
+    if not frames.is_cuda:
+        raise ValueError(f"{name}: the frames must be on the GPU, got a CPU tensor")
+    dev = frames.device
+    key = (str(dev), H, W, int(q_max), subsampling)
+    if key not in _JPEG_HEADERS:
+        if len(_JPEG_HEADERS) > 64:
+            _JPEG_HEADERS.clear()
+        _JPEG_HEADERS[key] = torch.frombuffer(bytearray(jpeg_header(H, W, int(q_max), subsampling)), dtype=torch.uint8).to(dev)
+    header = _JPEG_HEADERS[key]
+    dqt = jpeg_dqt_offsets()
+    R = jpeg_rate_size(0, F, H, W, subsampling, q_min, q_max)
+    cap = jpeg_size(4, F, H, W, subsampling, header.numel())
+    c8 = torch.empty(F, jpeg_size(0, F, H, W, subsampling), 64, dtype=torch.int16, device=dev)
+    coefs = torch.empty_like(c8)
+    seg_ws = torch.empty(2, F * jpeg_size(1, F, H, W, subsampling), dtype=torch.int64, device=dev)
+    state = torch.empty(jpeg_rate_size(2, F, H, W, subsampling, q_min, q_max), dtype=torch.int32, device=dev)
+    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    table = torch.empty(4 + 2 * R, F, dtype=torch.int64, device=dev)
+    check(_lib.load().ld_jpeg_encode_rate_u8(_ptr(frames), frames.stride(0), frames.stride(1), _ptr(device_tables(dev)), _ptr(header),
+                                             header.numel(), dqt[0], dqt[1], _ptr(c8), _ptr(coefs), _ptr(seg_ws), _ptr(state),
+                                             _ptr(out), cap, _ptr(table[0]), _ptr(table[1]), _ptr(table[2]), _ptr(table[3]),
+                                             _ptr(table[4]), 2 * R * F, F, H, W, sub, int(q_min), int(q_max),
+                                             int(frame_bytes or 0), int(clip_bytes or 0), _stream()), "ld_jpeg_encode_rate_u8")
+    return out, table
+
+
 def jpeg_dec_size(what: int, H, W, subsampling: str) -> int:
     """ld_jpeg_dec_size: 0 blocks per frame, 1 MCUs per frame, 2 bytes of the plane workspace per frame, 3 words of a table set
     (include/landiff_hip.h, LD_JPEG_DEC_SIZE_*).  Needs no GPU."""

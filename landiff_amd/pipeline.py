@@ -150,13 +150,16 @@ class LanDiffPipeline:
         self._t("retime", t0)
         return out
 
-    def encode(self, frames, cfg=None, verify: bool = False):
+    def encode(self, frames, cfg=None, verify: bool = False, rate=None):
         """uint8 frames [F, H, W, 3] -> list of F `bytes`, each a complete baseline JPEG, encoded on the pipeline's device (cfg: an
         encode.JpegConfig, default quality 95 at 4:2:0; landiff_amd.encode.encode_jpeg): the frames of a Motion-JPEG
         AVI (landiff.utils.write_mjpeg_avi_encoded) or stills.  A function of the frames alone: it takes what __call__,
         generate_stream, extend_video, edit_video or retime returned.  Timed as "encode"; the figures are self.last_encode.
         verify: the streams are decoded again where they are (landiff_amd.decode) and self.last_encode["verify"] holds
-        metrics.compare_clips(frames, decoded) -- PSNR, SSIM, the largest difference: what the written file loses."""
+        metrics.compare_clips(frames, decoded) -- PSNR, SSIM, the largest difference: what the written file loses.
+        rate (an encode.JpegRateConfig): the qualities are searched on the device so that the streams fit a byte budget (DESIGN
+        8.15; cfg.quality is the ceiling); self.last_encode["rate"] holds the mode, the budget, the chosen qualities and the frames
+        over budget, and with verify the figures state the loss at those qualities."""
         from .encode import JpegConfig, encode_jpeg, encode_report
         if not isinstance(frames, torch.Tensor) or frames.dim() != 4 or frames.dtype != torch.uint8 or frames.shape[-1] != 3:
             raise ValueError(f"encode: frames must be uint8 [F, H, W, 3], got {getattr(frames, 'dtype', type(frames))} "
@@ -168,13 +171,15 @@ class LanDiffPipeline:
             if verify:
                 from .decode import decode_jpeg
                 from .metrics import compare_clips
-                buf, offs, lens = encode_jpeg(on_dev, cfg, return_device=True)
+                buf, offs, lens, *info = encode_jpeg(on_dev, cfg, return_device=True, rate=rate, return_rate=rate is not None)
                 raw = buf.cpu().numpy().tobytes()
                 jpegs = [raw[o:o + n] for o, n in zip(offs.tolist(), lens.tolist())]
                 m = compare_clips(on_dev.contiguous(), decode_jpeg((buf, offs, lens))).as_dict()
-            else:
+            elif rate is None:
                 jpegs = encode_jpeg(on_dev, cfg)
-        self.last_encode = encode_report(jpegs, cfg)
+            else:
+                jpegs, *info = encode_jpeg(on_dev, cfg, rate=rate, return_rate=True)
+        self.last_encode = encode_report(jpegs, cfg) if rate is None else encode_report(jpegs, cfg, rate, info[0])
         if verify:
             self.last_encode["verify"] = {"clip": m["clip"], "frames": {k: m["frames"][k] for k in ("psnr", "ssim", "max_abs")}}
         self._t("encode", t0)
