@@ -706,7 +706,7 @@ int ld_retime_u8(const uint8_t* src, uint8_t* dst, const int32_t* src_idx, const
                  int32_t* sad, int64_t F, int64_t n_out, int64_t H, int64_t W, int64_t C, int32_t search, int32_t penalty,
                  int32_t max_sad, void* stream);
 
-/* ---- the encode stage (ld_jpeg.hip; landiff_amd/encode.py) ----
+/* ---- the encode stage (ld_jpeg.hip, the rules it shares in ld_jpeg_dev.h; landiff_amd/encode.py) ----
  * Baseline sequential JPEG of uint8 RGB frames, integer arithmetic only, the restart interval one MCU row: every MCU row of every
  * frame is an independent byte-aligned segment (DC predictors reset, the last byte padded with 1-bits, every 0xFF followed by 0x00).
  * subsampling: 420 (MCU 16 x 16, six blocks Y00 Y01 Y10 Y11 Cb Cr) or 444 (MCU 8 x 8, three blocks).  Frames whose size is no
@@ -759,7 +759,7 @@ int ld_jpeg_encode_u8(const uint8_t* frames, int64_t frame_stride, int64_t row_s
                       int64_t out_capacity, int64_t* offsets, int64_t* lengths, int64_t F, int64_t H, int64_t W,
                       int32_t subsampling, int32_t quality, void* stream);
 
-/* ---- rate control for the encode stage (ld_jpeg.hip; landiff_amd/encode.py JpegRateConfig) ----
+/* ---- rate control for the encode stage (ld_jpeg_rate.hip; ld_jpeg_c8_u8 in ld_jpeg.hip; landiff_amd/encode.py JpegRateConfig) ----
  * The encode above with the quality found on the device, so that the streams fit a byte budget.  Sizes are exact: a trial's size is
  * counted by the counting pass that lays out the final stream (header, every stuffed segment and its marker); nothing is estimated.
  * Two modes, exactly one a call (the other budget 0): frame_bytes = N, every stream <= N, each frame searching its own quality;

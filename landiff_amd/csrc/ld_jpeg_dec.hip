@@ -22,8 +22,9 @@
 // jpeg_colour_kernel: one workgroup per 256 pixels of one output row: chroma upsampling (read clamped to the real chroma size),
 //   colour conversion, the 768 bytes staged in LDS and stored as consecutive bytes.  All offsets are 64-bit.
 // Nothing depends on the order in which lanes or workgroups finish: two runs give the same bits.
-// The table layout, the geometry and the bit reader are ld_jpeg_dec_dev.h's, shared with the second entropy route
-// (ld_jpeg_dec_sync.hip), which also launches jpeg_decode_entropy_kernel under a mask for the segments it hands back.
+// The geometry, the small helpers and the workgroup scan are ld_jpeg_dev.h's, shared with the encode stage; the table layout and the
+// bit reader are ld_jpeg_dec_dev.h's, shared with the second entropy route (ld_jpeg_dec_sync.hip), which also launches
+// jpeg_decode_entropy_kernel under a mask for the segments it hands back.
 #include "ld_jpeg_dec_dev.h"
 
 using namespace ld_jpeg_dec;
@@ -270,8 +271,6 @@ struct ColourArgs {
   long frame_stride, row_stride;
   int H, W, tiles, PH, PW, sub420;
 };
-
-__device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
 
 __global__ __launch_bounds__(kThreads) void jpeg_colour_kernel(ColourArgs a) {
   __shared__ uint8_t line[kThreads * 3];

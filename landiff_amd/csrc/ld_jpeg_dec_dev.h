@@ -1,74 +1,25 @@
 // What the two entropy routes of the decode stage share (ld_jpeg_dec.hip: one lane per restart segment; ld_jpeg_dec_sync.hip: one
-// lane per subsequence of a segment): the layout of a table set, the frame's geometry, the workgroup scan, the bit
-// reader with its Huffman symbol and its EXTENDed value, and the launch of the lane-per-segment kernel under an optional mask.  Integer arithmetic only.
+// lane per subsequence of a segment) beyond ld_jpeg_dev.h: the layout of a table set, the bit reader with its Huffman
+// symbol and its EXTENDed value, and the launch of the lane-per-segment kernel under an optional mask.  Integer arithmetic only.
 #pragma once
-#include "ld_common.h"
-#include "../../include/landiff_hip.h"
+#include "ld_jpeg_dev.h"
 
 namespace ld_jpeg_dec {
 
-constexpr int kMaxWidth = 8192, kMaxHeight = 65535;          // the encoder's limits (ld_jpeg.hip)
+using ld_jpeg::Geom, ld_jpeg::geometry, ld_jpeg::aligned, ld_jpeg::clamp255, ld_jpeg::clampl, ld_jpeg::component_of, ld_jpeg::block_scan;
+
 // offsets into one table set (int32 words; LD_JPEG_DEC_TABLE_WORDS in all)
 constexpr int kTabQuant = 0, kTabHuff = 192, kHuffWords = 544, kTabWords = LD_JPEG_DEC_TABLE_WORDS;
 constexpr int kHuffLimit = 0, kHuffOff = 16, kHuffVals = 32, kHuffLook = 288;      // within one Huffman table
 static_assert(kTabHuff + 6 * kHuffWords == kTabWords, "table layout");
-
-struct Geom {
-  int mcu, bpm, mcux, mcuy, PH, PW;                // MCU edge, blocks per MCU, MCUs per row / column, the planes' padded size
-  long mcus, frame_blocks;
-};
-
-// The geometry of a frame; non-zero: the refusal's code (the message is set).
-inline int geometry(const char* who, int64_t H, int64_t W, int32_t subsampling, Geom* g) {
-  if (subsampling != 420 && subsampling != 444)
-    return ld_set_error(LD_ERR_UNSUPPORTED, "%s: subsampling must be 420 or 444, got %d", who, (int)subsampling);
-  LD_REQUIRE(H > 0 && W > 0, "%s: empty shape", who);
-  if (W > kMaxWidth || H > kMaxHeight)
-    return ld_set_error(LD_ERR_UNSUPPORTED, "%s: frames up to %d wide and %d high are supported, got %lld x %lld (H x W)", who,
-                        kMaxWidth, kMaxHeight, (long long)H, (long long)W);
-  g->mcu = subsampling == 420 ? 16 : 8;
-  g->bpm = subsampling == 420 ? 6 : 3;
-  g->mcux = (int)((W + g->mcu - 1) / g->mcu);
-  g->mcuy = (int)((H + g->mcu - 1) / g->mcu);
-  g->PH = g->mcuy * g->mcu;
-  g->PW = g->mcux * g->mcu;
-  g->mcus = (long)g->mcux * g->mcuy;
-  g->frame_blocks = g->mcus * g->bpm;
-  return LD_OK;
-}
-
-inline bool aligned(const void* p, size_t n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
 
 inline int check_frames(const char* who, int64_t F) {
   LD_REQUIRE(F > 0 && F < (1 << 16), "%s: 1 .. 65535 frames a call, got %lld", who, (long long)F);
   return LD_OK;
 }
 
-__device__ __forceinline__ long clampl(long v, long lo, long hi) { return v < lo ? lo : v > hi ? hi : v; }
-
 // the segments of a frame of `mcus` MCUs at restart interval ri, never more than the table's S rows
 __device__ __forceinline__ long segments_of(long mcus, long ri, long S) { return min(ri > 0 ? (mcus + ri - 1) / ri : 1L, S); }
-
-// the component of block j of an MCU of bpm blocks
-__device__ __forceinline__ int component_of(int j, int bpm) { return bpm == 6 ? (j < 4 ? 0 : j - 3) : j; }
-
-// exclusive scan of one value per thread over a workgroup of kN threads (tmp: kN values in LDS); the total is returned to every thread
-template <int kN, typename V>
-__device__ __forceinline__ V block_scan(V v, V* tmp, V* total) {
-  const int tid = threadIdx.x;
-  tmp[tid] = v;
-  __syncthreads();
-  for (int o = 1; o < kN; o <<= 1) {
-    const V add = tid >= o ? tmp[tid - o] : 0;
-    __syncthreads();
-    tmp[tid] += add;
-    __syncthreads();
-  }
-  const V incl = tmp[tid];
-  *total = tmp[kN - 1];
-  __syncthreads();
-  return incl - v;
-}
 
 // The next bits of one segment, p[0 .. end): a 64-bit buffer filled byte by byte from bit 63 down, zeros past the segment's end;
 // after a 0xFF the next byte (the stuffed 0x00) is skipped.  p[pos] is read only with pos < end.

@@ -9,8 +9,9 @@ from the DQT and DHT segments of a file PIL (libjpeg-turbo) wrote at quality 50 
 reads them again and compares -- and the kernels receive them as one device array (device_tables).  The rule itself is stated in
 DESIGN 8.12 and restated in numpy in tests/jpeg_ref.py; the kernels are held to that bit for bit.
 
-Rate control (JpegRateConfig, DESIGN 8.15, restated in tests/jpeg_rate_ref.py): the quality is searched on the device, by a stated
-bisection over exact stream sizes, so that every frame or the whole clip fits a byte budget; off unless asked for.
+Rate control (JpegRateConfig, csrc/ld_jpeg_rate.hip, DESIGN 8.15, restated in tests/jpeg_rate_ref.py): the quality is searched on
+the device, by a stated bisection over exact stream sizes, so that every frame or the whole clip fits a byte budget; off unless
+asked for.
 
 Nothing here runs unless it is asked for.  What quality-95 Motion-JPEG of a trained checkpoint's output looks like is not measured.
 """
@@ -20,7 +21,7 @@ import struct
 from dataclasses import dataclass
 
 SUBSAMPLINGS = ("420", "444")
-MAX_WIDTH, MAX_HEIGHT = 8192, 65535          # kMaxWidth / kMaxHeight of csrc/ld_jpeg.hip
+MAX_WIDTH, MAX_HEIGHT = 8192, 65535          # kMaxWidth / kMaxHeight of csrc/ld_jpeg_dev.h
 TABLE_SOURCE = "Annex K tables as written by PIL (libjpeg-turbo) at quality 50, optimize=False"
 
 # ---- the tables, as the DQT / DHT segments hold them ----

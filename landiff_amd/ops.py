@@ -920,13 +920,18 @@ def _jpeg_sub(name, subsampling) -> int:
     return int(subsampling)
 
 
+def _jpeg_size(symbol, *args) -> int:
+    """One of the library's *_size questions: the answer, or its refusal raised."""
+    n = getattr(_lib.load(), symbol)(*args)
+    if n < 0:
+        check(int(n), symbol)
+    return int(n)
+
+
 def jpeg_size(what: int, F, H, W, subsampling: str, header_bytes: int = 0) -> int:
     """ld_jpeg_size: 0 blocks per frame, 1 segments (MCU rows) per frame, 2 blocks per segment, 3 the most bytes of a segment, 4 the
     most bytes of F streams with their headers (include/landiff_hip.h, LD_JPEG_SIZE_*).  Needs no GPU."""
-    n = _lib.load().ld_jpeg_size(int(what), int(F), int(H), int(W), _jpeg_sub("jpeg_size", subsampling), int(header_bytes))
-    if n < 0:
-        check(int(n), "ld_jpeg_size")
-    return int(n)
+    return _jpeg_size("ld_jpeg_size", int(what), int(F), int(H), int(W), _jpeg_sub("jpeg_size", subsampling), int(header_bytes))
 
 
 def _jpeg_frames(name, frames, quality):
@@ -974,25 +979,36 @@ def jpeg_entropy_i16(coefs, mcus_per_row: int, subsampling: str = "420"):
 _JPEG_HEADERS: dict = {}
 
 
+def _jpeg_header_on(device, H, W, quality, subsampling):
+    """encode.jpeg_header of such frames as a uint8 tensor on the device, cached."""
+    from .encode import jpeg_header
+    key = (str(device), H, W, int(quality), subsampling)
+    if key not in _JPEG_HEADERS:
+        if len(_JPEG_HEADERS) > 64:
+            _JPEG_HEADERS.clear()
+        _JPEG_HEADERS[key] = torch.frombuffer(bytearray(jpeg_header(H, W, int(quality), subsampling)), dtype=torch.uint8).to(device)
+    return _JPEG_HEADERS[key]
+
+
+def _jpeg_encode_buffers(device, F, H, W, subsampling, header):
+    """What both encode wrappers allocate -> (capacity, coefficients int16 [F, blocks, 64], seg_ws int64 [2, segments], out uint8 [capacity])."""
+    cap = jpeg_size(4, F, H, W, subsampling, header.numel())
+    coefs = torch.empty(F, jpeg_size(0, F, H, W, subsampling), 64, dtype=torch.int16, device=device)
+    seg_ws = torch.empty(2, F * jpeg_size(1, F, H, W, subsampling), dtype=torch.int64, device=device)
+    return cap, coefs, seg_ws, torch.empty(cap, dtype=torch.uint8, device=device)
+
+
 def jpeg_encode_u8(frames, quality: int, subsampling: str = "420"):
     """uint8 RGB frames [F, H, W, 3] -> (stream buffer uint8 [capacity], offsets int64 [F], lengths int64 [F]), all on the device:
     frame f's complete baseline JPEG is buffer[offsets[f] : offsets[f] + lengths[f]], the frames back to back.  The buffer is sized
     by ld_jpeg_size's bound (nothing is ever cut to fit); only the streams' bytes of it are touched.  Four launches on the current
     stream; does not synchronise."""
-    from .encode import device_tables, jpeg_header
+    from .encode import device_tables
     F, H, W = _jpeg_frames("jpeg_encode_u8", frames, quality)
     sub = _jpeg_sub("jpeg_encode_u8", subsampling)
     dev = frames.device
-    key = (str(dev), H, W, int(quality), subsampling)
-    if key not in _JPEG_HEADERS:
-        if len(_JPEG_HEADERS) > 64:
-            _JPEG_HEADERS.clear()
-        _JPEG_HEADERS[key] = torch.frombuffer(bytearray(jpeg_header(H, W, int(quality), subsampling)), dtype=torch.uint8).to(dev)
-    header = _JPEG_HEADERS[key]
-    cap = jpeg_size(4, F, H, W, subsampling, header.numel())
-    coefs = torch.empty(F, jpeg_size(0, F, H, W, subsampling), 64, dtype=torch.int16, device=dev)
-    seg_ws = torch.empty(2, F * jpeg_size(1, F, H, W, subsampling), dtype=torch.int64, device=dev)
-    out = torch.empty(cap, dtype=torch.uint8, device=dev)
+    header = _jpeg_header_on(dev, H, W, quality, subsampling)
+    cap, coefs, seg_ws, out = _jpeg_encode_buffers(dev, F, H, W, subsampling, header)
     table = torch.empty(2, F, dtype=torch.int64, device=dev)
     check(_lib.load().ld_jpeg_encode_u8(_ptr(frames), frames.stride(0), frames.stride(1), _ptr(device_tables(dev)), _ptr(header),
                                         header.numel(), _ptr(coefs), _ptr(seg_ws), _ptr(out), cap, _ptr(table[0]), _ptr(table[1]),
@@ -1003,10 +1019,7 @@ def jpeg_encode_u8(frames, quality: int, subsampling: str = "420"):
 def jpeg_rate_size(what: int, F, H, W, subsampling: str, q_min: int, q_max: int) -> int:
     """ld_jpeg_rate_size: 0 the rounds of the search 1 + ceil(log2(q_max - q_min + 1)), 1 the launches of ld_jpeg_encode_rate_u8, 2 the
     int32 words of its state workspace, 3 the int64 words of its trial table (include/landiff_hip.h, LD_JPEG_RATE_SIZE_*).  Needs no GPU."""
-    n = _lib.load().ld_jpeg_rate_size(int(what), int(F), int(H), int(W), _jpeg_sub("jpeg_rate_size", subsampling), int(q_min), int(q_max))
-    if n < 0:
-        check(int(n), "ld_jpeg_rate_size")
-    return int(n)
+    return _jpeg_size("ld_jpeg_rate_size", int(what), int(F), int(H), int(W), _jpeg_sub("jpeg_rate_size", subsampling), int(q_min), int(q_max))
 
 
 def jpeg_c8_u8(frames, subsampling: str = "420"):
@@ -1052,7 +1065,7 @@ def jpeg_encode_rate_u8(frames, q_max: int, subsampling: str = "420", frame_byte
     buffer uint8 [capacity], table int64 [4 + 2 R, F]), both on the device: table[0] offsets, [1] lengths, [2] qualities, [3]
     over_budget, table[4:].view(R, F, 2) the (quality, size) of every trial.  1 + 3 R + 4 launches on the current stream; does not
     synchronise."""
-    from .encode import device_tables, jpeg_dqt_offsets, jpeg_header
+    from .encode import device_tables, jpeg_dqt_offsets
     name = "jpeg_encode_rate_u8"
     F, H, W = _jpeg_frames(name, frames, q_max)
     sub = _jpeg_sub(name, subsampling)
@@ -1066,20 +1079,12 @@ def jpeg_encode_rate_u8(frames, q_max: int, subsampling: str = "420", frame_byte
     if not frames.is_cuda:
         raise ValueError(f"{name}: the frames must be on the GPU, got a CPU tensor")
     dev = frames.device
-    key = (str(dev), H, W, int(q_max), subsampling)
-    if key not in _JPEG_HEADERS:
-        if len(_JPEG_HEADERS) > 64:
-            _JPEG_HEADERS.clear()
-        _JPEG_HEADERS[key] = torch.frombuffer(bytearray(jpeg_header(H, W, int(q_max), subsampling)), dtype=torch.uint8).to(dev)
-    header = _JPEG_HEADERS[key]
+    header = _jpeg_header_on(dev, H, W, q_max, subsampling)
     dqt = jpeg_dqt_offsets()
     R = jpeg_rate_size(0, F, H, W, subsampling, q_min, q_max)
-    cap = jpeg_size(4, F, H, W, subsampling, header.numel())
-    c8 = torch.empty(F, jpeg_size(0, F, H, W, subsampling), 64, dtype=torch.int16, device=dev)
-    coefs = torch.empty_like(c8)
-    seg_ws = torch.empty(2, F * jpeg_size(1, F, H, W, subsampling), dtype=torch.int64, device=dev)
+    cap, coefs, seg_ws, out = _jpeg_encode_buffers(dev, F, H, W, subsampling, header)
+    c8 = torch.empty_like(coefs)
     state = torch.empty(jpeg_rate_size(2, F, H, W, subsampling, q_min, q_max), dtype=torch.int32, device=dev)
-    out = torch.empty(cap, dtype=torch.uint8, device=dev)
     table = torch.empty(4 + 2 * R, F, dtype=torch.int64, device=dev)
     check(_lib.load().ld_jpeg_encode_rate_u8(_ptr(frames), frames.stride(0), frames.stride(1), _ptr(device_tables(dev)), _ptr(header),
                                              header.numel(), dqt[0], dqt[1], _ptr(c8), _ptr(coefs), _ptr(seg_ws), _ptr(state),
@@ -1092,10 +1097,7 @@ def jpeg_encode_rate_u8(frames, q_max: int, subsampling: str = "420", frame_byte
 def jpeg_dec_size(what: int, H, W, subsampling: str) -> int:
     """ld_jpeg_dec_size: 0 blocks per frame, 1 MCUs per frame, 2 bytes of the plane workspace per frame, 3 words of a table set
     (include/landiff_hip.h, LD_JPEG_DEC_SIZE_*).  Needs no GPU."""
-    n = _lib.load().ld_jpeg_dec_size(int(what), int(H), int(W), _jpeg_sub("jpeg_dec_size", subsampling))
-    if n < 0:
-        check(int(n), "ld_jpeg_dec_size")
-    return int(n)
+    return _jpeg_size("ld_jpeg_dec_size", int(what), int(H), int(W), _jpeg_sub("jpeg_dec_size", subsampling))
 
 
 def _jpeg_dec_arg(name, what, t, dtype, shape=None):
@@ -1104,6 +1106,27 @@ def _jpeg_dec_arg(name, what, t, dtype, shape=None):
     if shape is not None and tuple(t.shape) != tuple(shape):
         raise ValueError(f"{name}: {what} must be {tuple(shape)}, got {tuple(t.shape)}")
     return t
+
+
+def _jpeg_dec_tables(name, tables, H, W, subsampling):
+    words = jpeg_dec_size(3, H, W, subsampling)
+    if _jpeg_dec_arg(name, "tables", tables, torch.int32).dim() != 2 or tables.shape[0] < 1 or tables.shape[1] != words:
+        raise ValueError(f"{name}: tables must be [n_sets, {words}], got {tuple(tables.shape)}")
+
+
+def _jpeg_dec_inputs(name, data, seg_table, frame_info, ri, tables, tset, H, W, subsampling):
+    """What both entropy routes check of their inputs -> (F, S, the library's subsampling code)."""
+    sub = _jpeg_sub(name, subsampling)
+    _jpeg_dec_arg(name, "data", data, torch.uint8)
+    F = int(_jpeg_dec_arg(name, "ri", ri, torch.int32).numel())
+    if seg_table.dim() != 3 or F < 1:
+        raise ValueError(f"{name}: the segment table must be [F, rows, 5], got {tuple(seg_table.shape)}")
+    S = int(seg_table.shape[1])
+    _jpeg_dec_arg(name, "seg_table", seg_table, torch.int64, (F, S, 5))
+    _jpeg_dec_arg(name, "frame_info", frame_info, torch.int64, (F, 3))
+    _jpeg_dec_arg(name, "tset", tset, torch.int32, (F,))
+    _jpeg_dec_tables(name, tables, H, W, subsampling)
+    return F, S, sub
 
 
 def jpeg_find_segments(data, scan, ri, n_rows: int, H: int, W: int, subsampling: str = "420"):
@@ -1128,19 +1151,7 @@ def jpeg_decode_entropy(data, seg_table, frame_info, ri, tables, tset, H: int, W
     """The segments of jpeg_find_segments -> (coefficients int16 [F, blocks, 64] in ld_jpeg_coefs_u8's layout, status int32 [F, rows],
     decode.STATUS per segment).  tables int32 [n_sets, words] (decode.decode_tables), tset int32 [F] the set of every frame.  One
     launch, one lane per segment; does not synchronise."""
-    name = "jpeg_decode_entropy"
-    sub = _jpeg_sub(name, subsampling)
-    _jpeg_dec_arg(name, "data", data, torch.uint8)
-    F = int(_jpeg_dec_arg(name, "ri", ri, torch.int32).numel())
-    if seg_table.dim() != 3 or F < 1:
-        raise ValueError(f"{name}: the segment table must be [F, rows, 5], got {tuple(seg_table.shape)}")
-    S = int(seg_table.shape[1])
-    _jpeg_dec_arg(name, "seg_table", seg_table, torch.int64, (F, S, 5))
-    _jpeg_dec_arg(name, "frame_info", frame_info, torch.int64, (F, 3))
-    _jpeg_dec_arg(name, "tset", tset, torch.int32, (F,))
-    words = jpeg_dec_size(3, H, W, subsampling)
-    if _jpeg_dec_arg(name, "tables", tables, torch.int32).dim() != 2 or tables.shape[0] < 1 or tables.shape[1] != words:
-        raise ValueError(f"{name}: tables must be [n_sets, {words}], got {tuple(tables.shape)}")
+    F, S, sub = _jpeg_dec_inputs("jpeg_decode_entropy", data, seg_table, frame_info, ri, tables, tset, H, W, subsampling)
     coefs = torch.empty(F, jpeg_dec_size(0, H, W, subsampling), 64, dtype=torch.int16, device=data.device)
     status = torch.empty(F, S, dtype=torch.int32, device=data.device)
     check(_lib.load().ld_jpeg_decode_entropy(_ptr(data), data.numel(), _ptr(seg_table), _ptr(frame_info), _ptr(ri), _ptr(tables),
@@ -1152,10 +1163,7 @@ def jpeg_decode_entropy(data, seg_table, frame_info, ri, tables, tset, H: int, W
 def jpeg_dec_sync_size(what: int, scan_bytes: int, F: int, S: int, sub_bytes: int = 256, max_rounds: int = 32) -> int:
     """ld_jpeg_dec_sync_size: 0 bytes of jpeg_decode_entropy_sync's workspace, 1 rows of its flat list of subsequences (and of the
     exit table), from what the host knows: the frames' summed scan bytes, F frames of at most S segments.  Needs no GPU."""
-    n = _lib.load().ld_jpeg_dec_sync_size(int(what), int(scan_bytes), int(F), int(S), int(sub_bytes), int(max_rounds))
-    if n < 0:
-        check(int(n), "ld_jpeg_dec_sync_size")
-    return int(n)
+    return _jpeg_size("ld_jpeg_dec_sync_size", int(what), int(scan_bytes), int(F), int(S), int(sub_bytes), int(max_rounds))
 
 
 def jpeg_decode_entropy_sync(data, seg_table, frame_info, ri, tables, tset, H: int, W: int, subsampling: str = "420",
@@ -1166,19 +1174,7 @@ def jpeg_decode_entropy_sync(data, seg_table, frame_info, ri, tables, tset, H: i
     = (first row, rows) of every segment)]).  Coefficients and status are jpeg_decode_entropy's whatever max_rounds is.
     scan_bytes: the frames' summed scan bytes where the caller knows them (default: all of data); it sizes the grids.  A fixed
     number of launches; does not synchronise."""
-    name = "jpeg_decode_entropy_sync"
-    sub = _jpeg_sub(name, subsampling)
-    _jpeg_dec_arg(name, "data", data, torch.uint8)
-    F = int(_jpeg_dec_arg(name, "ri", ri, torch.int32).numel())
-    if seg_table.dim() != 3 or F < 1:
-        raise ValueError(f"{name}: the segment table must be [F, rows, 5], got {tuple(seg_table.shape)}")
-    S = int(seg_table.shape[1])
-    _jpeg_dec_arg(name, "seg_table", seg_table, torch.int64, (F, S, 5))
-    _jpeg_dec_arg(name, "frame_info", frame_info, torch.int64, (F, 3))
-    _jpeg_dec_arg(name, "tset", tset, torch.int32, (F,))
-    words = jpeg_dec_size(3, H, W, subsampling)
-    if _jpeg_dec_arg(name, "tables", tables, torch.int32).dim() != 2 or tables.shape[0] < 1 or tables.shape[1] != words:
-        raise ValueError(f"{name}: tables must be [n_sets, {words}], got {tuple(tables.shape)}")
+    F, S, sub = _jpeg_dec_inputs("jpeg_decode_entropy_sync", data, seg_table, frame_info, ri, tables, tset, H, W, subsampling)
     scan_bytes = data.numel() if scan_bytes is None else min(int(scan_bytes), data.numel())
     ws_bytes = jpeg_dec_sync_size(0, scan_bytes, F, S, sub_bytes, max_rounds)
     dev = data.device
@@ -1203,14 +1199,13 @@ def jpeg_decode_rgb(coefs, tables, tset, H: int, W: int, subsampling: str = "420
     strided, e.g. a window of a wider buffer).  Two launches; does not synchronise."""
     name = "jpeg_decode_rgb"
     sub = _jpeg_sub(name, subsampling)
-    blocks, words = jpeg_dec_size(0, H, W, subsampling), jpeg_dec_size(3, H, W, subsampling)
+    blocks = jpeg_dec_size(0, H, W, subsampling)
     if not isinstance(coefs, torch.Tensor) or coefs.dim() != 3:
         raise TypeError(f"{name}: the coefficients must be an int16 tensor [F, {blocks}, 64]")
     F = int(coefs.shape[0])
     _jpeg_dec_arg(name, "coefs", coefs, torch.int16, (F, blocks, 64))
     _jpeg_dec_arg(name, "tset", tset, torch.int32, (F,))
-    if _jpeg_dec_arg(name, "tables", tables, torch.int32).dim() != 2 or tables.shape[0] < 1 or tables.shape[1] != words:
-        raise ValueError(f"{name}: tables must be [n_sets, {words}], got {tuple(tables.shape)}")
+    _jpeg_dec_tables(name, tables, H, W, subsampling)
     if out is None:
         out = torch.empty(F, int(H), int(W), 3, dtype=torch.uint8, device=coefs.device)
     if (not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != (F, int(H), int(W), 3)

@@ -1,5 +1,5 @@
 """The rate control rule of the encode stage restated in plain Python / numpy on tests/jpeg_ref.py, for the tests of
-landiff_amd/encode.py's JpegRateConfig and csrc/ld_jpeg.hip's rate entry points.
+landiff_amd/encode.py's JpegRateConfig and csrc/ld_jpeg_rate.hip's entry points.
 
 Sizes are exact: the size of frame f at quality q is len(jpeg_ref.jpeg_encode(frame[None], q, sub)[0]) -- the header, every stuffed
 segment and its marker.  "Fits" means size <= budget.  Two modes: frame (every frame searches its own quality under frame_bytes) and

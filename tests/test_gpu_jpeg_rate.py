@@ -1,4 +1,4 @@
-"""Rate control of the encode stage on the GPU (landiff_amd/encode.py JpegRateConfig, csrc/ld_jpeg.hip) against the
+"""Rate control of the encode stage on the GPU (landiff_amd/encode.py JpegRateConfig, csrc/ld_jpeg_rate.hip) against the
 restatement tests/jpeg_rate_ref.py: torch.equal and bytes == throughout, no tolerance."""
 import io
 import json
